@@ -12,7 +12,11 @@ rank t % N), the scene is replicated, total work is fixed: strong scaling.
 `value` = BVH queries of all ranks / max-over-ranks wall time (scene build,
 upload and file I/O excluded -- the region the reference times, main.rs:59-100).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps frames,
+writes the last timed frame with --dump-outputs DIR, and prints the headline: metric, value, unit, ms_per_step, the
+workload.  With --full the line also carries (each --no-* option still leaves its part out)
+  framebuffer_checksum / framebuffer_sha256 -- of the assembled frame, and, with frames in flight, the un-pipelined
+                  figure and the duration of a frame rendered alone;
   roofline     -- the kernel with the largest share of the step (named in `kernel`; every kernel's share and
                   fraction is in `kernels`) against the ceiling that binds it, FP64-rate vector issue: useful
                   lane-operations per launch (the frame's work counters x the operation model below) / its
@@ -318,6 +322,24 @@ def ray_shares(cst, config, n_surfaces):
     return {k: round(v, 4) for k, v in out.items()}
 
 
+DUMP_FRAME_BYTES = 60_000_000   # --dump-outputs writes at most 64 MB in all
+
+
+def dump_outputs(out_dir, frame, rays):
+    """--dump-outputs: what a caller of the timed path receives for the last timed step -- the f32x3 framebuffer
+    (H, W, 3) and the step's BVH query count (all ranks) -- as framebuffer.npy (float32) and rays.npy (float64).  A
+    framebuffer larger than DUMP_FRAME_BYTES is written as a fixed, seeded sample of its pixels (n, 3), in pixel order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    fb = np.ascontiguousarray(frame, dtype=np.float32)
+    if fb.nbytes > DUMP_FRAME_BYTES:
+        px = fb.reshape(-1, 3)
+        keep = DUMP_FRAME_BYTES // (3 * px.itemsize)
+        fb = px[np.sort(np.random.default_rng(0x5EED).choice(px.shape[0], keep, replace=False))]
+    np.save(os.path.join(out_dir, "framebuffer.npy"), fb)
+    np.save(os.path.join(out_dir, "rays.npy"), np.array([rays], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -359,12 +381,23 @@ def main():
     ap.add_argument("--no-build", action="store_true",
                     help="do not run make: required under rocprofv3 (a profiled process must not spawn the compiler); "
                          "fails if the library is older than its sources")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well: the frame's checksum and sha256, "
+                         "roofline and ray shares (a counting launch), with frames in flight the un-pipelined figure, the "
+                         "secondary, fast and configs blocks and the CPU baseline (the --no-* options leave parts out); "
+                         "without it a run sets up, warms up, times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy: framebuffer.npy "
+                         "(float32, H x W x 3) and rays.npy (float64, its BVH queries)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import numpy as np
     import torch
 
-    load_op_model()
+    if args.full:
+        load_op_model()
     import __graft_entry__ as graft
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -475,8 +508,10 @@ def main():
     def workload_key(cx, W, H, chunk, camera=None):
         return f"config{cx.config}_{camera or args.camera}_{W}x{H}_{cx.spp}spp_chunk{chunk}_world{world}"
 
-    def measure(cx, cam_args, steps, warmup, want_roofline, fast=False):
-        """Times `steps` frames of the scene in `cx` from this camera; returns the pieces of the JSON line."""
+    def measure(cx, cam_args, steps, warmup, want_roofline, fast=False, extras=True, keep_frame=False):
+        """Times `steps` frames of the scene in `cx` from this camera; returns the pieces of the JSON line.  extras: the
+        frame's checksum and sha256 and, with frames in flight, the un-pipelined figure (--full); keep_frame: rank 0
+        returns the last timed frame in host memory (--dump-outputs)."""
         scene, flights, n_flights, objs, info, spp, max_bounces = cx.scene, cx.flights, cx.n_flights, cx.objs, cx.info, cx.spp, cx.max_bounces
         cam = rayrs_amd.Camera(*cam_args)
         H, W = cam.y_pixels(), cam.x_pixels()
@@ -574,10 +609,11 @@ def main():
         st = timed[-1]
         fb = fbs[(steps - 1) % F]
         rays = sum(t["rays"] for t in timed)
+        frame = fb.cpu().numpy() if (keep_frame and rank == 0) else None
         # frames in flight make ms_per_step a throughput figure; beside it, the same frames one after the other (one
         # flight: render, reduce, next frame), so that an N-GPU line can be read against the 1-GPU line like for like
         unpipelined_s = None
-        if F > 1:
+        if F > 1 and extras:
             fence()
             t_u = time.perf_counter()
             frames(2, nf=1)
@@ -599,19 +635,20 @@ def main():
         hit_ms = [t["hit_ms"] for t in timed_for_kernels]
         miss_ms = [t["miss_ms"] for t in timed_for_kernels]
 
-        tot = torch.tensor([float(rays), elapsed, unpipelined_s or 0.0], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+        tot = torch.tensor([float(rays), float(st["rays"]), elapsed, unpipelined_s or 0.0], dtype=torch.float64,
+                           device=dev if args.backend == "nccl" else "cpu")
         if use_dist:
-            r = tot[:1].clone()
-            e = tot[1:].clone()
+            r = tot[:2].clone()
+            e = tot[2:].clone()
             dist.all_reduce(r, op=dist.ReduceOp.SUM)
             dist.all_reduce(e, op=dist.ReduceOp.MAX)
-            total_rays, max_elapsed = float(r.item()), float(e[0].item())
+            total_rays, last_rays, max_elapsed = float(r[0].item()), float(r[1].item()), float(e[0].item())
             if unpipelined_s is not None:
                 unpipelined_s = float(e[1].item())
         else:
-            total_rays, max_elapsed = float(rays), elapsed
-        checksum, fb_sha = 0.0, None
-        if rank == 0:  # the assembled frame: identical bits for every rank count (tests/test_gpu_multi_process.py)
+            total_rays, last_rays, max_elapsed = float(rays), float(st["rays"]), elapsed
+        checksum, fb_sha = None, None
+        if rank == 0 and extras:  # the assembled frame: identical bits for every rank count (tests/test_gpu_multi_process.py)
             checksum = float(fb.double().sum().item())
             fb_sha = hashlib.sha256(fb.cpu().numpy().tobytes()).hexdigest()
 
@@ -753,13 +790,17 @@ def main():
                 "frame_alone_ms": alone_ms,
                 "ms_per_step": max_elapsed / steps * 1e3, "rays_per_step": int(total_rays / steps),
                 "checksum": checksum, "sha": fb_sha, "roofline": roofline, "shares": shares,
+                "frame": frame, "last_rays": last_rays,
                 "exact_walk": int(st["exact_walk"]), "local_pool": int(st["local_pool"]), "hot_group": int(st["hot_group"])}
 
-    main_run = measure(cx, cam_args, args.steps, args.warmup, not args.no_roofline, fast=args.fast_traversal)
+    main_run = measure(cx, cam_args, args.steps, args.warmup, args.full and not args.no_roofline, fast=args.fast_traversal,
+                       extras=args.full, keep_frame=args.dump_outputs is not None)
     W, H, chunk = main_run["W"], main_run["H"], main_run["chunk"]
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, main_run.pop("frame"), main_run["last_rays"])
 
     secondary = None
-    if (args.config == 5 and args.camera == "reference" and world == 1 and not reduced and not args.no_secondary
+    if (args.full and args.config == 5 and args.camera == "reference" and world == 1 and not reduced and not args.no_secondary
             and not args.no_roofline):
         close = scenes.camera_for_resolution(scenes.MESH_CLOSE_CAM, W0, H0)
         sec = measure(cx, close, 3, 1, True)
@@ -772,7 +813,7 @@ def main():
                      "roofline_frac": sec["roofline"]["frac"]}
 
     fast_block = None
-    if (args.config == 5 and args.camera == "reference" and world == 1 and not reduced and not args.no_fast
+    if (args.full and args.config == 5 and args.camera == "reference" and world == 1 and not reduced and not args.no_fast
             and not args.no_roofline and not args.fast_traversal and not main_run["local_pool"]):
         fr = measure(cx, cam_args, 3, 1, True, fast=True)
         # (reported, not asserted: the headline line must not be lost to its companion measurement; the tests pin it)
@@ -793,7 +834,7 @@ def main():
     # BASELINE.json configs[0..3] at full size beside the headline (on the driver's record, not only in
     # profiles/): 1 untimed + 3 timed frames each, the kernel with the largest share of the step priced as the headline's is
     configs_block = None
-    if (args.config == 5 and args.camera == "reference" and world == 1 and not reduced and not args.no_configs
+    if (args.full and args.config == 5 and args.camera == "reference" and world == 1 and not reduced and not args.no_configs
             and not args.no_roofline and not args.fast_traversal):
         configs_block = []
         for n in (1, 2, 3, 4):
@@ -813,7 +854,7 @@ def main():
             del c, r
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import _oracle
         ncores = effective_cores()

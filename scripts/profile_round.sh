@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, through gpurun): bash scripts/profile_round.sh <tag> [bench.py flags, e.g. --config 3]
 # Produces under gpurun_out/<tag>/:
-#   bench.json         the full line `python bench.py [flags]` prints
+#   bench.json         the full line `python bench.py --full [flags]` prints
 #   kernel_stats.csv   rocprofv3 --kernel-trace --stats of ONE bench step (same flags)
 #   pmc.json           per-kernel PMC sums of the same step, stamped with the source hash and the workload key
 #                      bench.py matches them by: fabric bytes (32 B x TCC_EA0_RDREQ_DRAM_32B / WRREQ_WRITE_DRAM_32B,
@@ -64,5 +64,5 @@ rm -rf $OUT/pmc_mem $OUT/pmc_sq $OUT/stats
 # fp64_valu_busy from profiles/*_pmc.json when its source hash and workload key match
 cp $OUT/pmc.json $ROOT/profiles/${TAG}_pmc.json
 cd $ROOT
-python bench.py --no-build "$@" > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --no-build --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 tail -c 200 $OUT/bench.json; echo

@@ -3,16 +3,19 @@ torch.distributed.run with two ranks (tile_rank = RANK, the framebuffer reduce, 
 both ranks on HIP device 0 and the reduce through gloo -- RCCL cannot put two ranks on one device.
 The assembled frame must be the single-process frame, bit for bit (sha256 of the f32 framebuffer),
 with the same ray count and the same sample chunk."""
+import hashlib
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--config", "5", "--res", "256", "--spp", "16", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+# --full: these tests compare the frames' sha256 and the un-pipelined figure, which a plain run does not compute
+COMMON = ["--config", "5", "--res", "256", "--spp", "16", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
           "--no-roofline", "--no-build"]
 
 
@@ -110,3 +113,20 @@ def test_frames_in_flight_render_the_same_frames_in_frame_order():
     assert a["config"]["frames_in_flight"] == 1 and b["config"]["frames_in_flight"] == 3
     assert a["framebuffer_sha256"] == b["framebuffer_sha256"] != one["framebuffer_sha256"]
     assert a["rays_per_step"] == b["rays_per_step"] < one["rays_per_step"]
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_frame(tmp_path):
+    """Without --full the line is the headline alone (no checksum, no roofline), --steps sets the timed frames, and
+    --dump-outputs writes the last timed frame: the frame a --full run hashes, bit for bit, and its ray count."""
+    out = tmp_path / "out"
+    plain = run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(out)]
+                + _with([a for a in COMMON if a != "--full"], steps=3))
+    full = run([sys.executable, "bench.py", "--gpus", "1"] + COMMON)
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["dtype"] == "f64"
+    assert plain["framebuffer_sha256"] is None and plain["roofline"] is None and plain["cpu_baseline"] is None
+    assert plain["rays_per_step"] == full["rays_per_step"]
+    fb = np.load(out / "framebuffer.npy")
+    assert fb.dtype == np.float32 and fb.shape == (256, 256, 3)
+    assert hashlib.sha256(fb.tobytes()).hexdigest() == full["framebuffer_sha256"]
+    rays = np.load(out / "rays.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [float(full["rays_per_step"])]
