@@ -2,8 +2,9 @@
 render a whole frame at these sizes in test time, so each full GPU frame is checked
 (1) bit for bit against the oracle on a band of image rows rendered at the full
 resolution and full spp (pixels are independent, so a band is an exact sub-problem),
-and (2) through size-independent properties: the ray count equals the oracle's on
-the band, no NaN/negative pixels, tile-sharded renders sum to the frame exactly."""
+(2) the same on the frame's first and last rows, and (3) through size-independent
+properties: the ray count equals the oracle's on the band, no NaN/negative pixels,
+tile-sharded renders sum to the frame exactly."""
 import numpy as np
 import pytest
 
@@ -36,6 +37,13 @@ def run_config(n, band_rows, tmp_path=None, r0=None):
     assert np.array_equal(band.view(np.uint64), want.view(np.uint64)), \
         f"{int((band != want).any(axis=2).sum())} band pixels differ"
     assert ost["paths"] == band_rows * W * spp
+    # the ends of the frame: its first row, and its last (in the last tile row, where the last items of the item
+    # counter, of the last round or segment end up)
+    for e0 in (0, H - 1):
+        ref, ost = osc.render(ocam, spp, mb, seed=0x5EED, sample_chunk=chunk, rows=(e0, e0 + 1), traversal=0)
+        assert np.array_equal(img[e0:e0 + 1].view(np.uint64), ref[e0:e0 + 1].view(np.uint64)), \
+            f"row {e0}: {int((img[e0] != ref[e0]).any(axis=1).sum())} pixels differ"
+        assert ost["paths"] == W * spp
     return scene, cam, img, st, (spp, mb)
 
 

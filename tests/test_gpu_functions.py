@@ -106,6 +106,23 @@ def test_rng_bit_exact():
     assert np.array_equal(out, ref)
 
 
+def test_rng_bit_exact_at_kernel_indices():
+    """Pixel indices up to 2^32 - 1, samples up to 2^30 - 1, draws up to 32002 -- what a 65535 x 65535 frame, a slot's
+    sample cursor and an 8000-bounce budget reach -- against the oracle and test_numeric.py's Python restatement."""
+    from test_numeric import draw_bits, rng_cases_at_kernel_indices
+    L = _ffi.lib()
+    pixel, sample, draw = rng_cases_at_kernel_indices(5000, np.random.default_rng(4))
+    n = len(pixel)
+    for seed in (0x5EED, (1 << 64) - 1):
+        out = np.zeros(n, dtype=np.uint64)
+        _ffi.check(L.rayrs_test_rng(0, seed, pixel.ctypes.data, sample.ctypes.data, draw.ctypes.data, n,
+                                    out.ctypes.data), "rayrs_test_rng")
+        ref = [_oracle.rng_bits(seed, int(p), int(s), int(d)) for p, s, d in zip(pixel, sample, draw)]
+        py = [draw_bits(seed, int(p), int(s), int(d)) for p, s, d in zip(pixel, sample, draw)]
+        assert np.array_equal(out, np.array(ref, dtype=np.uint64))
+        assert np.array_equal(out, np.array(py, dtype=np.uint64))
+
+
 def _rays(n, seed, spread=6.0):
     r = np.random.default_rng(seed)
     o = r.uniform(-spread, spread, (n, 3))

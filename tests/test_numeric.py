@@ -40,6 +40,28 @@ def test_rng_matches_independent_restatement():
         assert _oracle.rng_bits(seed, pixel, sample, draw) == draw_bits(seed, pixel, sample, draw)
 
 
+def rng_cases_at_kernel_indices(n, rng):
+    """(pixel, sample, draw) over the whole ranges the kernels pass: pixel = row * W + col < 2^32 (65535 x 65535 images),
+    sample < 2^30 (a slot's sample cursor), draw <= 2 + 4 x 8000 = 32002 (the bounce budget's limit), boundaries first."""
+    edges = [(0, 0, 0), ((1 << 16) - 1, 0, 0), (1 << 16, 1, 1), ((1 << 16) + 1, 2, 2), ((1 << 31) - 1, 3, 32002),
+             (1 << 31, (1 << 30) - 1, 32002), ((1 << 31) + 1, (1 << 30) - 1, 32001), ((1 << 32) - 1, (1 << 30) - 1, 32002),
+             ((1 << 32) - 1, 0, 0), (0, (1 << 30) - 1, 32002)]
+    pixel = rng.integers(0, 1 << 32, n - len(edges), dtype=np.uint64)
+    sample = rng.integers(0, 1 << 30, n - len(edges), dtype=np.uint64)
+    draw = rng.integers(0, 32003, n - len(edges), dtype=np.uint64)
+    e = np.array(edges, dtype=np.uint64)
+    return (np.concatenate([e[:, 0], pixel]), np.concatenate([e[:, 1], sample]),
+            np.concatenate([e[:, 2], draw]).astype(np.uint32))
+
+
+def test_rng_matches_independent_restatement_at_kernel_indices():
+    rng = np.random.default_rng(1)
+    pixel, sample, draw = rng_cases_at_kernel_indices(3000, rng)
+    for seed in (0x5EED, (1 << 64) - 1):
+        for p, s, d in zip(pixel, sample, draw):
+            assert _oracle.rng_bits(seed, int(p), int(s), int(d)) == draw_bits(seed, int(p), int(s), int(d))
+
+
 def test_rng_known_answers():
     """Committed integers (tests/golden/rng_known_answers.txt): the hash must never change."""
     import os
