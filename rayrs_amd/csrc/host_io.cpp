@@ -458,6 +458,11 @@ static int rayrs_hdr_load_impl(const char* path, float** rgb_out, uint32_t* w_ou
 }
 
 // HDREncoder::encode (main.rs:113-121): flat (non-RLE) RGBE scanlines.
+// Rust's `as u8` on a float: towards zero, saturating at 0 and 255, NaN (of either sign) -> 0.
+static uint8_t f32_as_u8(float v) {
+    return v != v ? 0 : (v >= 255.f ? 255 : (v <= 0.f ? 0 : (uint8_t)v));
+}
+
 static int rayrs_hdr_save_impl(const char* path, const float* rgb, uint32_t w, uint32_t h) {
     if (!path || !rgb || !w || !h) return RAYRS_INVALID_ARG;
     FILE* f = std::fopen(path, "wb");
@@ -472,11 +477,15 @@ static int rayrs_hdr_save_impl(const char* path, const float* rgb, uint32_t w, u
             if (!(m > 1e-32f)) {
                 o[0] = o[1] = o[2] = o[3] = 0;
             } else {
-                int e;
-                const float s = std::frexp(m, &e) * 256.0f / m;
-                o[0] = (uint8_t)(p[0] > 0 ? p[0] * s : 0);
-                o[1] = (uint8_t)(p[1] > 0 ? p[1] * s : 0);
-                o[2] = (uint8_t)(p[2] > 0 ? p[2] * s : 0);
+                // m = mantissa * 2^e; an infinite m, or one of 2^127 and above, takes the largest exponent
+                // byte (255) and its components saturate
+                int e = 128;
+                if (std::isfinite(m)) std::frexp(m, &e);
+                if (e > 127) e = 127;
+                const float s = std::ldexp(1.0f, 8 - e);  // = frexp(m) * 256 / m, exactly
+                o[0] = f32_as_u8(p[0] * s);
+                o[1] = f32_as_u8(p[1] * s);
+                o[2] = f32_as_u8(p[2] * s);
                 o[3] = (uint8_t)(e + 128);
             }
         }

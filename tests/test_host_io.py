@@ -77,6 +77,48 @@ def test_hdr_round_trip_within_rgbe_precision(tmp_path):
     assert np.all(back[0, 0] == 0.0)
 
 
+def _rgbe_restated(px):
+    """The writer's RGBE word of one f32 pixel, written out plainly: m = the largest component that is not NaN;
+    m <= 1e-32 or all NaN -> 0 0 0 0; otherwise e = frexp(m)'s exponent (128 for an infinite m) capped at 127, byte
+    e + 128, and each component * 2^(8 - e) converted by Rust's `as u8` (NaN -> 0, saturating)."""
+    vals = [float(c) for c in px]
+    finite_or_inf = [v for v in vals if v == v]
+    m = max(finite_or_inf) if finite_or_inf else float("nan")
+    if not (m > float(np.float32(1e-32))):
+        return [0, 0, 0, 0]
+    e = 128 if np.isinf(m) else np.frexp(np.float32(m))[1]
+    e = min(int(e), 127)
+
+    def as_u8(x):
+        return 0 if x != x else (255 if x >= 255 else (0 if x <= 0 else int(x)))
+    return [as_u8(np.float32(v) * np.float32(2.0 ** (8 - e))) for v in vals] + [e + 128]
+
+
+def test_hdr_writer_is_defined_on_inf_nan_and_huge_pixels(tmp_path):
+    """An infinite component used to make the scale NaN (frexp(inf)) and a component of 2^127 or more an exponent
+    byte of 256: both undefined conversions to u8.  Every word is now the restatement above, whatever the NaN's sign,
+    and the same twice over."""
+    inf, nan, fmax = np.float32(np.inf), np.float32(np.nan), np.finfo(np.float32).max
+    px = [(inf, 1.0, 0.5), (inf, nan, -inf), (nan, nan, nan), (-nan, 2.0, nan), (nan, -nan, 0.25), (fmax, 1.0, 0.0),
+          (2.0 ** 127, 2.0 ** 126, 3.0), (1.9e38, inf, fmax), (-inf, -1.0, 0.0), (1e-32, 0.0, 0.0), (2e-32, 1e-33, 0.0),
+          (1.0, 0.5, 0.25), (0.999, 255.0, 3.0), (1e-40, 0.0, 0.0), (0.0, -0.0, 0.0), (6.5e4, 1.0, 1e-10)]
+    img = np.array(px, dtype=np.float32).reshape(1, len(px), 3)
+    words = []
+    for k, im in enumerate((img, img, np.where(np.isnan(img), -np.abs(img), img))):  # the last: every NaN negative
+        p = tmp_path / f"nf{k}.hdr"
+        io.save_hdr(p, im)
+        data = p.read_bytes()
+        head = b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y 1 +X %d\n" % len(px)
+        assert data.startswith(head) and len(data) == len(head) + 4 * len(px)
+        words.append(np.frombuffer(data[len(head):], dtype=np.uint8).reshape(len(px), 4))
+    assert np.array_equal(words[0], words[1]) and np.array_equal(words[0], words[2])
+    for i, q in enumerate(px):
+        assert words[0][i].tolist() == _rgbe_restated(np.array(q, dtype=np.float32)), (i, q)
+    assert words[0][0].tolist() == [255, 0, 0, 255] and words[0][2].tolist() == [0, 0, 0, 0]
+    back = io.load_hdr(tmp_path / "nf0.hdr")
+    assert np.isfinite(back).all() and back[0, 0, 0] == 255.0 * 2.0 ** 119
+
+
 def test_hdr_reads_new_style_rle(tmp_path):
     w, h = 16, 2
     body = b""
