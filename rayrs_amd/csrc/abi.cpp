@@ -689,6 +689,37 @@ static CameraDev make_camera_dev(const rayrs_camera* c) {
     return cam;
 }
 
+// The traversal kernel's launch settings, for a render and for rayrs_test_trace alike: its scheduling thresholds (rayrs_lab.h),
+// its grid, and the windows of a pool of n_windows dealt round robin.
+static void trav_thresholds(const rayrs_scene* s, bool exact, RenderDev& rp) {
+    const rayrs_lab_tuning& lab = s->lab;
+    rp.refill_min = lab.refill_min ? lab.refill_min : 52u;
+    // (a leaf phase once this many lanes stand on a leaf: 24 where a leaf is one primitive -- the fast walk's tree: 612 -> 604 ms
+    // of traversal on the headline frame against 32 --, 32 where it is a group of up to four -- the default walk: 988 -> 962 ms
+    // against 24)
+    rp.leaf_min = lab.leaf_min ? lab.leaf_min : (exact ? 48u : lab.gate_tree ? 32u : 24u);
+    // (the default walk: its lanes walk on while their leaf groups wait, so a leaf phase may wait for more of them -- or for
+    // leaf_wait lanes that can do nothing else; scripts/sim/walk_sched_sim.py, swept on the GPU: profiles/r06_leaf_queue.txt)
+    rp.leaf_wait = lab.leaf_wait ? lab.leaf_wait : 16u;
+    // (pre-tested rays -- a scene with a hot group, wavefront.hip finish_rays -- wanted a refill_min of 56 while a lane stood idle
+    // on its leaf: 664 -> 659 ms of traversal, profiles/r06_tuning_sweep.txt; with the leaf groups set aside 52 is best again:
+    // 626 -> 619 ms, profiles/r06_leaf_queue.txt)
+}
+
+static uint32_t trav_grid_blocks(const rayrs_scene* s, bool exact) {
+    uint32_t trav_bpc = (uint32_t)s->trav[s->walk_index(exact)].blocks_per_cu;
+    if (s->lab.trav_blocks_per_cu && s->lab.trav_blocks_per_cu < trav_bpc) trav_bpc = s->lab.trav_blocks_per_cu;
+    return (uint32_t)s->cu_count * trav_bpc;
+}
+
+static uint32_t trav_static_windows(const rayrs_scene* s, uint32_t n_windows, uint32_t trav_blocks) {
+    uint32_t static_pct = s->lab.static_pct ? s->lab.static_pct : 50u;
+    if (static_pct > 100) static_pct = 100;
+    // whole round-robin rounds covering about static_pct % of the pool's windows
+    const uint64_t n_waves = (uint64_t)trav_blocks * 4u;
+    return (uint32_t)((uint64_t)n_windows * static_pct / 100u / n_waves * n_waves);
+}
+
 int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params,
                         void* out_device, void* hip_stream) {
     RAYRS_GUARDED({
@@ -729,10 +760,6 @@ int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const ra
     rp.inv_nchunks = 1.0 / (double)rp.nchunks;
     rp.inv_tiles_x = 1.0 / (double)rp.tiles_x;
     if (rp.total_items >= (1ull << 32)) return RAYRS_UNSUPPORTED;
-    rp.refill_min = lab.refill_min ? lab.refill_min : 52u;
-    // (a leaf phase once this many lanes stand on a leaf: 24 where a leaf is one primitive -- the fast walk's tree: 612 -> 604 ms
-    // of traversal on the headline frame against 32 --, 32 where it is a group of up to four -- the default walk: 988 -> 962 ms
-    // against 24; it is set below, once the walk is known)
     rp.count_work = params->count_work ? 1u : 0u;
     rp.out_format = params->out_format;
     rp.out = out_device;
@@ -763,14 +790,8 @@ int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const ra
 
     const bool exact = params->fast_traversal == 0u || camera_is_far(scene, camera);
     scene->last_exact = exact;
-    rp.leaf_min = lab.leaf_min ? lab.leaf_min : (exact ? 48u : lab.gate_tree ? 32u : 24u);
-    // (the default walk: its lanes walk on while their leaf groups wait, so a leaf phase may wait for more of them -- or for
-    // leaf_wait lanes that can do nothing else; scripts/sim/walk_sched_sim.py, swept on the GPU: profiles/r06_leaf_queue.txt)
-    rp.leaf_wait = lab.leaf_wait ? lab.leaf_wait : 16u;
+    trav_thresholds(scene, exact, rp);
     const SceneDev sc = make_scene_dev(scene, exact);
-    // (pre-tested rays -- a scene with a hot group, wavefront.hip finish_rays -- wanted 56 while a lane stood idle on its
-    // leaf: 664 -> 659 ms of traversal, profiles/r06_tuning_sweep.txt; with the leaf groups set aside 52 is best again:
-    // 626 -> 619 ms, profiles/r06_leaf_queue.txt)
     const CameraDev cam = make_camera_dev(camera);
 
     // ---- path pool.  A traversal launch works through the whole pool, and its ramp-up
@@ -800,11 +821,7 @@ int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const ra
 
     const bool compact = scene->flat.compact;
     const bool count = params->count_work != 0;
-    uint32_t trav_bpc = (uint32_t)scene->trav[scene->walk_index(exact)].blocks_per_cu;
-    if (lab.trav_blocks_per_cu && lab.trav_blocks_per_cu < trav_bpc) trav_bpc = lab.trav_blocks_per_cu;
-    const uint32_t trav_blocks = (uint32_t)scene->cu_count * trav_bpc;
-    uint32_t static_pct = lab.static_pct ? lab.static_pct : 50u;
-    if (static_pct > 100) static_pct = 100;
+    const uint32_t trav_blocks = trav_grid_blocks(scene, exact);
 
     // A path's light lives in a side array and only while it is not +0 (wavefront.h PathSlot).  Where a surface
     // emits, paths do get light, and the hit and miss kernels request the side array's entry together with the
@@ -832,11 +849,7 @@ int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const ra
         wf = pl.wf;
         wf.np = np;
         const uint32_t n_windows = np / wf_window_slots();
-        {
-            // whole round-robin rounds covering about static_pct % of the pool's windows
-            const uint64_t n_waves = (uint64_t)trav_blocks * 4u;
-            rp.static_windows = (uint32_t)((uint64_t)n_windows * static_pct / 100u / n_waves * n_waves);
-        }
+        rp.static_windows = trav_static_windows(scene, n_windows, trav_blocks);
 
         // the gen, hit and miss kernels run with this one grid, so wave w means the same windows in all three: one
         // wave per window, at most 8 ... 24 workgroups per CU (below)
@@ -1153,6 +1166,92 @@ int rayrs_test_intersect(rayrs_scene* scene, const double* o, const double* d, u
     ST_TRY(dprim.download(object, n * 8));
     for (uint64_t i = 0; i < n; i++)  // DFS slot -> object index in insertion order
         if (object[i] >= 0) object[i] = (int64_t)scene->flat.prim_object[(size_t)object[i]];
+    return RAYRS_OK;
+}
+
+int rayrs_test_trace(rayrs_scene* scene, const double* o, const double* d, uint64_t n, int exact, double* t, int64_t* object,
+                     uint64_t* pre_answered) {
+    if (!scene || !o || !d || !t || !object) return RAYRS_INVALID_ARG;
+    if (scene->device < 0) return RAYRS_NO_DEVICE;
+    HIP_TRY(hipSetDevice(scene->device));
+    const bool ex = exact != 0;
+    const SceneDev sc = make_scene_dev(scene, ex);
+    RenderDev rp;
+    std::memset(&rp, 0, sizeof(rp));
+    trav_thresholds(scene, ex, rp);
+    const uint32_t trav_blocks = trav_grid_blocks(scene, ex);
+    // the pool: rayrs_tuning.pool_slots slots if set (the rays then go through it in chunks of that many), whole windows
+    uint64_t np64 = scene->tuning.pool_slots ? scene->tuning.pool_slots : (n < (1u << 20) ? n : (1u << 20));
+    np64 = np64 < 1024u ? 1024u : (np64 + 1023u) & ~1023ull;
+    const uint32_t np = (uint32_t)np64;
+    WfDev wf;
+    std::memset(&wf, 0, sizeof(wf));
+    wf.np = np;
+    wf.trav_threads = trav_blocks * 256u;
+    rp.static_windows = trav_static_windows(scene, np / wf_window_slots(), trav_blocks);
+    DevBuf dslots, dstate, dctl, dspill, dcount, dans, dorg, ddir;
+    ST_TRY(dslots.alloc((size_t)np * sizeof(PathSlot)));
+    ST_TRY(dstate.alloc(np));
+    ST_TRY(dctl.alloc(sizeof(WfCtl)));
+    ST_TRY(dspill.alloc((size_t)(sc.stack_depth - sc.stack_lds) * wf.trav_threads * 4u));
+    ST_TRY(dcount.alloc(sizeof(Counters)));
+    ST_TRY(dans.alloc(sizeof(unsigned long long)));
+    ST_TRY(dorg.alloc((size_t)np * 24));
+    ST_TRY(ddir.alloc((size_t)np * 24));
+    HIP_TRY(hipMemset(dcount.p, 0, sizeof(Counters)));
+    HIP_TRY(hipMemset(dans.p, 0, sizeof(unsigned long long)));
+    wf.slots = (PathSlot*)dslots.p;
+    wf.state = (uint8_t*)dstate.p;
+    wf.ctl = (WfCtl*)dctl.p;
+    wf.stack_spill = (uint32_t*)dspill.p;
+    rp.counters = (Counters*)dcount.p;
+    std::vector<uint8_t> state(np);
+    std::vector<PathSlot> slots(np);
+    constexpr uint32_t MAX_ROUNDS = 64;
+    for (uint64_t base = 0; base < n; base += np) {
+        const uint32_t m = (uint32_t)(n - base < np ? n - base : np);
+        HIP_TRY(hipMemcpy(dorg.p, o + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ddir.p, d + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice));
+        HIP_TRY(wf_launch_intake(sc, wf, (const double*)dorg.p, (const double*)ddir.p, m, (unsigned long long*)dans.p, nullptr));
+        // the traversal rounds of a render (abi.cpp rayrs_render_launch): there the hit kernel resets the window cursor
+        uint32_t round = 0;
+        for (;; round++) {
+            WfCtl ctl;
+            std::memset(&ctl, 0, sizeof(ctl));
+            ctl.live_slots = m;
+            HIP_TRY(hipMemcpy(dctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
+            HIP_TRY(wf_launch_trav(scene->flat.compact, false, sc, rp, wf, trav_blocks, nullptr));
+            HIP_TRY(hipDeviceSynchronize());
+            ST_TRY(dstate.download(state.data(), np));
+            bool ready = false;
+            for (uint32_t i = 0; i < m; i++) ready |= (state[i] & 7u) == WF_READY;
+            if (!ready) break;
+            if (round + 1 >= MAX_ROUNDS) {
+                g_last_error = "rayrs_test_trace: slots still READY after the traversal rounds";
+                return RAYRS_HIP_ERROR;
+            }
+        }
+        ST_TRY(dslots.download(slots.data(), (size_t)m * sizeof(PathSlot)));
+        for (uint32_t i = 0; i < m; i++) {
+            if (state[i] == WF_HIT) {
+                if (slots[i].ray.prim >= scene->flat.prim_object.size()) {
+                    g_last_error = "rayrs_test_trace: a HIT slot names no primitive";
+                    return RAYRS_HIP_ERROR;
+                }
+                t[base + i] = slots[i].ray.t;
+                object[base + i] = (int64_t)scene->flat.prim_object[slots[i].ray.prim];  // DFS slot -> insertion order
+            } else if (state[i] == WF_MISS) {
+                t[base + i] = 0.0;
+                object[base + i] = -1;
+            } else {
+                g_last_error = "rayrs_test_trace: a slot left neither HIT nor MISS";
+                return RAYRS_HIP_ERROR;
+            }
+        }
+    }
+    unsigned long long answered = 0;
+    ST_TRY(dans.download(&answered, sizeof(answered)));
+    if (pre_answered) *pre_answered = answered;
     return RAYRS_OK;
 }
 

@@ -23,6 +23,13 @@ int rayrs_test_rng(int device, uint64_t seed, const uint64_t* pixel, const uint6
 /* Bvh::intersect for n rays (o,d = n*3): t[i] and the object index (-1 miss).  exact: 1 = the default walk, 0 = the fast one */
 int rayrs_test_intersect(rayrs_scene* scene, const double* o, const double* d, uint64_t n, int exact, double* t,
                          int64_t* object);
+/* The same queries answered by the kernels a render answers them with: the rays go into slots of a pool as the kernels that
+ * make rays leave them (on a scene with a hot group, under the default walk, with their pre-test: wavefront.hip finish_rays)
+ * and through the traversal kernel's rounds -- with the render's template arguments, grid, LDS layout, rayrs_tuning.pool_slots
+ * (the rays go through a pool of that many slots in turn) and rayrs_lab.h settings.  t, object as rayrs_test_intersect;
+ * *pre_answered (may be null): how many rays the pre-test answered outright (they entered no slot of the first record). */
+int rayrs_test_trace(rayrs_scene* scene, const double* o, const double* d, uint64_t n, int exact, double* t, int64_t* object,
+                     uint64_t* pre_answered);
 /* n samples, each exactly as a render starts and runs it -- the path key of (seed, pixel, sample), the primary ray, the
  * loop of lib.rs:521-560 -- in one lane each, with their traces: for sample i, n_queries[i] loop iterations, and for
  * the first min(n_queries[i], cap) of them object[i*cap + b] (-1: the query found nothing), t (0 then), throughput

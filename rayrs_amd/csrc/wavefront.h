@@ -96,5 +96,10 @@ hipError_t wf_launch_hit(bool compact, bool eager_light, const SceneDev& sc, con
                          uint32_t blocks, hipStream_t stream);
 hipError_t wf_launch_miss(bool compact, bool eager_light, const SceneDev& sc, const CameraDev& cam, const RenderDev& rp, const WfDev& wf,
                           uint32_t blocks, hipStream_t stream);
+// rayrs_test_trace (rayrs_selftest.h): caller rays o, d (n <= wf.np, 3 doubles each) into slots 0 .. n - 1 as the kernels that
+// make rays leave them (with finish_rays' pre-test on a scene with a hot group); the other slots DEAD.  *answered += the rays
+// the pre-test answered outright.
+hipError_t wf_launch_intake(const SceneDev& sc, const WfDev& wf, const double* o, const double* d, uint32_t n,
+                            unsigned long long* answered, hipStream_t stream);
 
 }  // namespace rayrs

@@ -1106,7 +1106,44 @@ __global__ void __launch_bounds__(256, 3) wf_miss_kernel(SceneDev sc, CameraDev 
     store_sample_count(sc, rp, wf, sn);
 }
 
+// ----------------------------------------------------------------- intake (rayrs_test_trace, rayrs_selftest.h: tests only)
+
+// Caller rays into the pool, each left in its slot as the kernels that make rays leave it: ray i of `o`, `d` in slot i, its
+// 1 / d and the root Node's box computed as next_sample / emit_rays compute them; on a scene with a hot group (the default
+// walk) the pre-test of finish_rays -- which reads the scene and the pool at the KA_* offsets, hence the leading arguments --,
+// else state READY, or MISS for a ray that misses the root box.  Slots n .. np - 1 become DEAD.  *answered += the rays the
+// pre-test answered outright (entered the root box and no slot of the first record).
+__global__ void __launch_bounds__(256) wf_intake_kernel(SceneDev sc, CameraDev cam, RenderDev rp, WfDev wf, const double* o,
+                                                        const double* d, uint32_t n, unsigned long long* answered) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;  // (the grid covers the pool: np is a multiple of 1024)
+    const bool got = slot < n;
+    const V3 ro = got ? mk(o[3 * slot], o[3 * slot + 1], o[3 * slot + 2]) : mk(0.0, 0.0, 0.0);
+    const V3 rd = got ? mk(d[3 * slot], d[3 * slot + 1], d[3 * slot + 2]) : mk(0.0, 0.0, 1.0);
+    const V3 inv = mk(1.0 / rd.x, 1.0 / rd.y, 1.0 / rd.z);
+    const bool enters = got && root_box_hit(sc, ro, inv);
+    if (sc.hot != nullptr) {  // wave-uniform: every lane takes part in finish_rays' ballots
+        SampleCount sn{0, 0, 0, 0, HotTally{0, 0, 0}, 0, 0, 0};
+        finish_rays(got, enters, false, slot, ro, rd, inv, 1u, sn);
+        if ((threadIdx.x & 63u) == 0 && sn.pre_done) atomicAdd(answered, (unsigned long long)sn.pre_done);
+    } else if (got) {
+        RaySlot* rs = ray_slot(wf, slot);
+        rs->o[0] = ro.x, rs->o[1] = ro.y, rs->o[2] = ro.z;
+        rs->d[0] = rd.x, rs->d[1] = rd.y, rs->d[2] = rd.z;
+        rs->bd = 1u;
+        wf.state[slot] = enters ? ready_state(rd) : WF_MISS;
+    }
+    if (!got && slot < wf.np) wf.state[slot] = WF_DEAD;
+}
+
 // ----------------------------------------------------------- launch glue
+
+hipError_t wf_launch_intake(const SceneDev& sc, const WfDev& wf, const double* o, const double* d, uint32_t n,
+                            unsigned long long* answered, hipStream_t stream) {
+    const CameraDev cam{};  // (not read: finish_rays reads the scene and the pool only)
+    const RenderDev rp{};
+    hipLaunchKernelGGL(wf_intake_kernel, dim3(wf.np / 256u), dim3(256), 0, stream, sc, cam, rp, wf, o, d, n, answered);
+    return hipGetLastError();
+}
 
 static inline uint32_t trav_lds_bytes(bool compact, uint32_t stack_lds, uint32_t leafq, uint32_t hot_records) {
     return 4u * 64u * (stack_lds + 1u + leafq) * 4u + 4u * WINDOW * 2u + hot_records * (compact ? 144u : 272u);

@@ -5,6 +5,7 @@ decides, since the closest hit does not depend on the topology otherwise -- is (
 primitives (equal-t ties: the first leaf wins, bvh.rs:62) and (2) which box gates which leaves (a leaf is reached iff
 the box of its parent Node is entered; a flat box never is, geometry.rs:474).  Both are compared exactly: Python's
 floats are the same IEEE doubles, list.sort is stable like slice::sort_by."""
+import bisect
 import math
 
 import numpy as np
@@ -56,16 +57,20 @@ def area(b):  # geometry.rs:640-645
     return 2.0 * x * y + 2.0 * y * z + 2.0 * x * z
 
 
-def sah(total_area, left, right):  # calculate_sah(0.3, 1., ...), bvh.rs:15-38
-    pl = area(bbox_list(left)) / total_area if left else 0.0
-    pr = area(bbox_list(right)) / total_area if right else 0.0
-    return 0.3 + 1.0 * (pl * len(left) + pr * len(right))
+class Node:  # BvhTree::Node(AxisAlignedBoundingBox, Vec<BvhTree>), bvh.rs:222
+    def __init__(self, box, children):
+        self.box, self.children = box, children
+
+
+class LeafNode:  # BvhTree::LeafNode(Object), bvh.rs:223
+    def __init__(self, obj):
+        self.object = obj
 
 
 def build(items, splits, order, groups):
     """BvhTree::build_sah (splits > 0, bvh.rs:227-317) / build_midpoint (:319-389).  items: [(object index, bbox)].
     Appends the objects to `order` depth-first and the bottom Nodes / direct leaves to `groups` as (first position
-    in the order, count, gating box)."""
+    in the order, count, gating box).  Returns the tree: Node(box, children) / LeafNode(object index)."""
     box = bbox_list(items)
     if len(items) > 4:
         x, y, z = box[1] - box[0], box[3] - box[2], box[5] - box[4]
@@ -77,24 +82,40 @@ def build(items, splits, order, groups):
             mn, ln = box[2 * ax], (x, y, z)[ax]
             dist = ln / (splits - 1)
             best, best_sah = None, math.inf
+            # the boxes of items[:k + 1] and items[k:] once, not once per split (a min / max is exact, so only the sign of a
+            # zero bound can depend on the order of the fold, and no surface area, hence no cost, depends on that sign);
+            # the centres are sorted, so split_ind is a bisection
+            pre, suf = [items[0][1]], [items[-1][1]]
+            for it in items[1:]:
+                pre.append(expand(pre[-1], it[1]))
+            for it in items[-2::-1]:
+                suf.append(expand(it[1], suf[-1]))
+            suf.reverse()
+            sorted_ok = not any(c != c for c in cs)
             for i in range(1, splits + 1):
-                ind = first_above(mn + i * dist)
-                if ind is not None:
-                    s = sah(area(box), items[:ind], items[ind:])
+                v = mn + i * dist
+                ind = bisect.bisect_right(cs, v) if sorted_ok else first_above(v)
+                if ind is not None and ind < len(cs):
+                    pl = area(pre[ind - 1]) / area(box) if ind else 0.0  # calculate_sah(0.3, 1., ...), bvh.rs:15-38
+                    pr = area(suf[ind]) / area(box)
+                    s = 0.3 + 1.0 * (pl * ind + pr * (len(items) - ind))
                     if s < best_sah:
                         best_sah, best = s, ind
         else:
             best = first_above(center(box)[ax])
         ind = len(items) // 2 if (best is None or best == 0 or best == len(items) - 1) else best
+        children = []
         for side in (items[:ind], items[ind:]):
             if len(side) > 1:
-                build(side, splits, order, groups)
+                children.append(build(side, splits, order, groups))
             else:  # LeafNode directly under this Node: no box of its own (bvh.rs:297, :302) -- this Node's gates it
                 groups.append((len(order), 1, box))
                 order.append(side[0][0])
-    else:
-        groups.append((len(order), len(items), box))
-        order.extend(i for i, _ in items)
+                children.append(LeafNode(side[0][0]))
+        return Node(box, children)
+    groups.append((len(order), len(items), box))
+    order.extend(i for i, _ in items)
+    return Node(box, [LeafNode(i) for i, _ in items])
 
 
 def singles(objs):
