@@ -1,4 +1,5 @@
-// abi.cpp -- the extern "C" boundary declared in include/rayrs_hip.h.
+// abi.cpp -- the extern "C" boundary declared in include/rayrs_hip.h: the entry points, a scene's lifetime, and a render as
+// plan_frame (arithmetic only), reserve, enqueue.  The device self tests of rayrs_selftest.h are in selftest.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,7 +16,6 @@
 #include "kernels.h"
 #include "local_pool.h"
 #include "rayrs_lab.h"
-#include "rayrs_selftest.h"
 #include "scene_host.hpp"
 #include "scene_internal.hpp"
 #include "wavefront.h"
@@ -168,10 +168,7 @@ int rayrs_object_from_triangles_f64(rayrs_objects* objs, const double* verts, ui
 int rayrs_object_from_spheres(rayrs_objects* objs, double radius, const double* centers, uint32_t n,
                               const rayrs_material* mat, const rayrs_emission* emission) {
     if (!objs || (!centers && n)) return RAYRS_INVALID_ARG;
-    for (uint32_t i = 0; i < n; i++) {
-        const int st = rayrs_object_sphere(objs, radius, centers + 3 * (size_t)i, mat, emission);
-        if (st != RAYRS_OK) return st;
-    }
+    for (uint32_t i = 0; i < n; i++) RAYRS_TRY(rayrs_object_sphere(objs, radius, centers + 3 * (size_t)i, mat, emission));
     return RAYRS_OK;
 }
 
@@ -187,62 +184,25 @@ int rayrs_object_box_geom(rayrs_objects* objs, const double ll[3], const double 
         {RAYRS_AXIS_ZREV, ll[0], ur[0], ll[1], ur[1], ll[2]}, {RAYRS_AXIS_Z, ll[0], ur[0], ll[1], ur[1], ur[2]},
         {RAYRS_AXIS_YREV, ll[0], ur[0], ll[2], ur[2], ll[1]}, {RAYRS_AXIS_Y, ll[0], ur[0], ll[2], ur[2], ll[1]},
     };
-    for (const auto& f : faces) {
-        const int st = rayrs_object_plane(objs, f.axis, f.u0, f.u1, f.v0, f.v1, f.pos, mat, emission);
-        if (st != RAYRS_OK) return st;
-    }
+    for (const auto& f : faces) RAYRS_TRY(rayrs_object_plane(objs, f.axis, f.u0, f.u1, f.v0, f.v1, f.pos, mat, emission));
     return RAYRS_OK;
 }
 
 // ------------------------------------------------------------------- Scene
 
-extern "C++" void rayrs::scene_free_device(rayrs_scene* s) {
-    if (s->device < 0) return;
-    (void)hipSetDevice(s->device);
-    if (s->pending && s->last_stream) (void)hipStreamSynchronize(s->last_stream);
-    for (auto& w : s->trav)
-        if (w.d_nodes) (void)hipFree(w.d_nodes);
-    if (s->d_prims) (void)hipFree(s->d_prims);
-    if (s->d_hot) (void)hipFree(s->d_hot);
-    if (s->d_surfaces) (void)hipFree(s->d_surfaces);
-    if (s->d_hdri) (void)hipFree(s->d_hdri);
-    if (s->d_counters) (void)hipFree(s->d_counters);
-    if (s->d_partial) (void)hipFree(s->d_partial);
-    {
-        rayrs_scene::Pool& pl = s->pool;
-        if (pl.block) (void)hipFree(pl.block);
-        if (pl.d_wave_items) (void)hipFree(pl.d_wave_items);
-        if (pl.d_stack_spill) (void)hipFree(pl.d_stack_spill);
-        if (pl.wf.ctl) (void)hipFree(pl.wf.ctl);
-        if (pl.h_live) (void)hipHostFree(pl.h_live);
-        for (auto& e : pl.ev_batch)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : pl.ev_round)
-            if (e) (void)hipEventDestroy(e);
-    }
-    if (s->d_next_item) (void)hipFree(s->d_next_item);
-    if (s->multi_out) (void)hipFree(s->multi_out);
-    if (s->multi_stream) (void)hipStreamDestroy(s->multi_stream);
-    if (s->d_local_light) (void)hipFree(s->d_local_light);
-    if (s->d_local_items) (void)hipFree(s->d_local_items);
-    for (auto& e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-}
-
-void rayrs_scene_destroy(rayrs_scene* scene) {
-    if (!scene) return;
-    scene_free_device(scene);
-    delete scene;
-}
+void rayrs_scene_destroy(rayrs_scene* scene) { delete scene; }
 
 // Sizes the traversal workgroup's LDS from the tree and the scene's tuning, and asks the runtime how
 // many such workgroups fit a CU.  A workgroup's LDS: the first stack_lds entries of each lane's stack
 // (deeper entries overflow to HBM; on the 1M-triangle scene 99.4 % of visits happen with at most 7
 // pending), 4 KiB of window lists, and the hot_records largest wide records.  13 + 4 + 14 KiB (the default walk's trees: 17 KiB with the lanes' leaf queues + 4 + 10) lets
 // five workgroups (the kernel's launch bound) share a CU's 160 KiB.
+// The kernel's dynamic-LDS limit belongs to the kernel on a device, not to a scene, and the scenes of a process share
+// it: it is only ever raised (wf_trav_raise_lds), so it ends at no less than the largest size among the trees this scene has.
 static int scene_configure_traversal(rayrs_scene* s) {
     const FlatScene& f = s->flat;
     for (int x = 0; x < 3; x++) {
+        if (x == 2 && !f.has_hot) continue;
         const WalkTree& t = s->tree(x);
         rayrs_scene::Walk& w = s->trav[x];
         const uint32_t depth = t.depth ? t.depth : 1;
@@ -254,7 +214,9 @@ static int scene_configure_traversal(rayrs_scene* s) {
         if (s->lab.hot_records == 0xffffffffu) hot = 0;
         else if (s->lab.hot_records) hot = s->lab.hot_records < WIDE_FRONT ? s->lab.hot_records : WIDE_FRONT;
         w.hot_records = hot < t.n() ? hot : t.n();
-        HIP_TRY(wf_trav_occupancy(f.compact, w.stack_lds, w.leafq, w.hot_records, &w.blocks_per_cu));
+        const uint32_t lds = wf_trav_lds_bytes(f.compact, w.stack_lds, w.leafq, w.hot_records);
+        HIP_TRY(wf_trav_raise_lds(f.compact, lds));  // (before the query, which is about a launch with this much)
+        HIP_TRY(wf_trav_occupancy(f.compact, lds, &w.blocks_per_cu));
         if (w.blocks_per_cu < 1) w.blocks_per_cu = 1;
     }
     return RAYRS_OK;
@@ -306,42 +268,28 @@ extern "C++" int rayrs::scene_upload(rayrs_scene* s) {
     for (int x = 0; x < 3; x++) {
         const WalkTree& t = s->tree(x);
         if (x == 2 && !f.has_hot) continue;
-        HIP_TRY(hipMalloc(&s->trav[x].d_nodes, t.node_bytes.size()));
-        HIP_TRY(hipMemcpy(s->trav[x].d_nodes, t.node_bytes.data(), t.node_bytes.size(), hipMemcpyHostToDevice));
+        HIP_TRY(s->trav[x].d_nodes.upload(t.node_bytes.data(), t.node_bytes.size()));
     }
-    if (f.has_hot) {
-        HIP_TRY(hipMalloc((void**)&s->d_hot, sizeof(HotGroupDev)));
-        HIP_TRY(hipMemcpy(s->d_hot, &f.hot, sizeof(HotGroupDev), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&s->d_prims, f.prim_bytes.size()));
-    HIP_TRY(hipMemcpy(s->d_prims, f.prim_bytes.data(), f.prim_bytes.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&s->d_surfaces, s->surfaces.size() * sizeof(SurfaceDev)));
-    HIP_TRY(hipMemcpy(s->d_surfaces, s->surfaces.data(), s->surfaces.size() * sizeof(SurfaceDev),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&s->d_hdri, f.hdri_quads.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(s->d_hdri, f.hdri_quads.data(), f.hdri_quads.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&s->d_counters, sizeof(Counters)));
-    for (auto& e : s->ev) HIP_TRY(hipEventCreate(&e));
+    if (f.has_hot) HIP_TRY(s->d_hot.upload(&f.hot, sizeof(HotGroupDev)));
+    HIP_TRY(s->d_prims.upload(f.prim_bytes.data(), f.prim_bytes.size()));
+    HIP_TRY(s->d_surfaces.upload(s->surfaces.data(), s->surfaces.size() * sizeof(SurfaceDev)));
+    HIP_TRY(s->d_hdri.upload(f.hdri_quads.data(), f.hdri_quads.size() * sizeof(float)));
+    HIP_TRY(s->d_counters.reserve(sizeof(Counters)));
+    for (auto& e : s->ev) HIP_TRY(e.create());
     s->device_bytes = f.walk.node_bytes.size() + f.gate.node_bytes.size() + (f.has_hot ? f.gate_hot.node_bytes.size() : 0) + f.prim_bytes.size() + s->surfaces.size() * sizeof(SurfaceDev) +
                       f.hdri_quads.size() * sizeof(float);
-    {
-        const int st = scene_configure_traversal(s);
-        if (st != RAYRS_OK) return st;
-    }
-    {
-        rayrs_scene::Pool& pl = s->pool;
-        HIP_TRY(hipMalloc((void**)&pl.wf.ctl, sizeof(WfCtl)));
-        HIP_TRY(hipHostMalloc((void**)&pl.h_live, 2 * sizeof(uint32_t), hipHostMallocDefault));
-        for (auto& e : pl.ev_batch) HIP_TRY(hipEventCreate(&e));
-    }
-    HIP_TRY(hipMalloc((void**)&s->d_next_item, sizeof(unsigned long long)));
+    RAYRS_TRY(scene_configure_traversal(s));
+    HIP_TRY(s->pool.d_ctl.reserve(sizeof(WfCtl)));
+    HIP_TRY(s->pool.h_live.alloc(2 * sizeof(uint32_t)));
+    for (auto& e : s->pool.ev_batch) HIP_TRY(e.create());
+    HIP_TRY(s->d_next_item.reserve(sizeof(unsigned long long)));
     if (s->local_ok) {
         HIP_TRY(lp_configure());
         // (from about 13 primitives and surface rows up three workgroups' LDS no longer fit a CU: ask, do not assume)
         HIP_TRY(lp_occupancy(s->flat.compact, s->local.n_prims, (uint32_t)s->surfaces.size(), &s->local_blocks_per_cu));
         if (s->local_blocks_per_cu < 1) s->local_blocks_per_cu = 1;
         if (s->local_blocks_per_cu > (int)LP_WPS) s->local_blocks_per_cu = (int)LP_WPS;
-        HIP_TRY(hipMalloc((void**)&s->d_local_items, LOCAL_MAX_SEGMENTS * sizeof(unsigned long long)));
+        HIP_TRY(s->d_local_items.reserve(LOCAL_MAX_SEGMENTS * sizeof(unsigned long long)));
     }
     return RAYRS_OK;
 }
@@ -352,8 +300,7 @@ int rayrs_scene_new(const rayrs_objects* objs, double z_near, double z_far, int 
     if (!objs || !out) return RAYRS_INVALID_ARG;
     *out = nullptr;
     std::unique_ptr<rayrs_scene> s(new rayrs_scene());
-    int st = build_flat_scene(objs->list, z_near, z_far, heuristic, splits, hdri_w, hdri_h, hdri_rgb, &s->flat);
-    if (st != RAYRS_OK) return st;
+    RAYRS_TRY(build_flat_scene(objs->list, z_near, z_far, heuristic, splits, hdri_w, hdri_h, hdri_rgb, &s->flat));
     // Every traversal lane gets a stack of WalkTree::depth entries (12 in LDS, the rest in HBM: 1.3 MB per entry on a
     // 256-CU device).  The reference recurses as deep as its tree; a tree that needs more than 4096 pending
     // entries (a chain of thousands of nested objects) is refused instead of allocating gigabytes for it.
@@ -365,13 +312,7 @@ int rayrs_scene_new(const rayrs_objects* objs, double z_near, double z_far, int 
     s->n_objects = objs->list.objs.size();
     s->device = device;
     scene_configure_local(s.get());
-    if (device >= 0) {
-        st = scene_upload(s.get());
-        if (st != RAYRS_OK) {
-            scene_free_device(s.get());
-            return st;
-        }
-    }
+    if (device >= 0) RAYRS_TRY(scene_upload(s.get()));
     *out = s.release();
     return RAYRS_OK;
     })
@@ -421,28 +362,22 @@ int rayrs_scene_export_bvh(const rayrs_scene* scene, double* child_box, uint32_t
     return RAYRS_OK;
 }
 
-int rayrs_scene_export_wide(const rayrs_scene* scene, double* wide_box, uint32_t* wide_ref) {
-    if (!scene) return RAYRS_INVALID_ARG;
-    const WalkTree& t = scene->flat.walk;
+static int export_tree(const WalkTree& t, double* wide_box, uint32_t* wide_ref) {
     if (wide_box && !t.box.empty()) std::memcpy(wide_box, t.box.data(), t.box.size() * 8);
     if (wide_ref && !t.ref.empty()) std::memcpy(wide_ref, t.ref.data(), t.ref.size() * 4);
     return RAYRS_OK;
+}
+
+int rayrs_scene_export_wide(const rayrs_scene* scene, double* wide_box, uint32_t* wide_ref) {
+    return scene ? export_tree(scene->flat.walk, wide_box, wide_ref) : RAYRS_INVALID_ARG;
 }
 
 int rayrs_scene_export_gate_tree(const rayrs_scene* scene, double* wide_box, uint32_t* wide_ref) {
-    if (!scene) return RAYRS_INVALID_ARG;
-    const WalkTree& t = scene->flat.gate;
-    if (wide_box && !t.box.empty()) std::memcpy(wide_box, t.box.data(), t.box.size() * 8);
-    if (wide_ref && !t.ref.empty()) std::memcpy(wide_ref, t.ref.data(), t.ref.size() * 4);
-    return RAYRS_OK;
+    return scene ? export_tree(scene->flat.gate, wide_box, wide_ref) : RAYRS_INVALID_ARG;
 }
 
 int rayrs_scene_export_hot_tree(const rayrs_scene* scene, double* wide_box, uint32_t* wide_ref) {
-    if (!scene || !scene->flat.has_hot) return RAYRS_INVALID_ARG;
-    const WalkTree& t = scene->flat.gate_hot;
-    if (wide_box && !t.box.empty()) std::memcpy(wide_box, t.box.data(), t.box.size() * 8);
-    if (wide_ref && !t.ref.empty()) std::memcpy(wide_ref, t.ref.data(), t.ref.size() * 4);
-    return RAYRS_OK;
+    return scene && scene->flat.has_hot ? export_tree(scene->flat.gate_hot, wide_box, wide_ref) : RAYRS_INVALID_ARG;
 }
 
 int rayrs_scene_clone_to_device(const rayrs_scene* scene, int device, rayrs_scene** out) {
@@ -457,11 +392,7 @@ int rayrs_scene_clone_to_device(const rayrs_scene* scene, int device, rayrs_scen
         s->lab = scene->lab;
         s->device = device;
         scene_configure_local(s.get());
-        const int st = scene_upload(s.get());
-        if (st != RAYRS_OK) {
-            scene_free_device(s.get());
-            return st;
-        }
+        RAYRS_TRY(scene_upload(s.get()));
         *out = s.release();
         return RAYRS_OK;
     })
@@ -480,11 +411,17 @@ static int scene_quiesce(rayrs_scene* scene) {  // settings change between rende
     return RAYRS_OK;
 }
 
+// A render in flight ends before any member releases what it uses (nothing here touches rayrs_last_error).
+rayrs_scene::~rayrs_scene() {
+    if (device < 0) return;
+    (void)hipSetDevice(device);
+    if (pending && last_stream) (void)hipStreamSynchronize(last_stream);
+}
+
 int rayrs_scene_set_tuning(rayrs_scene* scene, const rayrs_tuning* tuning) {
     if (!scene || !tuning) return RAYRS_INVALID_ARG;
     if (tuning->local_pool > 1u) return RAYRS_INVALID_ARG;
-    const int st = scene_quiesce(scene);
-    if (st != RAYRS_OK) return st;
+    RAYRS_TRY(scene_quiesce(scene));
     scene->tuning = *tuning;
     return RAYRS_OK;
 }
@@ -495,29 +432,42 @@ extern "C" int rayrs_lab_ticks(rayrs_scene* scene, uint64_t out[16]) {
     if (!scene || !out || scene->device < 0) return RAYRS_INVALID_ARG;
     HIP_TRY(hipSetDevice(scene->device));
     Counters c;
-    HIP_TRY(hipMemcpy(&c, scene->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(scene->d_counters.download(&c, sizeof(c)));
     for (int i = 0; i < 16; i++) out[i] = c.lab_ticks[i];
     return RAYRS_OK;
 }
 #endif
+
+// A timed round r owns four events, pool.ev_round[4 r + k]: k = 0 before its traversal kernel, 1 behind it, 2 behind the hit
+// kernel, 3 behind the miss kernel (the local-pool route: 0 and 1 around a segment's one launch).  round_event records one
+// of them (and creates the round's four the first time); round_ms reads the three intervals back after the frame.
+static int round_event(rayrs_scene::Pool& pl, uint32_t r, uint32_t k, hipStream_t stream) {
+    while (pl.ev_round.size() < 4 * (size_t)(r + 1)) {
+        Event e;
+        HIP_TRY(e.create());
+        pl.ev_round.push_back(std::move(e));
+    }
+    HIP_TRY(hipEventRecord(pl.ev_round[4 * (size_t)r + k], stream));
+    return RAYRS_OK;
+}
+
+static int round_ms(const rayrs_scene* scene, uint32_t r, float ms[3]) {
+    const Event* e = &scene->pool.ev_round[4 * (size_t)r];
+    ms[1] = ms[2] = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms[0], e[0], e[1]));
+    if (scene->last_local) return RAYRS_OK;  // one kernel per segment
+    HIP_TRY(hipEventElapsedTime(&ms[1], e[1], e[2]));
+    HIP_TRY(hipEventElapsedTime(&ms[2], e[2], e[3]));
+    return RAYRS_OK;
+}
 
 // rayrs_lab.h: HIP-event times of the last render's path rounds, three per round (traversal, hit, miss kernel; the
 // local-pool route: its launch, 0, 0).  Returns the number of rounds; writes at most cap_rounds of them.
 extern "C" int rayrs_lab_round_ms(rayrs_scene* scene, float* out, uint32_t cap_rounds) {
     if (!scene || scene->device < 0 || scene->pending) return RAYRS_INVALID_ARG;
     HIP_TRY(hipSetDevice(scene->device));
-    const rayrs_scene::Pool& pl = scene->pool;
-    for (uint32_t r = 0; r < pl.timed_rounds && r < cap_rounds && out; r++) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, pl.ev_round[4 * r], pl.ev_round[4 * r + 1]));
-        out[3 * r] = ms, out[3 * r + 1] = out[3 * r + 2] = 0.f;
-        if (scene->last_local) continue;
-        HIP_TRY(hipEventElapsedTime(&ms, pl.ev_round[4 * r + 1], pl.ev_round[4 * r + 2]));
-        out[3 * r + 1] = ms;
-        HIP_TRY(hipEventElapsedTime(&ms, pl.ev_round[4 * r + 2], pl.ev_round[4 * r + 3]));
-        out[3 * r + 2] = ms;
-    }
-    return (int)pl.timed_rounds;
+    for (uint32_t r = 0; r < scene->pool.timed_rounds && r < cap_rounds && out; r++) RAYRS_TRY(round_ms(scene, r, out + 3 * r));
+    return (int)scene->pool.timed_rounds;
 }
 
 // rayrs_lab.h: the kernels' development knobs (tests/ and scripts/ubench/ only)
@@ -529,8 +479,7 @@ int rayrs_lab_set(rayrs_scene* scene, const rayrs_lab_tuning* lab) {
         return RAYRS_INVALID_ARG;
     if (lab->local_reserve != 0u && (lab->local_reserve < 8u || lab->local_reserve > 4096u)) return RAYRS_INVALID_ARG;
     if (lab->local_segment_items != 0u && lab->local_segment_items < 65536u) return RAYRS_INVALID_ARG;
-    const int st = scene_quiesce(scene);
-    if (st != RAYRS_OK) return st;
+    RAYRS_TRY(scene_quiesce(scene));
     scene->lab = *lab;
     if (scene->device >= 0) return scene_configure_traversal(scene);
     return RAYRS_OK;
@@ -618,17 +567,17 @@ int rayrs_camera_new(const double origin[3], const double up[3], const double lo
 
 // ------------------------------------------------------------------ render
 
-static SceneDev make_scene_dev(const rayrs_scene* s, bool exact) {
+extern "C++" SceneDev rayrs::make_scene_dev(const rayrs_scene* s, bool exact) {
     SceneDev sc;
     std::memset(&sc, 0, sizeof(sc));
     const int which = s->walk_index(exact);
     const WalkTree& t = s->tree(which);
     const rayrs_scene::Walk& w = s->trav[which];
-    sc.hot = which == 2 ? s->d_hot : nullptr;
-    sc.nodes = w.d_nodes;
-    sc.prims = s->d_prims;
-    sc.surfaces = s->d_surfaces;
-    sc.hdri = s->d_hdri;
+    sc.hot = which == 2 ? s->d_hot.as<HotGroupDev>() : nullptr;
+    sc.nodes = w.d_nodes.as<>();
+    sc.prims = s->d_prims.as<>();
+    sc.surfaces = s->d_surfaces.as<SurfaceDev>();
+    sc.hdri = s->d_hdri.as<float>();
     sc.hdri_w = s->flat.hdri_w;
     sc.hdri_h = s->flat.hdri_h;
     sc.hdri_wm1 = (double)(s->flat.hdri_w - 1u);
@@ -672,7 +621,7 @@ static bool camera_is_far(const rayrs_scene* s, const rayrs_camera* c) {
     return d2 > RAYRS_FAR_DIAGONALS * RAYRS_FAR_DIAGONALS * e2 || (small > 0.0 && d2 > RAYRS_FAR_PRIMITIVES * RAYRS_FAR_PRIMITIVES * small * small);
 }
 
-static CameraDev make_camera_dev(const rayrs_camera* c) {
+extern "C++" CameraDev rayrs::make_camera_dev(const rayrs_camera* c) {
     CameraDev cam;
     std::memset(&cam, 0, sizeof(cam));
     for (int i = 0; i < 3; i++) {
@@ -689,9 +638,9 @@ static CameraDev make_camera_dev(const rayrs_camera* c) {
     return cam;
 }
 
-// The traversal kernel's launch settings, for a render and for rayrs_test_trace alike: its scheduling thresholds (rayrs_lab.h),
-// its grid, and the windows of a pool of n_windows dealt round robin.
-static void trav_thresholds(const rayrs_scene* s, bool exact, RenderDev& rp) {
+// The traversal kernel's launch settings on a pool of np slots, for a render and for rayrs_test_trace alike: its scheduling
+// thresholds (rayrs_lab.h) and the windows dealt round robin into rp, its grid as the result.
+extern "C++" uint32_t rayrs::trav_settings(const rayrs_scene* s, bool exact, uint32_t np, RenderDev& rp) {
     const rayrs_lab_tuning& lab = s->lab;
     rp.refill_min = lab.refill_min ? lab.refill_min : 52u;
     // (a leaf phase once this many lanes stand on a leaf: 24 where a leaf is one primitive -- the fast walk's tree: 612 -> 604 ms
@@ -704,20 +653,228 @@ static void trav_thresholds(const rayrs_scene* s, bool exact, RenderDev& rp) {
     // (pre-tested rays -- a scene with a hot group, wavefront.hip finish_rays -- wanted a refill_min of 56 while a lane stood idle
     // on its leaf: 664 -> 659 ms of traversal, profiles/r06_tuning_sweep.txt; with the leaf groups set aside 52 is best again:
     // 626 -> 619 ms, profiles/r06_leaf_queue.txt)
-}
-
-static uint32_t trav_grid_blocks(const rayrs_scene* s, bool exact) {
     uint32_t trav_bpc = (uint32_t)s->trav[s->walk_index(exact)].blocks_per_cu;
-    if (s->lab.trav_blocks_per_cu && s->lab.trav_blocks_per_cu < trav_bpc) trav_bpc = s->lab.trav_blocks_per_cu;
-    return (uint32_t)s->cu_count * trav_bpc;
+    if (lab.trav_blocks_per_cu && lab.trav_blocks_per_cu < trav_bpc) trav_bpc = lab.trav_blocks_per_cu;
+    const uint32_t blocks = (uint32_t)s->cu_count * trav_bpc;
+    // whole round-robin rounds covering about static_pct % of the pool's windows
+    const uint32_t static_pct = lab.static_pct ? lab.static_pct : 50u;  // (rayrs_lab_set: at most 100)
+    const uint64_t n_waves = (uint64_t)blocks * 4u;
+    rp.static_windows = (uint32_t)((uint64_t)(np / wf_window_slots()) * static_pct / 100u / n_waves * n_waves);
+    return blocks;
 }
 
-static uint32_t trav_static_windows(const rayrs_scene* s, uint32_t n_windows, uint32_t trav_blocks) {
-    uint32_t static_pct = s->lab.static_pct ? s->lab.static_pct : 50u;
-    if (static_pct > 100) static_pct = 100;
-    // whole round-robin rounds covering about static_pct % of the pool's windows
-    const uint64_t n_waves = (uint64_t)trav_blocks * 4u;
-    return (uint32_t)((uint64_t)n_windows * static_pct / 100u / n_waves * n_waves);
+// A pool of np slots (whole windows) in one block -- the slot records, the light entries, the state bytes -- walked by
+// trav_blocks workgroups whose stacks overflow into `spill`.
+extern "C++" WfDev rayrs::pool_wf(const DevBuf& block, uint32_t np, const DevBuf& ctl, uint32_t trav_blocks, const DevBuf& spill) {
+    WfDev wf;
+    std::memset(&wf, 0, sizeof(wf));
+    wf.slots = block.as<PathSlot>();
+    wf.light = reinterpret_cast<double*>(wf.slots + np);
+    wf.state = reinterpret_cast<uint8_t*>(wf.light + (size_t)np * 4u);
+    wf.ctl = ctl.as<WfCtl>();
+    wf.np = np;
+    wf.trav_threads = trav_blocks * 256u;
+    wf.stack_spill = spill.as<uint32_t>();
+    return wf;
+}
+
+// What a frame is, worked out before anything is allocated or enqueued: plan_frame calls nothing in HIP.
+struct FramePlan {
+    SceneDev sc;
+    CameraDev cam;
+    RenderDev rp;  // complete but for `partial`
+    bool exact, eager_light, use_local;  // use_local: the local-pool route (else the streaming route)
+    uint64_t partial_need;     // item sums the frame needs at a time
+    // the local-pool route: launches over segments of seg_tiles whole tiles, by local_blocks workgroups
+    uint64_t tile_items, seg_tiles, seg_items;
+    uint32_t local_blocks;  // (0: not this route)
+    // the streaming route: live_total slots in a pool of np, the traversal grid, the gen / hit / miss kernels' common grid
+    uint64_t live_total;
+    uint32_t np, trav_blocks, flat_blocks;  // (np 0, and with it flat_blocks and spill_words: not this route)
+    size_t spill_words;
+};
+
+// The frame's items: the (pixel, chunk) pairs of this rank's 8x8 tiles (the caller refuses 2^32 of them and more).
+static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, void* out_device) {
+    RenderDev rp;
+    std::memset(&rp, 0, sizeof(rp));
+    rp.spp = params->spp;
+    rp.max_bounces = params->max_bounces;
+    rp.seed = params->seed;
+    rp.chunk = (params->sample_chunk == 0 || params->sample_chunk >= params->spp) ? params->spp : params->sample_chunk;
+    rp.nchunks = (rp.spp + rp.chunk - 1) / rp.chunk;
+    rp.tile_rank = params->tile_rank;
+    rp.tile_ranks = params->tile_ranks;
+    rp.tiles_x = (camera->x_pixels + 7) / 8;
+    rp.tiles_y = (camera->y_pixels + 7) / 8;
+    const uint64_t n_tiles = (uint64_t)rp.tiles_x * rp.tiles_y;
+    const uint64_t n_local = n_tiles > rp.tile_rank ? (n_tiles - rp.tile_rank + rp.tile_ranks - 1) / rp.tile_ranks : 0;
+    rp.n_local_tiles = (uint32_t)n_local;
+    rp.total_items = n_local * rp.nchunks * 64ull;
+    rp.inv_nchunks = 1.0 / (double)rp.nchunks;
+    rp.inv_tiles_x = 1.0 / (double)rp.tiles_x;
+    rp.count_work = params->count_work ? 1u : 0u;
+    rp.out_format = params->out_format;
+    rp.out = out_device;
+    rp.counters = scene->d_counters.as<Counters>();
+    rp.next_item = scene->d_next_item.as<unsigned long long>();
+    return rp;
+}
+
+static int plan_frame(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, void* out_device,
+                      FramePlan& p) {
+    const rayrs_lab_tuning& lab = scene->lab;
+    RenderDev& rp = p.rp = make_render_dev(scene, camera, params, out_device);
+    if (rp.total_items >= (1ull << 32)) return RAYRS_UNSUPPORTED;
+    // Item sums: 24 bytes per (pixel, chunk) item, added per pixel in chunk order by the resolve kernel.  The streaming
+    // kernels finish items in no particular order, so the array covers the frame.  The local-pool route renders the frame
+    // as a sequence of launches over segments of whole tiles and resolves each segment behind its launch: one segment's
+    // worth is all it needs (config 4: 3.2 GB instead of 25.8).
+    p.use_local = scene->local_ok && scene->tuning.local_pool != 1u;
+    p.tile_items = (uint64_t)rp.nchunks * 64u;
+    uint64_t seg_want = lab.local_segment_items ? lab.local_segment_items : LOCAL_SEGMENT_ITEMS;
+    // (a frame stays within LOCAL_MAX_SEGMENTS launches: larger segments rather than a refused frame)
+    if ((rp.total_items + seg_want - 1) / seg_want > LOCAL_MAX_SEGMENTS) seg_want = (rp.total_items + LOCAL_MAX_SEGMENTS - 1) / LOCAL_MAX_SEGMENTS;
+    p.seg_tiles = (seg_want + p.tile_items - 1) / p.tile_items > 0 ? (seg_want + p.tile_items - 1) / p.tile_items : 1;
+    p.seg_items = p.seg_tiles * p.tile_items;
+    p.partial_need = p.use_local && p.seg_items < rp.total_items ? p.seg_items : rp.total_items;
+    if (p.use_local && p.seg_items >= (1ull << 32)) return RAYRS_UNSUPPORTED;  // (one tile's chunks alone: spp beyond 2^27)
+    // LP_WPS workgroups of four waves per CU; fewer when the frame has fewer items than resident paths
+    p.local_blocks = (uint32_t)scene->cu_count * (uint32_t)scene->local_blocks_per_cu;
+    const uint64_t most_items = rp.total_items < p.seg_items ? rp.total_items : p.seg_items;
+    const uint64_t want_blocks = (most_items + 4u * LP_PATHS_PER_WAVE - 1) / (4u * LP_PATHS_PER_WAVE);
+    if (want_blocks < p.local_blocks) p.local_blocks = (uint32_t)(want_blocks ? want_blocks : 1);
+    if (!p.use_local || rp.total_items == 0) p.local_blocks = 0;
+
+    p.exact = params->fast_traversal == 0u || camera_is_far(scene, camera);
+    p.sc = make_scene_dev(scene, p.exact);
+    p.cam = make_camera_dev(camera);
+
+    // ---- path pool.  A traversal launch works through the whole pool, and its ramp-up
+    // and drain are a fixed cost, so large pools win even when that leaves only one or two
+    // items per slot -- up to the point where the hit and miss kernels lose more to the larger
+    // footprint.  Swept on the headline frame with one-line slots: 24 M slots 1520 ms, 32 M 1516,
+    // 48 M 1497, 64 M 1467, 96 M 1468, 128 M 1481, 192 M 1498 (round 1, 192-byte slots: 32 M).
+    // Swept again on round 3's kernels (the traversal kernel faster, its fixed cost per launch the same): 64 M 1369 ms,
+    // 80 M 1372, 96 M 1368, 112 M 1353, 128 M 1356, 160 M 1353, 192 M 1350: 112 M slots (18 GB of the 288 GB), 84 rounds.
+    // And on round 6's (the hit kernel at three waves per SIMD, the cheap queries answered by the kernels that make the rays):
+    // 80 M 1298 ms, 96 M 1290, 112 M 1276, 128 M 1278, 144 M 1267, 160 M 1250, 192 M 1250, 224 M 1246, 256 M 1242, 320 M 1242
+    // (profiles/r06_leaf_queue.txt (12)): 256 M slots (43 GB), 52 rounds.
+    // A frame should also last some tens of rounds, or filling and draining the pool is all it does: at most one
+    // slot per 12 samples -- which is what a one-eighth tile share of the headline frame gets (44.7 M: 33.5 M 189 ms,
+    // 48 M 184, 64 M 186).
+    constexpr uint64_t POOL_MAX_SLOTS = 1ull << 28;
+    uint64_t np64 = rp.total_items;
+    if (np64 > POOL_MAX_SLOTS) np64 = POOL_MAX_SLOTS;
+    {
+        const uint64_t samples = rp.n_local_tiles * 64ull * rp.spp;
+        const uint64_t by_work = samples / 12u > (1ull << 20) ? samples / 12u : (1ull << 20);
+        if (np64 > by_work) np64 = by_work;
+    }
+    if (scene->tuning.pool_slots) np64 = scene->tuning.pool_slots;
+    if (np64 > rp.total_items) np64 = rp.total_items;
+    p.live_total = np64;
+    const bool streaming = !p.use_local && rp.total_items > 0;  // (the local-pool route keeps its paths in LDS)
+    p.np = streaming ? (uint32_t)((p.live_total + 1023ull) & ~1023ull) : 0u;  // whole windows
+    p.trav_blocks = trav_settings(scene, p.exact, p.np, rp);
+    p.spill_words = streaming ? (size_t)(p.sc.stack_depth - p.sc.stack_lds) * p.trav_blocks * 256u : 0;
+
+    // A path's light lives in a side array and only while it is not +0 (wavefront.h PathSlot).  Where a surface
+    // emits, paths do get light, and the hit and miss kernels request the side array's entry together with the
+    // slot instead of after it.
+    p.eager_light = lab.eager_light != 0u;
+    for (const SurfaceDev& sf : scene->surfaces)
+        if (sf.emit[0] != 0.0 || sf.emit[1] != 0.0 || sf.emit[2] != 0.0) p.eager_light = true;
+
+    // the gen, hit and miss kernels run with this one grid, so wave w means the same windows in all three: one
+    // wave per window, at most 8 ... 24 workgroups per CU (below)
+    const uint32_t n_windows = p.np / wf_window_slots();
+    p.flat_blocks = (n_windows + 3u) / 4u;
+    // (8 ... 24 workgroups per CU, so that a wave has about nine windows: with the hit kernel at three resident workgroups
+    // per CU a finer grid evens out the end of a launch -- hit 411 -> 404 ms on the headline's 218 k windows at 24 -- but
+    // a wave that gets three windows spends its time on its first and last batch: config 3's 87 k windows want 8 or 9
+    // (198 against 200.5 ms at 24); profiles/r06_leaf_queue.txt (9))
+    uint32_t per_cu = lab.flat_blocks_per_cu;
+    if (!per_cu) {
+        per_cu = n_windows / (36u * (uint32_t)scene->cu_count);
+        per_cu = per_cu < FLAT_BLOCKS_PER_CU_MIN ? FLAT_BLOCKS_PER_CU_MIN : per_cu > FLAT_BLOCKS_PER_CU_MAX ? FLAT_BLOCKS_PER_CU_MAX : per_cu;
+    }
+    const uint32_t flat_cap = (uint32_t)scene->cu_count * per_cu;
+    if (p.flat_blocks > flat_cap) p.flat_blocks = flat_cap;
+    return RAYRS_OK;
+}
+
+// ---- one launch per segment of the frame's items; a launch ends when its last path has (local_pool.hip)
+static int enqueue_local(rayrs_scene* scene, const FramePlan& p, hipStream_t stream) {
+    rayrs_scene::Pool& pl = scene->pool;
+    const RenderDev& rp = p.rp;
+    const uint64_t n_seg = (rp.total_items + p.seg_items - 1) / p.seg_items;
+    for (uint64_t seg = 0; seg < n_seg; seg++) {
+        LocalDev lp;
+        lp.light = scene->d_local_light.as<double>();
+        lp.next_item = scene->d_local_items.as<unsigned long long>() + seg;
+        lp.item_base = seg * p.seg_items;
+        lp.item_count = rp.total_items - lp.item_base < p.seg_items ? rp.total_items - lp.item_base : p.seg_items;
+        RenderDev rseg = rp;
+        rseg.partial_item0 = lp.item_base;
+        const uint64_t share = lp.item_count / ((uint64_t)p.local_blocks * 4u * 16u);  // a sixteenth of a wave's share
+        lp.reserve = (uint32_t)(share < 8u ? 8u : share > 256u ? 256u : share);
+        if (scene->lab.local_reserve) lp.reserve = scene->lab.local_reserve;
+        lp.pad = 0;
+        RAYRS_TRY(round_event(pl, (uint32_t)seg, 0, stream));
+        HIP_TRY(lp_launch(scene->flat.compact, rp.count_work != 0u, p.sc, scene->local, p.cam, rseg, lp, p.local_blocks, stream));
+        RAYRS_TRY(round_event(pl, (uint32_t)seg, 1, stream));
+        // the segment's tiles, resolved behind its launch (the next segment reuses the item-sum array)
+        HIP_TRY(launch_resolve(p.cam, rseg, (uint32_t)(seg * p.seg_tiles), (uint32_t)(lp.item_count / p.tile_items), stream));
+        pl.timed_rounds = (uint32_t)seg + 1;
+    }
+    scene->rounds = (uint32_t)n_seg;
+    return RAYRS_OK;
+}
+
+static int enqueue_streaming(rayrs_scene* scene, const FramePlan& p, const WfDev& wf, hipStream_t stream) {
+    rayrs_scene::Pool& pl = scene->pool;
+    const RenderDev& rp = p.rp;
+    uint32_t* h_live = pl.h_live.as<uint32_t>();
+    HIP_TRY(wf_launch_init(wf, (uint32_t)p.live_total, stream));
+    HIP_TRY(wf_launch_gen(scene->flat.compact, p.sc, p.cam, rp, wf, p.flat_blocks, stream));  // initial fill; later samples start in hit/miss
+    h_live[0] = h_live[1] = (uint32_t)p.live_total;
+    // Rounds are enqueued in batches; the live-slot count of batch b is read back while batch b+1 is
+    // already queued, so the GPU never waits for the host.  Rounds behind the frame's last one find
+    // live_slots == 0 and return at once; batches shrink from 16 rounds to 4 once fewer than an eighth of
+    // the slots have work, so that at most 7 such rounds are queued after the end.
+    constexpr uint32_t MAX_TIMED = 8192;
+    uint32_t it = 0;
+    uint32_t batch = 16;
+    for (uint32_t b = 0;; b++) {
+        for (uint32_t k = 0; k < batch; k++, it++) {
+            const bool timed = it < MAX_TIMED;  // (rounds beyond the event pool: rayrs_render_finish extrapolates)
+            if (timed) RAYRS_TRY(round_event(pl, it, 0, stream));
+            HIP_TRY(wf_launch_trav(scene->flat.compact, rp.count_work != 0u, p.sc, rp, wf, p.trav_blocks, stream));
+            if (timed) RAYRS_TRY(round_event(pl, it, 1, stream));
+            HIP_TRY(wf_launch_hit(scene->flat.compact, p.eager_light, p.sc, p.cam, rp, wf, p.flat_blocks, stream));
+            if (timed) RAYRS_TRY(round_event(pl, it, 2, stream));
+            HIP_TRY(wf_launch_miss(scene->flat.compact, p.eager_light, p.sc, p.cam, rp, wf, p.flat_blocks, stream));
+            if (timed) {
+                RAYRS_TRY(round_event(pl, it, 3, stream));
+                pl.timed_rounds = it + 1;
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(&h_live[b & 1u], &wf.ctl->live_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(pl.ev_batch[b & 1u], stream));
+        if (b > 0) {
+            HIP_TRY(hipEventSynchronize(pl.ev_batch[(b - 1u) & 1u]));
+            const uint64_t seen = h_live[(b - 1u) & 1u];
+            if (seen == 0u) break;
+            batch = seen * 8u < p.live_total ? 4u : 16u;
+        }
+        if (it > (1u << 26)) {
+            g_last_error = "path rounds did not terminate";
+            return RAYRS_HIP_ERROR;
+        }
+    }
+    scene->rounds = it;
+    return RAYRS_OK;
 }
 
 int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params,
@@ -740,266 +897,36 @@ int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const ra
         HIP_TRY(hipStreamSynchronize(scene->last_stream));
         scene->pending = false;
     }
-    const rayrs_lab_tuning& lab = scene->lab;
 
-    RenderDev rp;
-    std::memset(&rp, 0, sizeof(rp));
-    rp.spp = params->spp;
-    rp.max_bounces = params->max_bounces;
-    rp.seed = params->seed;
-    rp.chunk = (params->sample_chunk == 0 || params->sample_chunk >= params->spp) ? params->spp : params->sample_chunk;
-    rp.nchunks = (rp.spp + rp.chunk - 1) / rp.chunk;
-    rp.tile_rank = params->tile_rank;
-    rp.tile_ranks = params->tile_ranks;
-    rp.tiles_x = (camera->x_pixels + 7) / 8;
-    rp.tiles_y = (camera->y_pixels + 7) / 8;
-    const uint64_t n_tiles = (uint64_t)rp.tiles_x * rp.tiles_y;
-    const uint64_t n_local = n_tiles > rp.tile_rank ? (n_tiles - rp.tile_rank + rp.tile_ranks - 1) / rp.tile_ranks : 0;
-    rp.n_local_tiles = (uint32_t)n_local;
-    rp.total_items = n_local * rp.nchunks * 64ull;
-    rp.inv_nchunks = 1.0 / (double)rp.nchunks;
-    rp.inv_tiles_x = 1.0 / (double)rp.tiles_x;
-    if (rp.total_items >= (1ull << 32)) return RAYRS_UNSUPPORTED;
-    rp.count_work = params->count_work ? 1u : 0u;
-    rp.out_format = params->out_format;
-    rp.out = out_device;
-    rp.counters = scene->d_counters;
+    FramePlan p;
+    RAYRS_TRY(plan_frame(scene, camera, params, out_device, p));
+    scene->last_exact = p.exact;
 
-    // Item sums: 24 bytes per (pixel, chunk) item, added per pixel in chunk order by the resolve kernel.  The streaming
-    // kernels finish items in no particular order, so the array covers the frame.  The local-pool route renders the frame
-    // as a sequence of launches over segments of whole tiles and resolves each segment behind its launch: one segment's
-    // worth is all it needs (config 4: 3.2 GB instead of 25.8).
-    const bool use_local = scene->local_ok && scene->tuning.local_pool != 1u;
-    const uint64_t tile_items = (uint64_t)rp.nchunks * 64u;
-    uint64_t seg_want = lab.local_segment_items ? lab.local_segment_items : LOCAL_SEGMENT_ITEMS;
-    // (a frame stays within LOCAL_MAX_SEGMENTS launches: larger segments rather than a refused frame)
-    if ((rp.total_items + seg_want - 1) / seg_want > LOCAL_MAX_SEGMENTS) seg_want = (rp.total_items + LOCAL_MAX_SEGMENTS - 1) / LOCAL_MAX_SEGMENTS;
-    const uint64_t seg_tiles = (seg_want + tile_items - 1) / tile_items > 0 ? (seg_want + tile_items - 1) / tile_items : 1;
-    const uint64_t seg_items = seg_tiles * tile_items;
-    const uint64_t partial_need = use_local && seg_items < rp.total_items ? seg_items : rp.total_items;
-    if (use_local && seg_items >= (1ull << 32)) return RAYRS_UNSUPPORTED;  // (one tile's chunks alone: spp beyond 2^27)
-    if (partial_need > scene->partial_items) {
-        if (scene->d_partial) HIP_TRY(hipFree(scene->d_partial));
-        scene->d_partial = nullptr;
-        scene->partial_items = 0;
-        HIP_TRY(hipMalloc((void**)&scene->d_partial, (size_t)partial_need * 3 * sizeof(double)));
-        scene->partial_items = (size_t)partial_need;
-    }
-    rp.partial = scene->d_partial;
-    rp.partial_item0 = 0;
-
-    const bool exact = params->fast_traversal == 0u || camera_is_far(scene, camera);
-    scene->last_exact = exact;
-    trav_thresholds(scene, exact, rp);
-    const SceneDev sc = make_scene_dev(scene, exact);
-    const CameraDev cam = make_camera_dev(camera);
-
-    // ---- path pool.  A traversal launch works through the whole pool, and its ramp-up
-    // and drain are a fixed cost, so large pools win even when that leaves only one or two
-    // items per slot -- up to the point where the hit and miss kernels lose more to the larger
-    // footprint.  Swept on the headline frame with one-line slots: 24 M slots 1520 ms, 32 M 1516,
-    // 48 M 1497, 64 M 1467, 96 M 1468, 128 M 1481, 192 M 1498 (round 1, 192-byte slots: 32 M).
-    // Swept again on round 3's kernels (the traversal kernel faster, its fixed cost per launch the same): 64 M 1369 ms,
-    // 80 M 1372, 96 M 1368, 112 M 1353, 128 M 1356, 160 M 1353, 192 M 1350: 112 M slots (18 GB of the 288 GB), 84 rounds.
-    // And on round 6's (the hit kernel at three waves per SIMD, the cheap queries answered by the kernels that make the rays):
-    // 80 M 1298 ms, 96 M 1290, 112 M 1276, 128 M 1278, 144 M 1267, 160 M 1250, 192 M 1250, 224 M 1246, 256 M 1242, 320 M 1242
-    // (profiles/r06_leaf_queue.txt (12)): 256 M slots (43 GB), 52 rounds.
-    // A frame should also last some tens of rounds, or filling and draining the pool is all it does: at most one
-    // slot per 12 samples -- which is what a one-eighth tile share of the headline frame gets (44.7 M: 33.5 M 189 ms,
-    // 48 M 184, 64 M 186).
-    constexpr uint64_t POOL_MAX_SLOTS = 1ull << 28;
-    uint64_t np64 = rp.total_items;
-    if (np64 > POOL_MAX_SLOTS) np64 = POOL_MAX_SLOTS;
-    {
-        const uint64_t samples = n_local * 64ull * rp.spp;
-        const uint64_t by_work = samples / 12u > (1ull << 20) ? samples / 12u : (1ull << 20);
-        if (np64 > by_work) np64 = by_work;
-    }
-    if (scene->tuning.pool_slots) np64 = scene->tuning.pool_slots;
-    if (np64 > rp.total_items) np64 = rp.total_items;
-    const uint64_t live_total = np64;
-
-    const bool compact = scene->flat.compact;
-    const bool count = params->count_work != 0;
-    const uint32_t trav_blocks = trav_grid_blocks(scene, exact);
-
-    // A path's light lives in a side array and only while it is not +0 (wavefront.h PathSlot).  Where a surface
-    // emits, paths do get light, and the hit and miss kernels request the side array's entry together with the
-    // slot instead of after it.
-    bool eager_light = lab.eager_light != 0u;
-    for (const SurfaceDev& sf : scene->surfaces)
-        if (sf.emit[0] != 0.0 || sf.emit[1] != 0.0 || sf.emit[2] != 0.0) eager_light = true;
-    constexpr size_t slot_bytes = sizeof(PathSlot) + 4 * sizeof(double);  // slot + its entry of the light array
+    // ---- what the plan needs of the scene's buffers, which only grow (nothing of the route the frame does not take)
     rayrs_scene::Pool& pl = scene->pool;
-    WfDev wf = pl.wf;
-    uint32_t flat_blocks = 0;
-    if (!use_local && rp.total_items > 0) {  // (the local-pool route keeps its paths in LDS)
-        const uint32_t np = (uint32_t)((live_total + 1023ull) & ~1023ull);  // whole windows
-        const size_t block_bytes = (size_t)np * (slot_bytes + 1u);
-        if (block_bytes > pl.block_bytes || !pl.block) {
-            if (pl.block) HIP_TRY(hipFree(pl.block));
-            pl.block = nullptr;
-            pl.block_bytes = 0;
-            HIP_TRY(hipMalloc(&pl.block, block_bytes));
-            pl.block_bytes = block_bytes;
-        }
-        pl.wf.slots = static_cast<PathSlot*>(pl.block);
-        pl.wf.light = reinterpret_cast<double*>(pl.wf.slots + np);
-        pl.wf.state = reinterpret_cast<uint8_t*>(pl.wf.light + (size_t)np * 4u);
-        wf = pl.wf;
-        wf.np = np;
-        const uint32_t n_windows = np / wf_window_slots();
-        rp.static_windows = trav_static_windows(scene, n_windows, trav_blocks);
+    HIP_TRY(scene->d_partial.reserve((size_t)p.partial_need * 3 * sizeof(double)));
+    p.rp.partial = scene->d_partial.as<double>();
+    HIP_TRY(scene->d_local_light.reserve((size_t)p.local_blocks * 4u * LP_PATHS_PER_WAVE * 4 * sizeof(double)));
+    HIP_TRY(pl.block.reserve((size_t)p.np * POOL_SLOT_BYTES));
+    HIP_TRY(pl.d_wave_items.reserve((size_t)p.flat_blocks * 4u * 2 * sizeof(unsigned long long)));
+    HIP_TRY(pl.d_stack_spill.reserve(p.spill_words * sizeof(uint32_t)));
+    WfDev wf = pool_wf(pl.block, p.np, pl.d_ctl, p.trav_blocks, pl.d_stack_spill);
+    wf.n_flat_waves = p.flat_blocks * 4u;
+    wf.wave_items = pl.d_wave_items.as<unsigned long long>();
 
-        // the gen, hit and miss kernels run with this one grid, so wave w means the same windows in all three: one
-        // wave per window, at most 8 ... 24 workgroups per CU (below)
-        uint32_t fb = (n_windows + 3u) / 4u;
-        // (8 ... 24 workgroups per CU, so that a wave has about nine windows: with the hit kernel at three resident workgroups
-        // per CU a finer grid evens out the end of a launch -- hit 411 -> 404 ms on the headline's 218 k windows at 24 -- but
-        // a wave that gets three windows spends its time on its first and last batch: config 3's 87 k windows want 8 or 9
-        // (198 against 200.5 ms at 24); profiles/r06_leaf_queue.txt (9))
-        uint32_t per_cu = lab.flat_blocks_per_cu;
-        if (!per_cu) {
-            per_cu = n_windows / (36u * (uint32_t)scene->cu_count);
-            per_cu = per_cu < FLAT_BLOCKS_PER_CU_MIN ? FLAT_BLOCKS_PER_CU_MIN : per_cu > FLAT_BLOCKS_PER_CU_MAX ? FLAT_BLOCKS_PER_CU_MAX : per_cu;
-        }
-        const uint32_t flat_cap = (uint32_t)scene->cu_count * per_cu;
-        if (fb > flat_cap) fb = flat_cap;
-        flat_blocks = fb;
-        wf.n_flat_waves = fb * 4u;
-        if (wf.n_flat_waves > pl.wave_items_cap) {
-            if (pl.d_wave_items) HIP_TRY(hipFree(pl.d_wave_items));
-            pl.d_wave_items = nullptr;
-            pl.wave_items_cap = 0;
-            HIP_TRY(hipMalloc((void**)&pl.d_wave_items, (size_t)wf.n_flat_waves * 2 * sizeof(unsigned long long)));
-            pl.wave_items_cap = wf.n_flat_waves;
-        }
-        wf.wave_items = pl.d_wave_items;
-        wf.trav_threads = trav_blocks * 256u;
-        {
-            const size_t words = (size_t)(sc.stack_depth - sc.stack_lds) * wf.trav_threads;
-            if (words > pl.stack_spill_words) {
-                if (pl.d_stack_spill) HIP_TRY(hipFree(pl.d_stack_spill));
-                pl.d_stack_spill = nullptr;
-                pl.stack_spill_words = 0;
-                HIP_TRY(hipMalloc((void**)&pl.d_stack_spill, words * sizeof(uint32_t)));
-                pl.stack_spill_words = words;
-            }
-            wf.stack_spill = pl.d_stack_spill;
-        }
-    }
-    rp.next_item = scene->d_next_item;
     pl.timed_rounds = 0;
-
-    HIP_TRY(hipMemsetAsync(scene->d_counters, 0, sizeof(Counters), stream));
-    HIP_TRY(hipMemsetAsync(scene->d_next_item, 0, sizeof(unsigned long long), stream));
-    if (use_local) HIP_TRY(hipMemsetAsync(scene->d_local_items, 0, LOCAL_MAX_SEGMENTS * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(p.rp.counters, 0, sizeof(Counters), stream));
+    HIP_TRY(hipMemsetAsync(p.rp.next_item, 0, sizeof(unsigned long long), stream));
+    if (p.use_local) HIP_TRY(hipMemsetAsync(scene->d_local_items.as<>(), 0, LOCAL_MAX_SEGMENTS * sizeof(unsigned long long), stream));
     HIP_TRY(hipEventRecord(scene->ev[0], stream));
     scene->rounds = 0;
-    scene->last_local = use_local;
-    auto round_events = [&](size_t n) -> int {
-        while (pl.ev_round.size() < n) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            pl.ev_round.push_back(e);
-        }
-        return RAYRS_OK;
-    };
-    if (use_local && rp.total_items > 0) {
-        // ---- one launch per segment of the frame's items; a launch ends when its last path has (local_pool.hip)
-        const uint64_t n_seg = (rp.total_items + seg_items - 1) / seg_items;
-        // LP_WPS workgroups of four waves per CU; fewer when the frame has fewer items than resident paths
-        uint32_t blocks = (uint32_t)scene->cu_count * (uint32_t)scene->local_blocks_per_cu;
-        {
-            const uint64_t most_items = rp.total_items < seg_items ? rp.total_items : seg_items;
-            const uint64_t want = (most_items + 4u * LP_PATHS_PER_WAVE - 1) / (4u * LP_PATHS_PER_WAVE);
-            if (want < blocks) blocks = (uint32_t)(want ? want : 1);
-        }
-        const size_t paths = (size_t)blocks * 4u * LP_PATHS_PER_WAVE;
-        if (paths > scene->local_light_paths) {
-            if (scene->d_local_light) HIP_TRY(hipFree(scene->d_local_light));
-            scene->d_local_light = nullptr;
-            scene->local_light_paths = 0;
-            HIP_TRY(hipMalloc((void**)&scene->d_local_light, paths * 4 * sizeof(double)));
-            scene->local_light_paths = paths;
-        }
-        for (uint64_t seg = 0; seg < n_seg; seg++) {
-            LocalDev lp;
-            lp.light = scene->d_local_light;
-            lp.next_item = scene->d_local_items + seg;
-            lp.item_base = seg * seg_items;
-            lp.item_count = rp.total_items - lp.item_base < seg_items ? rp.total_items - lp.item_base : seg_items;
-            RenderDev rseg = rp;
-            rseg.partial_item0 = lp.item_base;
-            {
-                const uint64_t share = lp.item_count / ((uint64_t)blocks * 4u * 16u);  // a sixteenth of a wave's share
-                lp.reserve = (uint32_t)(share < 8u ? 8u : share > 256u ? 256u : share);
-                if (lab.local_reserve) lp.reserve = lab.local_reserve;
-                lp.pad = 0;
-            }
-            {
-                const int st = round_events(4 * (size_t)(seg + 1));
-                if (st != RAYRS_OK) return st;
-            }
-            HIP_TRY(hipEventRecord(pl.ev_round[4 * seg], stream));
-            HIP_TRY(lp_launch(compact, count, sc, scene->local, cam, rseg, lp, blocks, stream));
-            HIP_TRY(hipEventRecord(pl.ev_round[4 * seg + 1], stream));
-            // the segment's tiles, resolved behind its launch (the next segment reuses the item-sum array)
-            HIP_TRY(launch_resolve(cam, rseg, (uint32_t)(seg * seg_tiles), (uint32_t)(lp.item_count / tile_items), stream));
-            pl.timed_rounds = (uint32_t)seg + 1;
-        }
-        scene->rounds = (uint32_t)n_seg;
-    } else if (rp.total_items > 0) {
-        HIP_TRY(wf_launch_init(wf, (uint32_t)live_total, stream));
-        HIP_TRY(wf_launch_gen(compact, sc, cam, rp, wf, flat_blocks, stream));  // initial fill; later samples start in hit/miss
-        pl.h_live[0] = pl.h_live[1] = (uint32_t)live_total;
-        // Rounds are enqueued in batches; the live-slot count of batch b is read back while batch b+1 is
-        // already queued, so the GPU never waits for the host.  Rounds behind the frame's last one find
-        // live_slots == 0 and return at once; batches shrink from 16 rounds to 4 once fewer than an eighth of
-        // the slots have work, so that at most 7 such rounds are queued after the end.
-        constexpr uint32_t MAX_TIMED = 8192;
-        uint32_t it = 0;
-        uint32_t batch = 16;
-        for (uint32_t b = 0;; b++) {
-            for (uint32_t k = 0; k < batch; k++, it++) {
-                const bool timed = it < MAX_TIMED;
-                // four events per round: before the traversal kernel, after it, after the hit kernel, after the miss kernel
-                if (timed) {
-                    const int st = round_events(4 * (size_t)(it + 1));
-                    if (st != RAYRS_OK) return st;
-                    HIP_TRY(hipEventRecord(pl.ev_round[4 * it], stream));
-                }
-                HIP_TRY(wf_launch_trav(compact, count, sc, rp, wf, trav_blocks, stream));
-                if (timed) HIP_TRY(hipEventRecord(pl.ev_round[4 * it + 1], stream));
-                HIP_TRY(wf_launch_hit(compact, eager_light, sc, cam, rp, wf, flat_blocks, stream));
-                if (timed) HIP_TRY(hipEventRecord(pl.ev_round[4 * it + 2], stream));
-                HIP_TRY(wf_launch_miss(compact, eager_light, sc, cam, rp, wf, flat_blocks, stream));
-                if (timed) {
-                    HIP_TRY(hipEventRecord(pl.ev_round[4 * it + 3], stream));
-                    pl.timed_rounds = it + 1;
-                }
-            }
-            HIP_TRY(hipMemcpyAsync(&pl.h_live[b & 1u], &wf.ctl->live_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipEventRecord(pl.ev_batch[b & 1u], stream));
-            if (b > 0) {
-                HIP_TRY(hipEventSynchronize(pl.ev_batch[(b - 1u) & 1u]));
-                const uint64_t seen = pl.h_live[(b - 1u) & 1u];
-                if (seen == 0u) break;
-                batch = seen * 8u < live_total ? 4u : 16u;
-            }
-            if (it > (1u << 26)) {
-                g_last_error = "path rounds did not terminate";
-                return RAYRS_HIP_ERROR;
-            }
-        }
-        scene->rounds = it;
-    }
+    scene->last_local = p.use_local;
+    if (p.rp.total_items > 0) RAYRS_TRY(p.use_local ? enqueue_local(scene, p, stream) : enqueue_streaming(scene, p, wf, stream));
     HIP_TRY(hipEventRecord(scene->ev[1], stream));
-    if (!use_local) HIP_TRY(launch_resolve(cam, rp, 0u, rp.n_local_tiles, stream));
+    if (!p.use_local) HIP_TRY(launch_resolve(p.cam, p.rp, 0u, p.rp.n_local_tiles, stream));
     HIP_TRY(hipEventRecord(scene->ev[2], stream));
     scene->last_stream = stream;
     scene->pending = true;
-    scene->last_count = count;
     return RAYRS_OK;
     })
 }
@@ -1013,7 +940,7 @@ int rayrs_render_finish(rayrs_scene* scene, rayrs_render_stats* stats) {
     scene->pending = false;
     if (stats) {
         Counters c;
-        HIP_TRY(hipMemcpy(&c, scene->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+        HIP_TRY(scene->d_counters.download(&c, sizeof(c)));
         std::memset(stats, 0, sizeof(*stats));
         stats->rays = c.rays;
         stats->paths = c.paths;
@@ -1036,20 +963,16 @@ int rayrs_render_finish(rayrs_scene* scene, rayrs_render_stats* stats) {
         stats->trace_ms = ms;
         HIP_TRY(hipEventElapsedTime(&ms, scene->ev[0], scene->ev[2]));
         stats->total_ms = ms;
-        const rayrs_scene::Pool& pl = scene->pool;
+        const uint32_t timed_rounds = scene->pool.timed_rounds;
         double t = 0.0, h = 0.0, m = 0.0;
-        for (uint32_t r = 0; r < pl.timed_rounds; r++) {
-            HIP_TRY(hipEventElapsedTime(&ms, pl.ev_round[4 * r], pl.ev_round[4 * r + 1]));
-            t += ms;
-            if (scene->last_local) continue;  // one kernel per segment
-            HIP_TRY(hipEventElapsedTime(&ms, pl.ev_round[4 * r + 1], pl.ev_round[4 * r + 2]));
-            h += ms;
-            HIP_TRY(hipEventElapsedTime(&ms, pl.ev_round[4 * r + 2], pl.ev_round[4 * r + 3]));
-            m += ms;
+        for (uint32_t r = 0; r < timed_rounds; r++) {
+            float k[3];
+            RAYRS_TRY(round_ms(scene, r, k));
+            t += k[0], h += k[1], m += k[2];
         }
         // rounds beyond the event pool (very long renders) are extrapolated from the timed ones
-        if (pl.timed_rounds && scene->rounds > pl.timed_rounds) {
-            const double f = (double)scene->rounds / (double)pl.timed_rounds;
+        if (timed_rounds && scene->rounds > timed_rounds) {
+            const double f = (double)scene->rounds / (double)timed_rounds;
             t *= f, h *= f, m *= f;
         }
         stats->kernel_ms = t;
@@ -1069,276 +992,12 @@ int rayrs_render(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_ren
     HIP_TRY(hipSetDevice(scene->device));
     const size_t elem = params->out_format == RAYRS_OUT_F64 ? 8 : 4;
     const size_t bytes = (size_t)camera->x_pixels * camera->y_pixels * 3 * elem;
-    void* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_out, bytes));
-    // pixels of other ranks' tiles keep the caller's values
-    hipError_t e = hipMemcpy(d_out, out_host, bytes, hipMemcpyHostToDevice);
-    int st = e == hipSuccess ? RAYRS_OK : hip_fail(e, "hipMemcpy(out H2D)");
-    if (st == RAYRS_OK) st = rayrs_render_launch(scene, camera, params, d_out, nullptr);
-    if (st == RAYRS_OK) st = rayrs_render_finish(scene, stats);
-    if (st == RAYRS_OK) {
-        e = hipMemcpy(out_host, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) st = hip_fail(e, "hipMemcpy(out D2H)");
-    }
-    (void)hipFree(d_out);
-    return st;
-}
-
-// ------------------------------------------------------------- self tests
-
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t bytes) {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-        return e == hipSuccess ? RAYRS_OK : hip_fail(e, "hipMalloc");
-    }
-    int upload(const void* src, size_t bytes) {
-        int st = alloc(bytes);
-        if (st != RAYRS_OK) return st;
-        if (!bytes) return RAYRS_OK;
-        hipError_t e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-        return e == hipSuccess ? RAYRS_OK : hip_fail(e, "hipMemcpy H2D");
-    }
-    int download(void* dst, size_t bytes) {
-        if (!bytes) return RAYRS_OK;
-        hipError_t e = hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost);
-        return e == hipSuccess ? RAYRS_OK : hip_fail(e, "hipMemcpy D2H");
-    }
-};
-#define ST_TRY(expr)                  \
-    do {                              \
-        int _s = (expr);              \
-        if (_s != RAYRS_OK) return _s; \
-    } while (0)
-}  // namespace
-
-int rayrs_test_math(int device, int fn, const double* x, const double* y, uint64_t n, double* out) {
-    if (!x || !out) return RAYRS_INVALID_ARG;
-    HIP_TRY(hipSetDevice(device));
-    DevBuf dx, dy, dout;
-    ST_TRY(dx.upload(x, n * 8));
-    if (y) ST_TRY(dy.upload(y, n * 8));
-    ST_TRY(dout.alloc(n * 8));
-    if (n) HIP_TRY(launch_test_math(fn, (const double*)dx.p, y ? (const double*)dy.p : nullptr, n, (double*)dout.p, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    return dout.download(out, n * 8);
-}
-
-int rayrs_test_rng(int device, uint64_t seed, const uint64_t* pixel, const uint64_t* sample, const uint32_t* draw,
-                   uint64_t n, uint64_t* out_bits) {
-    if (!pixel || !sample || !draw || !out_bits) return RAYRS_INVALID_ARG;
-    HIP_TRY(hipSetDevice(device));
-    DevBuf dp, ds, dd, dout;
-    ST_TRY(dp.upload(pixel, n * 8));
-    ST_TRY(ds.upload(sample, n * 8));
-    ST_TRY(dd.upload(draw, n * 4));
-    ST_TRY(dout.alloc(n * 8));
-    if (n)
-        HIP_TRY(launch_test_rng(seed, (const uint64_t*)dp.p, (const uint64_t*)ds.p, (const uint32_t*)dd.p, n,
-                                (uint64_t*)dout.p, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    return dout.download(out_bits, n * 8);
-}
-
-int rayrs_test_intersect(rayrs_scene* scene, const double* o, const double* d, uint64_t n, int exact, double* t,
-                         int64_t* object) {
-    if (!scene || !o || !d || !t || !object) return RAYRS_INVALID_ARG;
-    if (scene->device < 0) return RAYRS_NO_DEVICE;
-    HIP_TRY(hipSetDevice(scene->device));
-    DevBuf dorg, ddir, dt, dprim;
-    ST_TRY(dorg.upload(o, n * 24));
-    ST_TRY(ddir.upload(d, n * 24));
-    ST_TRY(dt.alloc(n * 8));
-    ST_TRY(dprim.alloc(n * 8));
-    const SceneDev sc = make_scene_dev(scene, exact != 0);
-    DevBuf dspill;  // stack entries beyond the LDS part, one strip per thread of the launch
-    const uint64_t threads = (n + 255) / 256 * 256;
-    if (sc.stack_depth > sc.stack_lds) ST_TRY(dspill.alloc((size_t)(sc.stack_depth - sc.stack_lds) * threads * 4));
-    if (n)
-        HIP_TRY(launch_test_intersect(scene->flat.compact, sc, (const double*)dorg.p, (const double*)ddir.p, n,
-                                      (double*)dt.p, (long long*)dprim.p, (uint32_t*)dspill.p, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    ST_TRY(dt.download(t, n * 8));
-    ST_TRY(dprim.download(object, n * 8));
-    for (uint64_t i = 0; i < n; i++)  // DFS slot -> object index in insertion order
-        if (object[i] >= 0) object[i] = (int64_t)scene->flat.prim_object[(size_t)object[i]];
+    DevBuf d_out;
+    HIP_TRY(d_out.upload(out_host, bytes));  // pixels of other ranks' tiles keep the caller's values
+    RAYRS_TRY(rayrs_render_launch(scene, camera, params, d_out.as<>(), nullptr));
+    RAYRS_TRY(rayrs_render_finish(scene, stats));
+    HIP_TRY(d_out.download(out_host, bytes));
     return RAYRS_OK;
-}
-
-int rayrs_test_trace(rayrs_scene* scene, const double* o, const double* d, uint64_t n, int exact, double* t, int64_t* object,
-                     uint64_t* pre_answered) {
-    if (!scene || !o || !d || !t || !object) return RAYRS_INVALID_ARG;
-    if (scene->device < 0) return RAYRS_NO_DEVICE;
-    HIP_TRY(hipSetDevice(scene->device));
-    const bool ex = exact != 0;
-    const SceneDev sc = make_scene_dev(scene, ex);
-    RenderDev rp;
-    std::memset(&rp, 0, sizeof(rp));
-    trav_thresholds(scene, ex, rp);
-    const uint32_t trav_blocks = trav_grid_blocks(scene, ex);
-    // the pool: rayrs_tuning.pool_slots slots if set (the rays then go through it in chunks of that many), whole windows
-    uint64_t np64 = scene->tuning.pool_slots ? scene->tuning.pool_slots : (n < (1u << 20) ? n : (1u << 20));
-    np64 = np64 < 1024u ? 1024u : (np64 + 1023u) & ~1023ull;
-    const uint32_t np = (uint32_t)np64;
-    WfDev wf;
-    std::memset(&wf, 0, sizeof(wf));
-    wf.np = np;
-    wf.trav_threads = trav_blocks * 256u;
-    rp.static_windows = trav_static_windows(scene, np / wf_window_slots(), trav_blocks);
-    DevBuf dslots, dstate, dctl, dspill, dcount, dans, dorg, ddir;
-    ST_TRY(dslots.alloc((size_t)np * sizeof(PathSlot)));
-    ST_TRY(dstate.alloc(np));
-    ST_TRY(dctl.alloc(sizeof(WfCtl)));
-    ST_TRY(dspill.alloc((size_t)(sc.stack_depth - sc.stack_lds) * wf.trav_threads * 4u));
-    ST_TRY(dcount.alloc(sizeof(Counters)));
-    ST_TRY(dans.alloc(sizeof(unsigned long long)));
-    ST_TRY(dorg.alloc((size_t)np * 24));
-    ST_TRY(ddir.alloc((size_t)np * 24));
-    HIP_TRY(hipMemset(dcount.p, 0, sizeof(Counters)));
-    HIP_TRY(hipMemset(dans.p, 0, sizeof(unsigned long long)));
-    wf.slots = (PathSlot*)dslots.p;
-    wf.state = (uint8_t*)dstate.p;
-    wf.ctl = (WfCtl*)dctl.p;
-    wf.stack_spill = (uint32_t*)dspill.p;
-    rp.counters = (Counters*)dcount.p;
-    std::vector<uint8_t> state(np);
-    std::vector<PathSlot> slots(np);
-    constexpr uint32_t MAX_ROUNDS = 64;
-    for (uint64_t base = 0; base < n; base += np) {
-        const uint32_t m = (uint32_t)(n - base < np ? n - base : np);
-        HIP_TRY(hipMemcpy(dorg.p, o + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ddir.p, d + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice));
-        HIP_TRY(wf_launch_intake(sc, wf, (const double*)dorg.p, (const double*)ddir.p, m, (unsigned long long*)dans.p, nullptr));
-        // the traversal rounds of a render (abi.cpp rayrs_render_launch): there the hit kernel resets the window cursor
-        uint32_t round = 0;
-        for (;; round++) {
-            WfCtl ctl;
-            std::memset(&ctl, 0, sizeof(ctl));
-            ctl.live_slots = m;
-            HIP_TRY(hipMemcpy(dctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
-            HIP_TRY(wf_launch_trav(scene->flat.compact, false, sc, rp, wf, trav_blocks, nullptr));
-            HIP_TRY(hipDeviceSynchronize());
-            ST_TRY(dstate.download(state.data(), np));
-            bool ready = false;
-            for (uint32_t i = 0; i < m; i++) ready |= (state[i] & 7u) == WF_READY;
-            if (!ready) break;
-            if (round + 1 >= MAX_ROUNDS) {
-                g_last_error = "rayrs_test_trace: slots still READY after the traversal rounds";
-                return RAYRS_HIP_ERROR;
-            }
-        }
-        ST_TRY(dslots.download(slots.data(), (size_t)m * sizeof(PathSlot)));
-        for (uint32_t i = 0; i < m; i++) {
-            if (state[i] == WF_HIT) {
-                if (slots[i].ray.prim >= scene->flat.prim_object.size()) {
-                    g_last_error = "rayrs_test_trace: a HIT slot names no primitive";
-                    return RAYRS_HIP_ERROR;
-                }
-                t[base + i] = slots[i].ray.t;
-                object[base + i] = (int64_t)scene->flat.prim_object[slots[i].ray.prim];  // DFS slot -> insertion order
-            } else if (state[i] == WF_MISS) {
-                t[base + i] = 0.0;
-                object[base + i] = -1;
-            } else {
-                g_last_error = "rayrs_test_trace: a slot left neither HIT nor MISS";
-                return RAYRS_HIP_ERROR;
-            }
-        }
-    }
-    unsigned long long answered = 0;
-    ST_TRY(dans.download(&answered, sizeof(answered)));
-    if (pre_answered) *pre_answered = answered;
-    return RAYRS_OK;
-}
-
-int rayrs_test_path_trace(rayrs_scene* scene, const rayrs_camera* camera, uint64_t seed, uint32_t max_bounces,
-                          const uint32_t* pixel, const uint32_t* sample, uint64_t n, int exact, uint32_t cap,
-                          uint32_t* n_queries, int64_t* object, double* t, double* throughput, uint32_t* draw, double* rgb) {
-    if (!scene || !camera || !pixel || !sample || !n_queries || !object || !t || !throughput || !draw || !rgb || cap == 0)
-        return RAYRS_INVALID_ARG;
-    if (scene->device < 0) return RAYRS_NO_DEVICE;
-    for (uint64_t i = 0; i < n; i++)
-        if ((pixel[i] >> 16) >= camera->y_pixels || (pixel[i] & 0xffffu) >= camera->x_pixels) return RAYRS_INVALID_ARG;
-    HIP_TRY(hipSetDevice(scene->device));
-    DevBuf dpix, dsam, dn, dprim, dt, dthr, ddraw, drgb, dspill;
-    ST_TRY(dpix.upload(pixel, n * 4));
-    ST_TRY(dsam.upload(sample, n * 4));
-    ST_TRY(dn.alloc(n * 4));
-    ST_TRY(dprim.alloc(n * cap * 4));
-    ST_TRY(dt.alloc(n * cap * 8));
-    ST_TRY(dthr.alloc(n * cap * 24));
-    ST_TRY(ddraw.alloc(n * cap * 4));
-    ST_TRY(drgb.alloc(n * 24));
-    HIP_TRY(hipMemset(dprim.p, 0xff, n * cap * 4));
-    HIP_TRY(hipMemset(dt.p, 0, n * cap * 8));
-    HIP_TRY(hipMemset(dthr.p, 0, n * cap * 24));
-    HIP_TRY(hipMemset(ddraw.p, 0, n * cap * 4));
-    const SceneDev sc = make_scene_dev(scene, exact != 0);
-    const CameraDev cam = make_camera_dev(camera);
-    const uint64_t threads = (n + 255) / 256 * 256;
-    if (sc.stack_depth > sc.stack_lds) ST_TRY(dspill.alloc((size_t)(sc.stack_depth - sc.stack_lds) * threads * 4));
-    if (n)
-        HIP_TRY(launch_test_path_trace(scene->flat.compact, sc, cam, seed, max_bounces, (const uint32_t*)dpix.p,
-                                       (const uint32_t*)dsam.p, n, cap, (uint32_t*)dn.p, (uint32_t*)dprim.p, (double*)dt.p,
-                                       (double*)dthr.p, (uint32_t*)ddraw.p, (double*)drgb.p, (uint32_t*)dspill.p, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    std::vector<uint32_t> prim(n * cap);
-    ST_TRY(dn.download(n_queries, n * 4));
-    ST_TRY(dprim.download(prim.data(), n * cap * 4));
-    ST_TRY(dt.download(t, n * cap * 8));
-    ST_TRY(dthr.download(throughput, n * cap * 24));
-    ST_TRY(ddraw.download(draw, n * cap * 4));
-    ST_TRY(drgb.download(rgb, n * 24));
-    for (uint64_t k = 0; k < n * cap; k++)  // DFS slot -> object index in insertion order
-        object[k] = prim[k] == 0xffffffffu ? -1 : (int64_t)scene->flat.prim_object[prim[k]];
-    return RAYRS_OK;
-}
-
-int rayrs_test_material(int device, const rayrs_material* mat, const double* normal, const double* view,
-                        const uint64_t* key, uint64_t n, int32_t* scattered, double* color, double* dir,
-                        uint32_t* draws) {
-    RAYRS_GUARDED({
-    if (!mat || !normal || !view || !key || !scattered || !color || !dir || !draws) return RAYRS_INVALID_ARG;
-    ObjectList tmp;
-    const int surf = tmp.add_surface(mat, nullptr);
-    if (surf < 0) return surf;
-    HIP_TRY(hipSetDevice(device));
-    DevBuf ds, dn, dv, dk, dsc, dc, dd, ddr;
-    ST_TRY(ds.upload(&tmp.surfaces[0], sizeof(SurfaceDev)));
-    ST_TRY(dn.upload(normal, n * 24));
-    ST_TRY(dv.upload(view, n * 24));
-    ST_TRY(dk.upload(key, n * 8));
-    ST_TRY(dsc.alloc(n * 4));
-    ST_TRY(dc.alloc(n * 24));
-    ST_TRY(dd.alloc(n * 24));
-    ST_TRY(ddr.alloc(n * 4));
-    if (n)
-        HIP_TRY(launch_test_material((const SurfaceDev*)ds.p, (const double*)dn.p, (const double*)dv.p,
-                                     (const uint64_t*)dk.p, n, (int32_t*)dsc.p, (double*)dc.p, (double*)dd.p,
-                                     (uint32_t*)ddr.p, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    ST_TRY(dsc.download(scattered, n * 4));
-    ST_TRY(dc.download(color, n * 24));
-    ST_TRY(dd.download(dir, n * 24));
-    return ddr.download(draws, n * 4);
-    })
-}
-
-int rayrs_test_background(rayrs_scene* scene, const double* dir, uint64_t n, double* rgb) {
-    if (!scene || !dir || !rgb) return RAYRS_INVALID_ARG;
-    if (scene->device < 0) return RAYRS_NO_DEVICE;
-    HIP_TRY(hipSetDevice(scene->device));
-    DevBuf dd, dout;
-    ST_TRY(dd.upload(dir, n * 24));
-    ST_TRY(dout.alloc(n * 24));
-    const SceneDev sc = make_scene_dev(scene, false);
-    if (n) HIP_TRY(launch_test_background(sc, (const double*)dd.p, n, (double*)dout.p, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    return dout.download(rgb, n * 24);
 }
 
 }  // extern "C"

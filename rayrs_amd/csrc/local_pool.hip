@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_path.h"
+#include "launch_dispatch.h"
 #include "local_pool.h"
 #include "wavefront.h"
 
@@ -498,38 +499,31 @@ uint32_t lp_lds_bytes(uint32_t n_prims, uint32_t n_surfaces) { return lp_block_b
 
 hipError_t lp_configure() {
     const int most = (int)lp_block_bytes(LP_MAX_PRIMS, LP_MAX_PRIMS);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_path_kernel<true, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_path_kernel<true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_path_kernel<false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&lp_path_kernel<false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, most);
+    const void* const instances[] = {
+        reinterpret_cast<const void*>(&lp_path_kernel<true, false>), reinterpret_cast<const void*>(&lp_path_kernel<true, true>),
+        reinterpret_cast<const void*>(&lp_path_kernel<false, false>), reinterpret_cast<const void*>(&lp_path_kernel<false, true>)};
+    for (const void* k : instances) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // workgroups of the kernel a CU holds with this scene's LDS footprint (at most LP_WPS, its launch bound)
 hipError_t lp_occupancy(bool compact, uint32_t n_prims, uint32_t n_surfaces, int* blocks_per_cu) {
     const uint32_t lds = lp_block_bytes(n_prims < LP_MAX_PRIMS ? n_prims : LP_MAX_PRIMS, n_surfaces < LP_MAX_PRIMS ? n_surfaces : LP_MAX_PRIMS);
-    if (compact) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lp_path_kernel<true, false>, 256, lds);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lp_path_kernel<false, false>, 256, lds);
+    return with_bools([&](auto C) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lp_path_kernel<C(), false>, 256, lds);
+    }, compact);
 }
 
 hipError_t lp_launch(bool compact, bool count, const SceneDev& sc, const LocalScene& ls, const CameraDev& cam,
                      const RenderDev& rp, const LocalDev& lp, uint32_t blocks, hipStream_t stream) {
     const uint32_t n_surf = sc.n_surfaces < LP_MAX_PRIMS ? sc.n_surfaces : LP_MAX_PRIMS;
     const uint32_t lds = lp_block_bytes(ls.n_prims < LP_MAX_PRIMS ? ls.n_prims : LP_MAX_PRIMS, n_surf);
-    if (compact && count)
-        hipLaunchKernelGGL((lp_path_kernel<true, true>), dim3(blocks), dim3(256), lds, stream, sc, ls, cam, rp, lp);
-    else if (compact)
-        hipLaunchKernelGGL((lp_path_kernel<true, false>), dim3(blocks), dim3(256), lds, stream, sc, ls, cam, rp, lp);
-    else if (count)
-        hipLaunchKernelGGL((lp_path_kernel<false, true>), dim3(blocks), dim3(256), lds, stream, sc, ls, cam, rp, lp);
-    else
-        hipLaunchKernelGGL((lp_path_kernel<false, false>), dim3(blocks), dim3(256), lds, stream, sc, ls, cam, rp, lp);
+    with_bools([&](auto C, auto N) {
+        hipLaunchKernelGGL((lp_path_kernel<C(), N()>), dim3(blocks), dim3(256), lds, stream, sc, ls, cam, rp, lp);
+    }, compact, count);
     return hipGetLastError();
 }
 

@@ -153,8 +153,6 @@ int rccl_reduce_to_first(const std::vector<int>& devs, const std::vector<void*>&
 
 struct Rank {
     rayrs_scene* scene = nullptr;
-    void* d_out = nullptr;
-    hipStream_t stream = nullptr;
     rayrs_render_stats stats = {};
     int status = RAYRS_OK;
     std::string error;
@@ -169,17 +167,11 @@ void render_rank(Rank& r, const rayrs_camera* camera, rayrs_render_params params
     // would otherwise spend as long creating and freeing them as rendering
     rayrs_scene* s = r.scene;
     hipError_t e = hipSetDevice(s->device);
-    if (e == hipSuccess && !s->multi_stream) e = hipStreamCreateWithFlags(&s->multi_stream, hipStreamNonBlocking);
-    if (e == hipSuccess && s->multi_out_bytes < bytes) {
-        if (s->multi_out) (void)hipFree(s->multi_out);
-        s->multi_out = nullptr, s->multi_out_bytes = 0;
-        e = hipMalloc(&s->multi_out, bytes);
-        if (e == hipSuccess) s->multi_out_bytes = bytes;
-    }
-    r.stream = s->multi_stream, r.d_out = s->multi_out;
-    if (e == hipSuccess) e = hipMemsetAsync(r.d_out, 0, bytes, r.stream);  // the tiles of the other ranks stay exact zeros
+    if (e == hipSuccess && !s->multi_stream) e = s->multi_stream.create(hipStreamNonBlocking);
+    if (e == hipSuccess) e = s->multi_out.reserve(bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(s->multi_out.as<>(), 0, bytes, s->multi_stream);  // the tiles of the other ranks stay exact zeros
     if (e != hipSuccess) return fail(hip_fail(e, "rayrs_render_multi: device setup"));
-    int st = rayrs_render_launch(r.scene, camera, &params, r.d_out, r.stream);
+    int st = rayrs_render_launch(s, camera, &params, s->multi_out.as<>(), s->multi_stream);
     if (st == RAYRS_OK) st = rayrs_render_finish(r.scene, &r.stats);
     if (st != RAYRS_OK) fail(st);
 }
@@ -235,11 +227,11 @@ extern "C" int rayrs_render_multi(rayrs_scene* const* scenes, uint32_t n, const 
             for (uint32_t i = 0; i < n; i++) rank_device[i] = ranks[i].scene->device;
             const ReducePlan plan = plan_reduce(rank_device);
             devs = plan.devs;
-            for (const uint32_t l : plan.leader) bufs.push_back(ranks[l].d_out), streams.push_back(ranks[l].stream);
+            for (const uint32_t l : plan.leader) bufs.push_back(ranks[l].scene->multi_out.as<>()), streams.push_back(ranks[l].scene->multi_stream);
             for (const auto& [k, i] : plan.local) {
                 if (st != RAYRS_OK) break;
                 hipError_t e = hipSetDevice(devs[k]);
-                if (e == hipSuccess) e = launch_accumulate(bufs[k], ranks[i].d_out, count, f64, streams[k]);
+                if (e == hipSuccess) e = launch_accumulate(bufs[k], ranks[i].scene->multi_out.as<>(), count, f64, streams[k]);
                 if (e == hipSuccess) e = hipStreamSynchronize(streams[k]);
                 if (e != hipSuccess) st = hip_fail(e, "rayrs_render_multi: same-device sum");
             }

@@ -90,7 +90,12 @@ hipError_t wf_launch_gen(bool compact, const SceneDev& sc, const CameraDev& cam,
                          uint32_t blocks, hipStream_t stream);
 hipError_t wf_launch_trav(bool compact, bool count, const SceneDev& sc, const RenderDev& rp, const WfDev& wf,
                           uint32_t blocks, hipStream_t stream);
-hipError_t wf_trav_occupancy(bool compact, uint32_t stack_lds, uint32_t leafq, uint32_t hot_records, int* blocks_per_cu);
+// The traversal workgroup's dynamic LDS for a tree's settings; how many such workgroups a CU holds; and the kernel's
+// dynamic-LDS limit on the current device, which the scenes of a process share and which is therefore only ever raised:
+// at every launch it is at least what the launch asks for.
+uint32_t wf_trav_lds_bytes(bool compact, uint32_t stack_lds, uint32_t leafq, uint32_t hot_records);
+hipError_t wf_trav_occupancy(bool compact, uint32_t lds, int* blocks_per_cu);
+hipError_t wf_trav_raise_lds(bool compact, uint32_t lds);
 // eager_light: request the side array's entry together with the slot (scenes in which a surface emits)
 hipError_t wf_launch_hit(bool compact, bool eager_light, const SceneDev& sc, const CameraDev& cam, const RenderDev& rp, const WfDev& wf,
                          uint32_t blocks, hipStream_t stream);

@@ -25,9 +25,13 @@
 // hand-off is needed.
 #include <hip/hip_runtime.h>
 
+#include <map>
+#include <mutex>
+
 #include "device_path.h"
 #include "kernels.h"
 #include "lab_ticks.h"
+#include "launch_dispatch.h"
 #include "wavefront.h"
 
 namespace rayrs {
@@ -1145,7 +1149,14 @@ hipError_t wf_launch_intake(const SceneDev& sc, const WfDev& wf, const double* o
     return hipGetLastError();
 }
 
-static inline uint32_t trav_lds_bytes(bool compact, uint32_t stack_lds, uint32_t leafq, uint32_t hot_records) {
+// karg reads the kernel-argument segment at the KA_* offsets: right for a kernel whose leading parameters are these four
+template <class F> struct ka_leading : std::false_type {};
+template <class... Tail> struct ka_leading<void(SceneDev, CameraDev, RenderDev, WfDev, Tail...)> : std::true_type {};
+static_assert(ka_leading<decltype(wf_gen_kernel<true>)>::value && ka_leading<decltype(wf_hit_kernel<true, true>)>::value &&
+                  ka_leading<decltype(wf_miss_kernel<true, true>)>::value && ka_leading<decltype(wf_intake_kernel)>::value,
+              "a kernel that calls karg() takes (SceneDev, CameraDev, RenderDev, WfDev) first");
+
+uint32_t wf_trav_lds_bytes(bool compact, uint32_t stack_lds, uint32_t leafq, uint32_t hot_records) {
     return 4u * 64u * (stack_lds + 1u + leafq) * 4u + 4u * WINDOW * 2u + hot_records * (compact ? 144u : 272u);
 }
 
@@ -1158,78 +1169,66 @@ hipError_t wf_launch_init(const WfDev& wf, uint32_t live, hipStream_t stream) {
 
 hipError_t wf_launch_gen(bool compact, const SceneDev& sc, const CameraDev& cam, const RenderDev& rp, const WfDev& wf,
                          uint32_t blocks, hipStream_t stream) {
-    if (compact) hipLaunchKernelGGL(wf_gen_kernel<true>, dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
-    else hipLaunchKernelGGL(wf_gen_kernel<false>, dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
+    with_bools([&](auto C) {
+        hipLaunchKernelGGL(wf_gen_kernel<C()>, dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
+    }, compact);
     return hipGetLastError();
 }
 
-template <bool COMPACT, bool COUNT>
-static hipError_t launch_trav_t(const SceneDev& sc, const RenderDev& rp, const WfDev& wf, uint32_t blocks,
-                                hipStream_t stream) {
-    const uint32_t lds = trav_lds_bytes(COMPACT, sc.stack_lds, sc.leafq, sc.hot_records);
-    if (sc.exact && sc.hot) hipLaunchKernelGGL((wf_trav_kernel<COMPACT, COUNT, true, true>), dim3(blocks), dim3(256), lds, stream, sc, rp, wf);  // PRE
-    else if (sc.exact) hipLaunchKernelGGL((wf_trav_kernel<COMPACT, COUNT, true, false>), dim3(blocks), dim3(256), lds, stream, sc, rp, wf);
-    else hipLaunchKernelGGL((wf_trav_kernel<COMPACT, COUNT, false, false>), dim3(blocks), dim3(256), lds, stream, sc, rp, wf);
-    return hipGetLastError();
-}
-
+// The traversal kernel's instances: <COMPACT, COUNT> x the fast walk <false, false>, the default walk <true, false> and
+// the default walk on pre-tested rays <true, true> (a scene with a hot group).
 hipError_t wf_launch_trav(bool compact, bool count, const SceneDev& sc, const RenderDev& rp, const WfDev& wf,
                           uint32_t blocks, hipStream_t stream) {
-    if (compact)
-        return count ? launch_trav_t<true, true>(sc, rp, wf, blocks, stream)
-                     : launch_trav_t<true, false>(sc, rp, wf, blocks, stream);
-    return count ? launch_trav_t<false, true>(sc, rp, wf, blocks, stream)
-                 : launch_trav_t<false, false>(sc, rp, wf, blocks, stream);
+    const uint32_t lds = wf_trav_lds_bytes(compact, sc.stack_lds, sc.leafq, sc.hot_records);
+    with_bools([&](auto C, auto N, auto X, auto P) {
+        hipLaunchKernelGGL((wf_trav_kernel<C(), N(), X(), X() && P()>), dim3(blocks), dim3(256), lds, stream, sc, rp, wf);
+    }, compact, count, sc.exact != 0u, sc.hot != nullptr);
+    return hipGetLastError();
 }
 
-template <bool COMPACT, bool COUNT>
-static hipError_t trav_set_lds(uint32_t lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wf_trav_kernel<COMPACT, COUNT, false, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wf_trav_kernel<COMPACT, COUNT, true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&wf_trav_kernel<COMPACT, COUNT, true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+hipError_t wf_trav_occupancy(bool compact, uint32_t lds, int* blocks_per_cu) {
+    return with_bools([&](auto C) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, wf_trav_kernel<C(), false, false, false>, 256, lds);
+    }, compact);
 }
 
-hipError_t wf_trav_occupancy(bool compact, uint32_t stack_lds, uint32_t leafq, uint32_t hot_records, int* blocks_per_cu) {
-    hipError_t e = hipSuccess;
-    const uint32_t lds = trav_lds_bytes(compact, stack_lds, leafq, hot_records);
-    if (compact) {
-        if ((e = trav_set_lds<true, false>(lds)) != hipSuccess) return e;
-        if ((e = trav_set_lds<true, true>(lds)) != hipSuccess) return e;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, wf_trav_kernel<true, false, false, false>, 256, lds);
-    }
-    if ((e = trav_set_lds<false, false>(lds)) != hipSuccess) return e;
-    if ((e = trav_set_lds<false, true>(lds)) != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, wf_trav_kernel<false, false, false, false>, 256, lds);
+hipError_t wf_trav_raise_lds(bool compact, uint32_t lds) {
+    static std::mutex mutex;
+    static std::map<std::pair<int, bool>, uint32_t> raised;  // (device, compact): what the instances' limit there was last set to
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(mutex);
+    uint32_t& set = raised[{device, compact}];
+    if (lds <= set) return hipSuccess;
+    e = with_bools([&](auto C) {
+        const void* const instances[] = {
+            reinterpret_cast<const void*>(&wf_trav_kernel<C(), false, false, false>), reinterpret_cast<const void*>(&wf_trav_kernel<C(), true, false, false>),
+            reinterpret_cast<const void*>(&wf_trav_kernel<C(), false, true, false>), reinterpret_cast<const void*>(&wf_trav_kernel<C(), true, true, false>),
+            reinterpret_cast<const void*>(&wf_trav_kernel<C(), false, true, true>), reinterpret_cast<const void*>(&wf_trav_kernel<C(), true, true, true>)};
+        for (const void* k : instances) {
+            const hipError_t ek = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (ek != hipSuccess) return ek;
+        }
+        return hipSuccess;
+    }, compact);
+    if (e == hipSuccess) set = lds;
+    return e;
 }
 
 hipError_t wf_launch_hit(bool compact, bool eager_light, const SceneDev& sc, const CameraDev& cam, const RenderDev& rp,
                          const WfDev& wf, uint32_t blocks, hipStream_t stream) {
-    if (compact && eager_light)
-        hipLaunchKernelGGL((wf_hit_kernel<true, true>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
-    else if (compact)
-        hipLaunchKernelGGL((wf_hit_kernel<true, false>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
-    else if (eager_light)
-        hipLaunchKernelGGL((wf_hit_kernel<false, true>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
-    else
-        hipLaunchKernelGGL((wf_hit_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
+    with_bools([&](auto C, auto E) {
+        hipLaunchKernelGGL((wf_hit_kernel<C(), E()>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
+    }, compact, eager_light);
     return hipGetLastError();
 }
 
 hipError_t wf_launch_miss(bool compact, bool eager_light, const SceneDev& sc, const CameraDev& cam, const RenderDev& rp,
                           const WfDev& wf, uint32_t blocks, hipStream_t stream) {
-    if (compact && eager_light)
-        hipLaunchKernelGGL((wf_miss_kernel<true, true>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
-    else if (compact)
-        hipLaunchKernelGGL((wf_miss_kernel<true, false>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
-    else if (eager_light)
-        hipLaunchKernelGGL((wf_miss_kernel<false, true>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
-    else
-        hipLaunchKernelGGL((wf_miss_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
+    with_bools([&](auto C, auto E) {
+        hipLaunchKernelGGL((wf_miss_kernel<C(), E()>), dim3(blocks), dim3(256), 0, stream, sc, cam, rp, wf);
+    }, compact, eager_light);
     return hipGetLastError();
 }
 
