@@ -382,14 +382,95 @@ typedef struct {
 /* Applies to the renders launched on this scene afterwards.  Waits for a render in flight. */
 int rayrs_scene_set_tuning(rayrs_scene* scene, const rayrs_tuning* tuning);
 
+/* ---- progressive film: the same block loop in passes.  A film is a device-resident accumulation buffer bound to one
+ * scene, one camera and one set of sampling settings, to which samples are added pass by pass: look at a frame while it
+ * converges, add samples to a frame that is still noisy without paying for the first ones again, stop when the noise
+ * estimate says so, save a half-rendered frame and go on in another process.
+ *
+ * THE CONTRACT.  A sample's random numbers depend on (seed, pixel, sample index) only, and a pixel is the sum of its
+ * per-chunk sums added in chunk order, the first one assigned.  So after passes n_1 ... n_k, N = n_1 + ... + n_k,
+ * rayrs_film_read returns, bit for bit in both output formats, the frame rayrs_render returns for spp = N,
+ * sample_chunk = c and the same seed, max_bounces, tile share and walk -- for every partition of N into passes that the
+ * rules below allow, and across a rayrs_film_state_get / new film / rayrs_film_state_set in between.  The passes' rays
+ * and paths add up to that frame's, and nan_pixels / neg_pixels of the status are that frame's.
+ *   (rayrs_render with sample_chunk = 0 is the reference's ONE sequential sum per pixel, which no film reproduces in
+ *   pieces: a film's frame is the sample_chunk = c frame.)
+ *
+ * RULES.
+ *  - A film starts empty (N = 0).  c = sample_chunk is fixed for its life.  While the film is open N is a multiple of
+ *    c.  A pass with n % c != 0 ends in a short chunk and CLOSES the film (a short chunk can only be the last chunk of
+ *    the equivalent one-shot frame); n = 0, or any pass on a closed film, is RAYRS_INVALID_ARG and changes nothing.
+ *  - N + n < 2^30 (a path's sample cursor has 30 bits: the limit of rayrs_render_params.spp), and a pass obeys the
+ *    limits of a render of n samples (RAYRS_UNSUPPORTED: 2^32 (pixel, chunk) items, max_bounces > 8000, an image side
+ *    > 65535).
+ *  - A film holds a reference on nothing it does not own.  Destroying the scene before its films is the caller's
+ *    error, as destroying it under a render in flight is.  A pass uses the scene's path pool, item sums and counters:
+ *    one pass or one plain render in flight per scene (a pass waits for a rayrs_render_launch still in flight on the
+ *    scene, as the next launch would); the calls on one scene and its films come from one thread at a time.
+ *  - rayrs_render_multi does not take films.  A film with tile_rank / tile_ranks renders its share as rayrs_render
+ *    does, which is what a caller with one process per GPU needs; pixels outside the share read as +0.
+ *
+ * NOISE.  A BATCH-MEANS estimate on c-sample batches -- the statistic the chunk sums support at no cost in the shading
+ * kernels -- NOT a per-sample variance.  Per pixel, over the M full chunks so far (chunks of exactly c samples; M is
+ * the same for every pixel), with y_k = (c_k.x + c_k.y) + c_k.z the channel sum of chunk sum k, the film keeps
+ *     S1 = y_0 + y_1 + ...        S2 = y_0*y_0 + y_1*y_1 + ...
+ * both accumulated in chunk order starting by assignment, unfused.  A pixel is CONVERGED AT tau iff
+ *     M >= 2  and  M*S2 - S1*S1 <= ((tau*tau) * (S1*S1)) * (M-1)
+ * evaluated in f64 in exactly this order, M converted to f64: the standard error of the mean of the chunk means,
+ * estimated from their sample variance, is at most tau times the mean.  No square root and no division, so the count
+ * is exactly reproducible.  A pixel whose S1 or S2 is not finite counts in `nonfinite` and not in `unconverged`;
+ * `unconverged` = the pixels of the film's share that are neither converged nor non-finite.  With M < 2 every finite
+ * pixel is unconverged. */
+typedef struct rayrs_film rayrs_film;
+
+typedef struct {            /* zero-initialise */
+    uint32_t sample_chunk;  /* c >= 1, fixed for the film's life; 0 = 4 */
+    uint32_t max_bounces;   /* main.rs:77 passes 50 */
+    uint64_t seed;
+    uint32_t tile_rank, tile_ranks; /* as rayrs_render_params; 0, 0 = 0, 1 */
+    uint32_t fast_traversal;        /* as rayrs_render_params */
+    uint32_t pad;
+} rayrs_film_params;
+
+typedef struct {
+    uint64_t samples;       /* N: samples per pixel accumulated so far */
+    uint64_t full_chunks;   /* M: chunks of exactly c samples among them */
+    uint64_t rays, paths;   /* summed over all passes */
+    uint64_t nan_pixels, neg_pixels; /* of the running sums as they stand (main.rs:81-87) */
+    uint64_t unconverged, nonfinite; /* NOISE above, for the tau of the call */
+    uint32_t closed;        /* 1 = the last pass ended in a short chunk: no further pass is accepted */
+    uint32_t pad;
+} rayrs_film_status;
+
+/* RAYRS_NO_DEVICE on a host-only scene.  The film's footprint on the device: 40 bytes per pixel of the frame's 8x8 tiles. */
+int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, rayrs_film** out);
+void rayrs_film_destroy(rayrs_film* film);
+/* Adds the samples N .. N+n-1 to every pixel of the film's share.  Synchronous.  pass_stats (may be NULL): as
+ * rayrs_render's, for this pass alone (its nan_pixels / neg_pixels are 0: they are the status's). */
+int rayrs_film_render(rayrs_film* film, uint32_t n, rayrs_render_stats* pass_stats);
+/* The frame as it stands: running sum * (1 / N) as RAYRS_OUT_F32 or RAYRS_OUT_F64 into a HOST buffer of
+ * y_pixels*x_pixels*3 elements.  RAYRS_INVALID_ARG on an empty film. */
+int rayrs_film_read(rayrs_film* film, uint32_t out_format, void* out_host);
+/* tau: finite and >= 0. */
+int rayrs_film_status_get(rayrs_film* film, double tau, rayrs_film_status* out);
+/* Checkpoint: an opaque, versioned byte image of the film -- sums, statistics, counters and the settings it was created
+ * with.  rayrs_film_state_set accepts only an image of this library's image version whose recorded image size, c, seed,
+ * max_bounces, tile share and walk equal the film's, and whose length is exactly rayrs_film_state_bytes; otherwise
+ * RAYRS_INVALID_ARG and the film is unchanged.  The scene and the camera themselves are NOT recorded: continuing on
+ * another scene or view is the caller's error. */
+uint64_t rayrs_film_state_bytes(const rayrs_film* film);
+int rayrs_film_state_get(rayrs_film* film, void* out_host, uint64_t cap);
+int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
- * rayrs_render_stats.hot_*, rayrs_scene_export_hot_tree, rayrs_obj_load_spheres; the layout table below begins with this
+ * rayrs_render_stats.hot_*, rayrs_scene_export_hot_tree, rayrs_obj_load_spheres.  7: the progressive film (rayrs_film_*, rayrs_film_params,
+ * rayrs_film_status; no existing struct changed).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */
-#define RAYRS_ABI_VERSION 6
+#define RAYRS_ABI_VERSION 7
 uint32_t rayrs_abi_version(void);
 
 /* ---- layout of the structs above as THIS library was compiled, for bindings in other languages
@@ -397,7 +478,7 @@ uint32_t rayrs_abi_version(void);
  * #[repr(C)] structs carry the same numbers).  Writes up to `cap` words to `out` and returns the
  * number of words the full table has: first RAYRS_ABI_VERSION, then for each struct, in the order rayrs_material,
  * rayrs_emission, rayrs_camera, rayrs_scene_info_t, rayrs_render_params, rayrs_render_stats,
- * rayrs_tuning: sizeof, number of fields, then offsetof of every field in declaration order. */
+ * rayrs_tuning, rayrs_film_params, rayrs_film_status: sizeof, number of fields, then offsetof of every field in declaration order. */
 uint32_t rayrs_abi_layout(uint32_t* out, uint32_t cap);
 
 /* ---- file formats either side of the path (host only) ---- */

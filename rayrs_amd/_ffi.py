@@ -22,6 +22,8 @@ SYMBOLS = [
     "rayrs_scene_export_wide", "rayrs_scene_export_gate_tree", "rayrs_scene_export_hot_tree", "rayrs_scene_clone_to_device", "rayrs_scene_device", "rayrs_scene_set_tuning",
     "rayrs_camera_new",
     "rayrs_frame_sample_chunk", "rayrs_render", "rayrs_render_launch", "rayrs_render_finish", "rayrs_render_multi",
+    "rayrs_film_create", "rayrs_film_destroy", "rayrs_film_render", "rayrs_film_read", "rayrs_film_status_get",
+    "rayrs_film_state_bytes", "rayrs_film_state_get", "rayrs_film_state_set",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -92,6 +94,20 @@ class Tuning(C.Structure):
     _fields_ = [("pool_slots", C.c_uint32), ("local_pool", C.c_uint32)]
 
 
+class FilmParams(C.Structure):
+    _fields_ = [("sample_chunk", C.c_uint32), ("max_bounces", C.c_uint32), ("seed", C.c_uint64),
+                ("tile_rank", C.c_uint32), ("tile_ranks", C.c_uint32), ("fast_traversal", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class FilmStatus(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("full_chunks", C.c_uint64), ("rays", C.c_uint64), ("paths", C.c_uint64),
+                ("nan_pixels", C.c_uint64), ("neg_pixels", C.c_uint64), ("unconverged", C.c_uint64),
+                ("nonfinite", C.c_uint64), ("closed", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
 class LabTuning(C.Structure):
     """rayrs_amd/csrc/rayrs_lab.h: the kernels' development knobs -- tests/ and scripts/ubench/ only, not part of the
     boundary (include/rayrs_hip.h)."""
@@ -102,10 +118,10 @@ class LabTuning(C.Structure):
 
 
 # RAYRS_ABI_VERSION these mirrors were written against: lib() refuses a library of another version
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # the order rayrs_abi_layout() reports the public structs in
-ABI_STRUCTS = [MaterialDesc, EmissionDesc, CameraDesc, SceneInfo, RenderParams, RenderStats, Tuning]
+ABI_STRUCTS = [MaterialDesc, EmissionDesc, CameraDesc, SceneInfo, RenderParams, RenderStats, Tuning, FilmParams, FilmStatus]
 
 _lib = None
 
@@ -172,6 +188,16 @@ def lib():
     L.rayrs_render.argtypes = [vp, C.POINTER(CameraDesc), C.POINTER(RenderParams), vp, C.POINTER(RenderStats)]
     L.rayrs_render_launch.argtypes = [vp, C.POINTER(CameraDesc), C.POINTER(RenderParams), vp, vp]
     L.rayrs_render_finish.argtypes = [vp, C.POINTER(RenderStats)]
+    L.rayrs_film_create.argtypes = [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), C.POINTER(vp)]
+    L.rayrs_film_destroy.argtypes = [vp]
+    L.rayrs_film_destroy.restype = None
+    L.rayrs_film_render.argtypes = [vp, C.c_uint32, C.POINTER(RenderStats)]
+    L.rayrs_film_read.argtypes = [vp, C.c_uint32, vp]
+    L.rayrs_film_status_get.argtypes = [vp, C.c_double, C.POINTER(FilmStatus)]
+    L.rayrs_film_state_bytes.argtypes = [vp]
+    L.rayrs_film_state_bytes.restype = C.c_uint64
+    L.rayrs_film_state_get.argtypes = [vp, vp, C.c_uint64]
+    L.rayrs_film_state_set.argtypes = [vp, vp, C.c_uint64]
     L.rayrs_test_math.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
     L.rayrs_test_rng.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
     L.rayrs_test_intersect.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp]

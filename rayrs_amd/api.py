@@ -451,3 +451,117 @@ def render_finish(scene: Scene) -> dict:
     st = _ffi.RenderStats()
     _ffi.check(scene._L.rayrs_render_finish(scene._h, C.byref(st)), "rayrs_render_finish")
     return st.as_dict()
+
+
+class Film:
+    """A progressive film (include/rayrs_hip.h rayrs_film_*): samples are added to it pass by pass, and after passes
+    that add up to N samples image() is, bit for bit, render(scene, camera, N, sample_chunk=sample_chunk) with the same
+    seed, bounces, tile share and walk.  The scene must outlive the film."""
+
+    def __init__(self, scene: Scene, camera: Camera, sample_chunk: int = 4, max_bounces: int = 50, seed: int = 0x5EED,
+                 tile_rank: int = 0, tile_ranks: int = 1, fast_traversal: bool = False):
+        self._L, self._h = scene._L, None
+        self.scene, self.camera = scene, camera
+        p = _ffi.FilmParams()
+        p.sample_chunk, p.max_bounces, p.seed = int(sample_chunk), int(max_bounces), int(seed)
+        p.tile_rank, p.tile_ranks, p.fast_traversal = int(tile_rank), int(tile_ranks), 1 if fast_traversal else 0
+        self.sample_chunk = int(sample_chunk) or 4
+        self.tile_rank, self.tile_ranks = int(tile_rank), int(tile_ranks) or 1
+        h = C.c_void_p()
+        _ffi.check(self._L.rayrs_film_create(scene._h, C.byref(camera.desc), C.byref(p), C.byref(h)), "rayrs_film_create")
+        self._h = h
+
+    def render(self, n: int) -> dict:
+        """Adds n samples to every pixel; the pass's counters and times (as render()'s stats).  n that is not a
+        multiple of sample_chunk closes the film: no further pass is accepted."""
+        st = _ffi.RenderStats()
+        _ffi.check(self._L.rayrs_film_render(self._h, int(n), C.byref(st)), "rayrs_film_render")
+        return st.as_dict()
+
+    def image(self, out_f64: bool = False):
+        """The frame as it stands: (y_pixels, x_pixels, 3), f32 or f64."""
+        out = np.zeros((self.camera.y_pixels(), self.camera.x_pixels(), 3), dtype=np.float64 if out_f64 else np.float32)
+        _ffi.check(self._L.rayrs_film_read(self._h, 1 if out_f64 else 0, out.ctypes.data), "rayrs_film_read")
+        return out
+
+    def status(self, tau: float = 0.0) -> dict:
+        """samples, full_chunks, rays, paths, nan_pixels, neg_pixels, closed, and for this tau the batch-means noise
+        estimate's counts unconverged and nonfinite (include/rayrs_hip.h NOISE)."""
+        st = _ffi.FilmStatus()
+        _ffi.check(self._L.rayrs_film_status_get(self._h, float(tau), C.byref(st)), "rayrs_film_status_get")
+        return st.as_dict()
+
+    def pixels(self) -> int:
+        """Pixels of the film's share (what status()["unconverged"] counts among)."""
+        from . import tiles
+        return int(tiles.tile_mask(self.camera.x_pixels(), self.camera.y_pixels(), self.tile_rank, self.tile_ranks).sum())
+
+    def state(self) -> bytes:
+        n = int(self._L.rayrs_film_state_bytes(self._h))
+        buf = np.zeros(n, dtype=np.uint8)
+        _ffi.check(self._L.rayrs_film_state_get(self._h, buf.ctypes.data, n), "rayrs_film_state_get")
+        return buf.tobytes()
+
+    def set_state(self, image: bytes):
+        buf = np.frombuffer(image, dtype=np.uint8)
+        _ffi.check(self._L.rayrs_film_state_set(self._h, buf.ctypes.data, len(buf)), "rayrs_film_state_set")
+
+    def save(self, path):
+        """The film's byte image in a file, nothing else."""
+        with open(path, "wb") as f:
+            f.write(self.state())
+
+    def load(self, path):
+        """Continue from a saved film: refused (RayrsError, the film unchanged) unless the image was made with this
+        film's image size, sample_chunk, seed, max_bounces, tile share and walk."""
+        with open(path, "rb") as f:
+            self.set_state(f.read())
+
+    def close(self):
+        if self._h is not None:
+            self._L.rayrs_film_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def render_until(film, tau: float, max_unconverged_fraction: float = 0.0, pass_samples: int = 16, max_samples: int = 1024,
+                 time_budget_s: Optional[float] = None, on_pass=None):
+    """Adds passes of pass_samples samples (rounded up to a multiple of the film's sample_chunk) until at most
+    max_unconverged_fraction of its pixels are unconverged at tau ("converged"), or the next
+    pass would take the film beyond max_samples ("max_samples"), or time_budget_s seconds have passed ("time_budget").
+    on_pass(film, status) is called after every pass.  Returns (status, reason); the status is film.status(tau) as it
+    stands, with "pixels" added."""
+    import time
+    c = int(film.sample_chunk)
+    step = -(-int(pass_samples) // c) * c
+    if step <= 0:
+        raise ValueError("pass_samples must be positive")
+    pixels = int(film.pixels())
+    t0 = time.monotonic()
+
+    def done(st):
+        return st["samples"] > 0 and st["unconverged"] <= max_unconverged_fraction * pixels
+
+    st = film.status(tau)
+    while True:
+        if done(st):
+            reason = "converged"
+            break
+        if st["closed"] or st["samples"] + step > max_samples:
+            reason = "max_samples"
+            break
+        if time_budget_s is not None and time.monotonic() - t0 >= time_budget_s:
+            reason = "time_budget"
+            break
+        film.render(step)
+        st = film.status(tau)
+        if on_pass is not None:
+            on_pass(film, st)
+    st = dict(st)
+    st["pixels"] = pixels
+    return st, reason

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rayrs_hip.h"
+#include "film.h"
 #include "kernels.h"
 #include "local_pool.h"
 #include "rayrs_lab.h"
@@ -552,6 +553,17 @@ uint32_t rayrs_abi_layout(uint32_t* out, uint32_t cap) {
     RAYRS_FIELD(rayrs_render_stats, hot_prim_tests), RAYRS_FIELD(rayrs_render_stats, hot_tri_divided);
     RAYRS_STRUCT(rayrs_tuning, 2);
     RAYRS_FIELD(rayrs_tuning, pool_slots), RAYRS_FIELD(rayrs_tuning, local_pool);
+    RAYRS_STRUCT(rayrs_film_params, 7);
+    RAYRS_FIELD(rayrs_film_params, sample_chunk), RAYRS_FIELD(rayrs_film_params, max_bounces);
+    RAYRS_FIELD(rayrs_film_params, seed), RAYRS_FIELD(rayrs_film_params, tile_rank);
+    RAYRS_FIELD(rayrs_film_params, tile_ranks), RAYRS_FIELD(rayrs_film_params, fast_traversal);
+    RAYRS_FIELD(rayrs_film_params, pad);
+    RAYRS_STRUCT(rayrs_film_status, 10);
+    RAYRS_FIELD(rayrs_film_status, samples), RAYRS_FIELD(rayrs_film_status, full_chunks);
+    RAYRS_FIELD(rayrs_film_status, rays), RAYRS_FIELD(rayrs_film_status, paths);
+    RAYRS_FIELD(rayrs_film_status, nan_pixels), RAYRS_FIELD(rayrs_film_status, neg_pixels);
+    RAYRS_FIELD(rayrs_film_status, unconverged), RAYRS_FIELD(rayrs_film_status, nonfinite);
+    RAYRS_FIELD(rayrs_film_status, closed), RAYRS_FIELD(rayrs_film_status, pad);
 #undef RAYRS_STRUCT
 #undef RAYRS_FIELD
     for (uint32_t i = 0; i < cap && i < t.size(); i++) out[i] = t[i];
@@ -692,13 +704,18 @@ struct FramePlan {
     uint64_t live_total;
     uint32_t np, trav_blocks, flat_blocks;  // (np 0, and with it flat_blocks and spill_words: not this route)
     size_t spill_words;
+    // a film pass (rayrs_film_render): film_accumulate_kernel takes the resolve kernel's place
+    bool is_film;
+    FilmPassDev film;
 };
 
 // The frame's items: the (pixel, chunk) pairs of this rank's 8x8 tiles (the caller refuses 2^32 of them and more).
-static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, void* out_device) {
+static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
+                                 void* out_device) {
     RenderDev rp;
     std::memset(&rp, 0, sizeof(rp));
     rp.spp = params->spp;
+    rp.sample0 = sample0;
     rp.max_bounces = params->max_bounces;
     rp.seed = params->seed;
     rp.chunk = (params->sample_chunk == 0 || params->sample_chunk >= params->spp) ? params->spp : params->sample_chunk;
@@ -721,10 +738,10 @@ static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* c
     return rp;
 }
 
-static int plan_frame(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, void* out_device,
-                      FramePlan& p) {
+static int plan_frame(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
+                      void* out_device, FramePlan& p) {
     const rayrs_lab_tuning& lab = scene->lab;
-    RenderDev& rp = p.rp = make_render_dev(scene, camera, params, out_device);
+    RenderDev& rp = p.rp = make_render_dev(scene, camera, params, sample0, out_device);
     if (rp.total_items >= (1ull << 32)) return RAYRS_UNSUPPORTED;
     // Item sums: 24 bytes per (pixel, chunk) item, added per pixel in chunk order by the resolve kernel.  The streaming
     // kernels finish items in no particular order, so the array covers the frame.  The local-pool route renders the frame
@@ -825,7 +842,8 @@ static int enqueue_local(rayrs_scene* scene, const FramePlan& p, hipStream_t str
         HIP_TRY(lp_launch(scene->flat.compact, rp.count_work != 0u, p.sc, scene->local, p.cam, rseg, lp, p.local_blocks, stream));
         RAYRS_TRY(round_event(pl, (uint32_t)seg, 1, stream));
         // the segment's tiles, resolved behind its launch (the next segment reuses the item-sum array)
-        HIP_TRY(launch_resolve(p.cam, rseg, (uint32_t)(seg * p.seg_tiles), (uint32_t)(lp.item_count / p.tile_items), stream));
+        const uint32_t seg_lt0 = (uint32_t)(seg * p.seg_tiles), seg_n_lt = (uint32_t)(lp.item_count / p.tile_items);
+        HIP_TRY(p.is_film ? launch_film_accumulate(p.cam, rseg, p.film, seg_lt0, seg_n_lt, stream) : launch_resolve(p.cam, rseg, seg_lt0, seg_n_lt, stream));
         pl.timed_rounds = (uint32_t)seg + 1;
     }
     scene->rounds = (uint32_t)n_seg;
@@ -877,17 +895,20 @@ static int enqueue_streaming(rayrs_scene* scene, const FramePlan& p, const WfDev
     return RAYRS_OK;
 }
 
-int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params,
-                        void* out_device, void* hip_stream) {
+// A frame, or a film's pass: the samples sample0 .. sample0 + params->spp - 1 of every pixel of the share, summed per chunk
+// of that window.  film == nullptr: the chunk sums are resolved into out_device (rayrs_render_launch, sample0 = 0); else
+// they are added to the film's records and out_device is not used.
+extern "C++" int rayrs::render_enqueue(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
+                                       const FilmPassDev* film, void* out_device, void* hip_stream) {
     RAYRS_GUARDED({
-    if (!scene || !camera || !params || !out_device) return RAYRS_INVALID_ARG;
+    if (!scene || !camera || !params || (!out_device && !film)) return RAYRS_INVALID_ARG;
     if (scene->device < 0) return RAYRS_NO_DEVICE;
     if (params->spp == 0 || camera->x_pixels == 0 || camera->y_pixels == 0) return RAYRS_INVALID_ARG;
     if (camera->x_pixels > 65535u || camera->y_pixels > 65535u) return RAYRS_UNSUPPORTED;  // TailSlot::pix is 16 + 16 bits
     // a path's bounce count and RNG draw index travel as 16 bits each (15 + 16 in the local pool); a bounce draws at
     // most four numbers (material.rs:579 + :1009-1011 + lib.rs:539), so 8000 bounces stay below 2^15 and 2^16
     if (params->max_bounces > 8000u) return RAYRS_UNSUPPORTED;
-    if (params->spp > SLOT_SAMPLE_MASK) return RAYRS_UNSUPPORTED;     // a slot's sample cursor has 30 bits
+    if (params->spp > SLOT_SAMPLE_MASK || sample0 > SLOT_SAMPLE_MASK - params->spp) return RAYRS_UNSUPPORTED;  // a slot's sample cursor has 30 bits
     if (params->tile_ranks == 0 || params->tile_rank >= params->tile_ranks) return RAYRS_INVALID_ARG;
     if (params->out_format != RAYRS_OUT_F32 && params->out_format != RAYRS_OUT_F64) return RAYRS_INVALID_ARG;
     if (params->fast_traversal > 1u) return RAYRS_INVALID_ARG;
@@ -899,7 +920,9 @@ int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const ra
     }
 
     FramePlan p;
-    RAYRS_TRY(plan_frame(scene, camera, params, out_device, p));
+    RAYRS_TRY(plan_frame(scene, camera, params, sample0, out_device, p));
+    p.is_film = film != nullptr;
+    p.film = film ? *film : FilmPassDev{nullptr, 0u, 0u};
     scene->last_exact = p.exact;
 
     // ---- what the plan needs of the scene's buffers, which only grow (nothing of the route the frame does not take)
@@ -923,12 +946,18 @@ int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const ra
     scene->last_local = p.use_local;
     if (p.rp.total_items > 0) RAYRS_TRY(p.use_local ? enqueue_local(scene, p, stream) : enqueue_streaming(scene, p, wf, stream));
     HIP_TRY(hipEventRecord(scene->ev[1], stream));
-    if (!p.use_local) HIP_TRY(launch_resolve(p.cam, p.rp, 0u, p.rp.n_local_tiles, stream));
+    if (!p.use_local) HIP_TRY(p.is_film ? launch_film_accumulate(p.cam, p.rp, p.film, 0u, p.rp.n_local_tiles, stream) : launch_resolve(p.cam, p.rp, 0u, p.rp.n_local_tiles, stream));
     HIP_TRY(hipEventRecord(scene->ev[2], stream));
     scene->last_stream = stream;
     scene->pending = true;
     return RAYRS_OK;
     })
+}
+
+int rayrs_render_launch(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params,
+                        void* out_device, void* hip_stream) {
+    if (!out_device) return RAYRS_INVALID_ARG;
+    return render_enqueue(scene, camera, params, 0u, nullptr, out_device, hip_stream);
 }
 
 int rayrs_render_finish(rayrs_scene* scene, rayrs_render_stats* stats) {

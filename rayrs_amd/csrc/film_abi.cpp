@@ -1,0 +1,250 @@
+// film_abi.cpp -- the progressive film of include/rayrs_hip.h (rayrs_film_*): a film's lifetime, a pass as a render of a
+// sample window whose chunk sums go to the film's records (abi.cpp render_enqueue, film.hip), the frame and the status
+// read from the records, and the checkpoint image.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <new>
+
+#include "../../include/rayrs_hip.h"
+#include "film.h"
+#include "scene_internal.hpp"
+
+using namespace rayrs;
+
+namespace {
+// The checkpoint image: this header, then the film's records as they lie on the device (film.h).
+constexpr uint32_t STATE_MAGIC = 0x4d4c4652u;  // "RFLM"
+constexpr uint32_t STATE_VERSION = 1;
+struct StateHeader {
+    uint32_t magic, version;
+    uint32_t x_pixels, y_pixels;
+    uint32_t sample_chunk, max_bounces;
+    uint64_t seed;
+    uint32_t tile_rank, tile_ranks;
+    uint32_t fast_traversal, closed;
+    uint64_t samples, full_chunks, rays, paths;
+    uint64_t record_bytes;
+};
+static_assert(sizeof(StateHeader) == 88, "StateHeader");
+constexpr size_t STAGE_BYTES = 8u << 20;  // pinned staging of state_get / state_set, copied through in pieces
+}  // namespace
+
+struct rayrs_film {
+    rayrs_scene* scene = nullptr;  // not owned
+    rayrs_camera camera = {};
+    rayrs_film_params prm = {};    // as given, defaults filled in
+    uint32_t tiles_x = 0, tiles_y = 0;
+    uint64_t samples = 0, full_chunks = 0, rays = 0, paths = 0;
+    bool closed = false;
+    DevBuf d_rec;     // film.h: 40 bytes per pixel of the frame's tiles
+    DevBuf d_counts;  // one FilmCounts
+    DevBuf d_out;     // the frame rayrs_film_read copies out, grown on demand
+    PinnedBuf h_stage;
+    bool has_stage = false;
+    size_t record_bytes() const { return (size_t)tiles_x * tiles_y * FILM_TILE_DOUBLES * sizeof(double); }
+    StateHeader header() const {
+        StateHeader h;
+        std::memset(&h, 0, sizeof(h));
+        h.magic = STATE_MAGIC, h.version = STATE_VERSION;
+        h.x_pixels = camera.x_pixels, h.y_pixels = camera.y_pixels;
+        h.sample_chunk = prm.sample_chunk, h.max_bounces = prm.max_bounces, h.seed = prm.seed;
+        h.tile_rank = prm.tile_rank, h.tile_ranks = prm.tile_ranks, h.fast_traversal = prm.fast_traversal;
+        h.closed = closed ? 1u : 0u;
+        h.samples = samples, h.full_chunks = full_chunks, h.rays = rays, h.paths = paths;
+        h.record_bytes = record_bytes();
+        return h;
+    }
+};
+
+// the tile fields of a RenderDev, which is all the status kernel reads of it
+static RenderDev film_tiles(const rayrs_film* f) {
+    RenderDev rp;
+    std::memset(&rp, 0, sizeof(rp));
+    rp.tile_rank = f->prm.tile_rank, rp.tile_ranks = f->prm.tile_ranks;
+    rp.tiles_x = f->tiles_x, rp.tiles_y = f->tiles_y;
+    const uint64_t n_tiles = (uint64_t)f->tiles_x * f->tiles_y;
+    rp.n_local_tiles = n_tiles > rp.tile_rank ? (uint32_t)((n_tiles - rp.tile_rank + rp.tile_ranks - 1) / rp.tile_ranks) : 0u;
+    return rp;
+}
+
+// a film's calls run on the scene's device, behind whatever the scene still has in flight
+static int film_enter(rayrs_film* f) {
+    rayrs_scene* s = f->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->pending && s->last_stream) {
+        HIP_TRY(hipStreamSynchronize(s->last_stream));
+        s->pending = false;
+    }
+    return RAYRS_OK;
+}
+
+static int film_stage(rayrs_film* f) {
+    if (!f->has_stage) {
+        HIP_TRY(f->h_stage.alloc(STAGE_BYTES));
+        f->has_stage = true;
+    }
+    return RAYRS_OK;
+}
+
+extern "C" {
+
+int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, rayrs_film** out) {
+    RAYRS_GUARDED({
+    if (!scene || !camera || !params || !out) return RAYRS_INVALID_ARG;
+    *out = nullptr;
+    rayrs_film_params prm = *params;
+    if (prm.sample_chunk == 0) prm.sample_chunk = 4;
+    if (prm.tile_ranks == 0 && prm.tile_rank == 0) prm.tile_ranks = 1;
+    if (camera->x_pixels == 0 || camera->y_pixels == 0) return RAYRS_INVALID_ARG;
+    if (prm.tile_ranks == 0 || prm.tile_rank >= prm.tile_ranks || prm.fast_traversal > 1u || prm.pad != 0u) return RAYRS_INVALID_ARG;
+    if (camera->x_pixels > 65535u || camera->y_pixels > 65535u) return RAYRS_UNSUPPORTED;
+    if (prm.max_bounces > 8000u) return RAYRS_UNSUPPORTED;
+    if (prm.sample_chunk > SLOT_SAMPLE_MASK) return RAYRS_UNSUPPORTED;  // not one full chunk fits the 30-bit sample cursor
+    if (scene->device < 0) return RAYRS_NO_DEVICE;
+    std::unique_ptr<rayrs_film> f(new rayrs_film());
+    f->scene = scene;
+    f->camera = *camera;
+    f->prm = prm;
+    f->tiles_x = (camera->x_pixels + 7u) / 8u;
+    f->tiles_y = (camera->y_pixels + 7u) / 8u;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(f->d_rec.reserve(f->record_bytes()));
+    HIP_TRY(hipMemset(f->d_rec.as<>(), 0, f->record_bytes()));
+    HIP_TRY(f->d_counts.reserve(sizeof(FilmCounts)));
+    *out = f.release();
+    return RAYRS_OK;
+    })
+}
+
+void rayrs_film_destroy(rayrs_film* film) {
+    if (!film) return;
+    // (the scene outlives its films: the header's rule)
+    if (film->scene && film->scene->device >= 0) (void)hipSetDevice(film->scene->device);
+    delete film;
+}
+
+int rayrs_film_render(rayrs_film* film, uint32_t n, rayrs_render_stats* pass_stats) {
+    RAYRS_GUARDED({
+    if (!film || n == 0 || film->closed) return RAYRS_INVALID_ARG;
+    const uint32_t c = film->prm.sample_chunk;
+    if (film->samples > SLOT_SAMPLE_MASK || n > SLOT_SAMPLE_MASK - (uint32_t)film->samples) return RAYRS_UNSUPPORTED;
+    RAYRS_TRY(film_enter(film));
+    rayrs_render_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.spp = n;  // the pass's window: its chunks are chunks N/c .. of the one-shot frame, N being a multiple of c
+    p.max_bounces = film->prm.max_bounces;
+    p.seed = film->prm.seed;
+    p.sample_chunk = c;  // (c >= n: the window is one chunk, full if n == c)
+    p.tile_rank = film->prm.tile_rank, p.tile_ranks = film->prm.tile_ranks;
+    p.out_format = RAYRS_OUT_F64;
+    p.fast_traversal = film->prm.fast_traversal;
+    FilmPassDev fp;
+    fp.rec = film->d_rec.as<double>();
+    fp.first = film->samples == 0 ? 1u : 0u;
+    fp.full_chunks = n / c;
+    // the accumulate kernel follows the pass's path rounds on the same stream: no host round trip in between
+    RAYRS_TRY(render_enqueue(film->scene, &film->camera, &p, (uint32_t)film->samples, &fp, nullptr, nullptr));
+    rayrs_render_stats st;
+    RAYRS_TRY(rayrs_render_finish(film->scene, &st));
+    film->samples += n;
+    film->full_chunks += n / c;
+    film->rays += st.rays, film->paths += st.paths;
+    if (n % c != 0u) film->closed = true;
+    if (pass_stats) *pass_stats = st;
+    return RAYRS_OK;
+    })
+}
+
+int rayrs_film_read(rayrs_film* film, uint32_t out_format, void* out_host) {
+    RAYRS_GUARDED({
+    if (!film || !out_host || film->samples == 0) return RAYRS_INVALID_ARG;
+    if (out_format != RAYRS_OUT_F32 && out_format != RAYRS_OUT_F64) return RAYRS_INVALID_ARG;
+    RAYRS_TRY(film_enter(film));
+    const size_t bytes = (size_t)film->camera.x_pixels * film->camera.y_pixels * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4);
+    HIP_TRY(film->d_out.reserve(bytes));
+    const CameraDev cam = make_camera_dev(&film->camera);
+    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), 1.0 / (double)film->samples, out_format,
+                             film->d_out.as<>(), nullptr));
+    HIP_TRY(film->d_out.download(out_host, bytes));
+    return RAYRS_OK;
+    })
+}
+
+int rayrs_film_status_get(rayrs_film* film, double tau, rayrs_film_status* out) {
+    RAYRS_GUARDED({
+    if (!film || !out || !(tau >= 0.0) || !std::isfinite(tau)) return RAYRS_INVALID_ARG;
+    RAYRS_TRY(film_enter(film));
+    const CameraDev cam = make_camera_dev(&film->camera);
+    const RenderDev rp = film_tiles(film);
+    HIP_TRY(hipMemsetAsync(film->d_counts.as<>(), 0, sizeof(FilmCounts), nullptr));
+    HIP_TRY(launch_film_status(cam, rp, film->d_rec.as<double>(), film->full_chunks, tau * tau, film->d_counts.as<FilmCounts>(), nullptr));
+    FilmCounts c;
+    HIP_TRY(film->d_counts.download(&c, sizeof(c)));
+    std::memset(out, 0, sizeof(*out));
+    out->samples = film->samples, out->full_chunks = film->full_chunks;
+    out->rays = film->rays, out->paths = film->paths;
+    out->nan_pixels = c.nan_pixels, out->neg_pixels = c.neg_pixels;
+    out->unconverged = c.unconverged, out->nonfinite = c.nonfinite;
+    out->closed = film->closed ? 1u : 0u;
+    return RAYRS_OK;
+    })
+}
+
+uint64_t rayrs_film_state_bytes(const rayrs_film* film) { return film ? sizeof(StateHeader) + film->record_bytes() : 0; }
+
+int rayrs_film_state_get(rayrs_film* film, void* out_host, uint64_t cap) {
+    RAYRS_GUARDED({
+    if (!film || !out_host || cap < rayrs_film_state_bytes(film)) return RAYRS_INVALID_ARG;
+    RAYRS_TRY(film_enter(film));
+    RAYRS_TRY(film_stage(film));
+    const StateHeader h = film->header();
+    uint8_t* dst = static_cast<uint8_t*>(out_host);
+    std::memcpy(dst, &h, sizeof(h));
+    dst += sizeof(h);
+    const uint8_t* src = film->d_rec.as<uint8_t>();
+    for (size_t at = 0, total = film->record_bytes(); at < total; at += STAGE_BYTES) {
+        const size_t piece = total - at < STAGE_BYTES ? total - at : STAGE_BYTES;
+        HIP_TRY(hipMemcpyAsync(film->h_stage.as<void>(), src + at, piece, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        std::memcpy(dst + at, film->h_stage.as<void>(), piece);
+    }
+    return RAYRS_OK;
+    })
+}
+
+int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes) {
+    RAYRS_GUARDED({
+    if (!film || !in_host || bytes < sizeof(StateHeader)) return RAYRS_INVALID_ARG;
+    StateHeader h;
+    std::memcpy(&h, in_host, sizeof(h));
+    const StateHeader mine = film->header();
+    if (h.magic != STATE_MAGIC || h.version != STATE_VERSION) return RAYRS_INVALID_ARG;
+    if (h.x_pixels != mine.x_pixels || h.y_pixels != mine.y_pixels || h.sample_chunk != mine.sample_chunk ||
+        h.max_bounces != mine.max_bounces || h.seed != mine.seed || h.tile_rank != mine.tile_rank ||
+        h.tile_ranks != mine.tile_ranks || h.fast_traversal != mine.fast_traversal)
+        return RAYRS_INVALID_ARG;
+    if (h.record_bytes != mine.record_bytes || bytes != sizeof(StateHeader) + h.record_bytes) return RAYRS_INVALID_ARG;
+    // counters that no sequence of passes leaves behind: not this library's image
+    const uint64_t c = mine.sample_chunk;
+    if (h.closed > 1u || h.samples > SLOT_SAMPLE_MASK || h.full_chunks != h.samples / c || (h.closed == 0u) != (h.samples % c == 0u))
+        return RAYRS_INVALID_ARG;
+    RAYRS_TRY(film_enter(film));
+    RAYRS_TRY(film_stage(film));
+    const uint8_t* src = static_cast<const uint8_t*>(in_host) + sizeof(h);
+    uint8_t* dst = film->d_rec.as<uint8_t>();
+    for (size_t at = 0, total = film->record_bytes(); at < total; at += STAGE_BYTES) {
+        const size_t piece = total - at < STAGE_BYTES ? total - at : STAGE_BYTES;
+        std::memcpy(film->h_stage.as<void>(), src + at, piece);
+        HIP_TRY(hipMemcpyAsync(dst + at, film->h_stage.as<void>(), piece, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    film->samples = h.samples, film->full_chunks = h.full_chunks, film->rays = h.rays, film->paths = h.paths;
+    film->closed = h.closed != 0u;
+    return RAYRS_OK;
+    })
+}
+
+}  // extern "C"

@@ -177,7 +177,9 @@ struct RenderDev {
     uint64_t total_items;  // n_local_tiles * nchunks * 64
     double inv_nchunks, inv_tiles_x;  // reciprocals for udiv_by() in the kernels
     uint32_t refill_min, leaf_min;  // traversal scheduling thresholds (lanes)
-    uint32_t leaf_wait, pad_rd;     // ... the default walk: a leaf phase once this many lanes can do nothing but wait for one
+    uint32_t leaf_wait;             // ... the default walk: a leaf phase once this many lanes can do nothing but wait for one
+    uint32_t sample0;               // first sample of the window: the items' samples are sample0 .. sample0 + spp - 1 (0 but for a film
+                                    // pass, include/rayrs_hip.h rayrs_film_render, whose spp, chunk and nchunks are the pass's)
     uint32_t static_windows;        // pool windows dealt to the traversal waves round robin (wavefront.hip)
     uint32_t count_work;            // also count closest hits per surface (hit kernel)
     double* partial;       // item sums, 3 doubles each, of the items partial_item0 .. (all of them, or one segment's)
@@ -212,8 +214,9 @@ RR_LAYOUT_FN void item_geometry(const RenderDev& rp, uint32_t item, uint32_t& ro
     const uint32_t tile = udiv_by(item >> 6, rp.nchunks, rp.inv_nchunks, chunk) * rp.tile_ranks + rp.tile_rank;
     row = udiv_by(tile, rp.tiles_x, rp.inv_tiles_x, tile_col) * 8u + (pit >> 3);
     col = tile_col * 8u + (pit & 7u);
-    s_begin = chunk * rp.chunk;
-    s_end = s_begin + rp.chunk < rp.spp ? s_begin + rp.chunk : rp.spp;
+    const uint32_t w_end = rp.sample0 + rp.spp;  // the window's end (at most 2^30 - 1: checked at launch)
+    s_begin = rp.sample0 + chunk * rp.chunk;
+    s_end = s_begin + rp.chunk < w_end ? s_begin + rp.chunk : w_end;
 }
 
 }  // namespace rayrs

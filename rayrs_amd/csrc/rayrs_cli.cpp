@@ -1,7 +1,14 @@
 // rayrs_cli.cpp -- the reference's command line (rayrs/src/main.rs) on top of the C ABI:
 //
 //     rayrs hdri_path [spp] [--scene NAME] [--seed N] [--device N] [--max-bounces N] [--fast-traversal 0|1]
-//                           [--gpus N | --devices a,b,...]
+//                           [--gpus N | --devices a,b,...] [--sample-chunk C] [--pass N] [--until-noise TAU]
+//
+// --sample-chunk C sums a pixel's samples in chunks of C (rayrs_render_params.sample_chunk; default 0: the reference's one
+// sequential sum).  --pass N renders through a progressive film (rayrs_film_*) in passes of N samples, rounded up to a
+// multiple of C, and rewrites the PNG and the HDR after each pass; --until-noise TAU stops once every finite pixel is
+// converged at TAU (include/rayrs_hip.h NOISE), with spp as the upper limit, in passes of 16 unless --pass says otherwise.
+// A film sums in chunks (C defaults to 4 with either option) and writes the files a plain render with the same
+// --sample-chunk writes; with none of the three options the program does exactly what it did without them.
 //
 // --gpus N renders on HIP devices 0..N-1 at once (--devices names them; a device may be named more than
 // once to rehearse on fewer GPUs): image tiles interleaved over the devices, one RCCL reduce of the
@@ -118,6 +125,9 @@ int main(int argc, char** argv) {
     int device = 0;
     uint32_t max_bounces = 50;  // main.rs:77
     uint32_t fast_traversal = 0;  // rayrs_render_params.fast_traversal: 0 = the reference's visit set by construction
+    uint32_t sample_chunk = 0, pass = 0;
+    bool chunk_given = false, until_noise = false;
+    double tau = 0.0;
     std::vector<int> devices;
     int i = 2;
     if (i < argc && argv[i][0] != '-') {
@@ -134,6 +144,9 @@ int main(int argc, char** argv) {
         else if (opt == "--max-bounces") max_bounces = (uint32_t)std::atoi(argv[i + 1]);
         else if (opt == "--fast-traversal") fast_traversal = std::atoi(argv[i + 1]) ? 1u : 0u;
         else if (opt == "--exact-traversal") fast_traversal = std::atoi(argv[i + 1]) ? 0u : 1u;  // (the pre-round-5 spelling)
+        else if (opt == "--sample-chunk") sample_chunk = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10), chunk_given = true;
+        else if (opt == "--pass") pass = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10);
+        else if (opt == "--until-noise") tau = std::strtod(argv[i + 1], nullptr), until_noise = true;
         else if (opt == "--gpus") {
             devices.clear();
             for (int d = 0; d < std::atoi(argv[i + 1]); d++) devices.push_back(d);
@@ -153,6 +166,16 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "unknown option %s\n", opt.c_str());
             return 1;
         }
+    }
+    const bool use_film = pass != 0 || until_noise;
+    if (use_film && !devices.empty()) {
+        std::fprintf(stderr, "--pass / --until-noise render through a film, which is single-device: use --device, not --gpus / --devices\n");
+        return 1;
+    }
+    if (use_film && (!chunk_given || sample_chunk == 0)) sample_chunk = 4;
+    if (use_film) {
+        if (pass == 0) pass = 16;
+        pass = (uint32_t)(((uint64_t)pass + sample_chunk - 1) / sample_chunk * sample_chunk);  // an open film takes whole chunks
     }
     SceneDef def;
     if (!make_scene(scene_name, def)) {
@@ -201,15 +224,56 @@ int main(int argc, char** argv) {
     params.spp = spp;
     params.max_bounces = max_bounces;
     params.seed = seed;
-    params.sample_chunk = 0;  // the reference's single sequential sum per pixel
+    params.sample_chunk = sample_chunk;  // 0 (the default): the reference's single sequential sum per pixel
     params.tile_rank = 0;
     params.tile_ranks = 1;
     params.out_format = RAYRS_OUT_F32;
     params.fast_traversal = fast_traversal;
     std::vector<float> rgb((size_t)cam.x_pixels * cam.y_pixels * 3, 0.f);
+    std::vector<uint8_t> bytes(rgb.size());
+    // <scene>.png (gamma 1/2.2) and <scene>.hdr from rgb; the counts of image.rs:218-220 once, for the final frame
+    auto write_files = [&](bool final_frame) -> int {
+        uint64_t counts[3];
+        rayrs_image_to_bytes(rgb.data(), cam.x_pixels, cam.y_pixels, 1. / 2.2, bytes.data(), counts);  // main.rs:106
+        if (final_frame)
+            std::printf("Clamped pixels: %llu\nNaN pixels: %llu\nNegative pixels: %llu\n", (unsigned long long)counts[0],
+                        (unsigned long long)counts[1], (unsigned long long)counts[2]);  // image.rs:218-220
+        int s = rayrs_png_save((scene_name + ".png").c_str(), bytes.data(), cam.x_pixels, cam.y_pixels);
+        if (s != RAYRS_OK) return fail("png", s), s;
+        if ((s = rayrs_hdr_save((scene_name + ".hdr").c_str(), rgb.data(), cam.x_pixels, cam.y_pixels)) != RAYRS_OK) return fail("hdr", s), s;
+        return RAYRS_OK;
+    };
     rayrs_render_stats stats;
+    std::memset(&stats, 0, sizeof stats);
     const auto t0 = std::chrono::steady_clock::now();
-    if (scenes.size() == 1)
+    if (use_film) {
+        rayrs_film_params fprm;
+        std::memset(&fprm, 0, sizeof fprm);
+        fprm.sample_chunk = sample_chunk;
+        fprm.max_bounces = max_bounces;
+        fprm.seed = seed;
+        fprm.fast_traversal = fast_traversal;
+        rayrs_film* film = nullptr;
+        if ((st = rayrs_film_create(scene, &cam, &fprm, &film)) != RAYRS_OK) return fail("film", st);
+        rayrs_film_status fs;
+        std::memset(&fs, 0, sizeof fs);
+        uint32_t done = 0;
+        while (done < spp) {
+            const uint32_t n = spp - done < pass ? spp - done : pass;  // (a short last pass closes the film: it is the last)
+            rayrs_render_stats ps;
+            if ((st = rayrs_film_render(film, n, &ps)) != RAYRS_OK) return fail("film pass", st);
+            done += n;
+            if ((st = rayrs_film_read(film, RAYRS_OUT_F32, rgb.data())) != RAYRS_OK) return fail("film read", st);
+            if ((st = rayrs_film_status_get(film, tau, &fs)) != RAYRS_OK) return fail("film status", st);
+            std::printf("Pass: %u of %u samples, %llu pixels unconverged, %llu not finite\n", done, spp,
+                        (unsigned long long)fs.unconverged, (unsigned long long)fs.nonfinite);
+            if (done < spp && write_files(false) != RAYRS_OK) return 1;
+            if (until_noise && fs.unconverged == 0) break;
+        }
+        std::printf("Samples per pixel: %u\n", done);
+        stats.rays = fs.rays, stats.paths = fs.paths, stats.nan_pixels = fs.nan_pixels, stats.neg_pixels = fs.neg_pixels;
+        rayrs_film_destroy(film);
+    } else if (scenes.size() == 1)
         st = rayrs_render(scene, &cam, &params, rgb.data(), &stats);
     else
         st = rayrs_render_multi(scenes.data(), (uint32_t)scenes.size(), &cam, &params, rgb.data(), &stats);
@@ -220,15 +284,7 @@ int main(int argc, char** argv) {
     std::printf("Time taken %s: %.3f s\n", scene_name.c_str(), secs);         // main.rs:96-100
     std::printf("Rays: %llu (%.1f Mray/s)\n", (unsigned long long)stats.rays, (double)stats.rays / secs / 1e6);
 
-    std::vector<uint8_t> bytes(rgb.size());
-    uint64_t counts[3];
-    rayrs_image_to_bytes(rgb.data(), cam.x_pixels, cam.y_pixels, 1. / 2.2, bytes.data(), counts);  // main.rs:106
-    std::printf("Clamped pixels: %llu\nNaN pixels: %llu\nNegative pixels: %llu\n", (unsigned long long)counts[0],
-                (unsigned long long)counts[1], (unsigned long long)counts[2]);  // image.rs:218-220
-    if ((st = rayrs_png_save((scene_name + ".png").c_str(), bytes.data(), cam.x_pixels, cam.y_pixels)) != RAYRS_OK)
-        return fail("png", st);
-    if ((st = rayrs_hdr_save((scene_name + ".hdr").c_str(), rgb.data(), cam.x_pixels, cam.y_pixels)) != RAYRS_OK)
-        return fail("hdr", st);
+    if (write_files(true) != RAYRS_OK) return 1;
     for (rayrs_scene* sc : scenes) rayrs_scene_destroy(sc);
     return 0;
 }

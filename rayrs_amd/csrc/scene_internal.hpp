@@ -8,6 +8,7 @@
 
 #include "../../include/rayrs_hip.h"
 #include "device_mem.hpp"
+#include "film.h"
 #include "local_pool.h"
 #include "rayrs_lab.h"
 #include "scene_host.hpp"
@@ -93,6 +94,10 @@ CameraDev make_camera_dev(const rayrs_camera* c);
 uint32_t trav_settings(const rayrs_scene* s, bool exact, uint32_t np, RenderDev& rp);
 constexpr size_t POOL_SLOT_BYTES = sizeof(PathSlot) + 4 * sizeof(double) + 1u;  // a slot record, its light entry, its state byte
 WfDev pool_wf(const DevBuf& block, uint32_t np, const DevBuf& ctl, uint32_t trav_blocks, const DevBuf& spill);
+// enqueues a frame (film == nullptr, sample0 = 0: rayrs_render_launch) or a film's pass over the samples sample0 ..
+// sample0 + params->spp - 1 (film_abi.cpp); rayrs_render_finish waits for either (abi.cpp)
+int render_enqueue(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
+                   const FilmPassDev* film, void* out_device, void* hip_stream);
 }  // namespace rayrs
 
 #define HIP_TRY(expr)                                       \

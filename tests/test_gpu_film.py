@@ -1,0 +1,381 @@
+"""The progressive film on the GPU (include/rayrs_hip.h rayrs_film_*), held to the CPU oracle: after passes that add up
+to N samples the film's frame is OracleScene.render(spp=N, sample_chunk=c) bit for bit, for every partition of N, on the
+local-pool route and the streaming one, across a checkpoint, for tile shares, the fast walk and ragged images; and the
+noise counts are those computed from the oracle's per-sample traces (tests/_film.py)."""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _film
+import _nonfinite as N
+import _oracle
+import rayrs_amd
+from rayrs_amd import _ffi, io, procedural, scenes, tiles
+
+pytestmark = pytest.mark.gpu
+
+C, SEED, BOUNCES, W, H = _film.C, _film.SEED, _film.BOUNCES, _film.W, _film.H
+HERE = os.path.dirname(os.path.abspath(__file__))
+CLI = os.path.join(os.path.dirname(os.path.abspath(rayrs_amd.__file__)), "rayrs")
+# (scene of _film.DESCS, rayrs_tuning.local_pool): the local-pool route, the same scene on the streaming route, a mesh
+VARIANTS = [("sphere", 0), ("sphere", 1), ("mesh", 0)]
+IDS = ["sphere-local-pool", "sphere-streaming", "mesh-streaming"]
+PARTITIONS = [(32,), (4,) * 8, (8, 24), (12, 4, 16), (28, 4)]
+
+
+def assert_same_frame(img, ref, what=""):
+    a, b = img.view(np.uint64), ref.view(np.uint64)
+    if not np.array_equal(a, b):
+        bad = (a != b).any(axis=2)
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} pixels differ; first at {np.argwhere(bad)[0]}")
+
+
+class Setup:
+    def __init__(self, name, local_pool, w=W, h=H):
+        self.name, self.desc = name, _film.DESCS[name](w, h)
+        cam_args, objs, heur, env = self.desc
+        self.scene = rayrs_amd.Scene(objs, 1e-6, 1e6, heur, env, device=0)
+        self.scene.set_tuning(local_pool=local_pool)
+        assert self.scene.info()["local_pool"] == (1 if name == "sphere" and local_pool == 0 else 0)
+        self.cam = rayrs_amd.Camera(*cam_args)
+        self.osc, self.ocam = _film.oracle_of(self.desc)
+        self._refs = {}
+
+    def film(self, **kw):
+        kw.setdefault("sample_chunk", C)
+        return rayrs_amd.Film(self.scene, self.cam, max_bounces=BOUNCES, seed=SEED, **kw)
+
+    def ref(self, n, c=C):
+        if (n, c) not in self._refs:
+            self._refs[(n, c)] = self.osc.render(self.ocam, n, BOUNCES, SEED, sample_chunk=c)
+        return self._refs[(n, c)]
+
+
+def check_final(s, film, n, rays, paths, what):
+    """The film after n samples against the oracle's one-shot frame: both formats, the counters, the status."""
+    ref, ost = s.ref(n)
+    img = film.image(out_f64=True)
+    assert_same_frame(img, ref, what)
+    img32 = film.image()
+    assert img32.dtype == np.float32 and np.array_equal(img32.view(np.uint32), img.astype(np.float32).view(np.uint32)), what
+    st = film.status(0.2)
+    assert (rays, paths) == (ost["rays"], ost["paths"]) == (st["rays"], st["paths"]), what
+    assert (st["nan_pixels"], st["neg_pixels"]) == (ost["nan_pixels"], ost["neg_pixels"]), what
+    assert st["samples"] == n and st["full_chunks"] == n // C and st["closed"] == (1 if n % C else 0), what
+    return img, st
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_any_partition_renders_the_same_bits(variant):
+    s = Setup(*variant)
+    for part in PARTITIONS:
+        film = s.film()
+        n = rays = paths = 0
+        for k in part:
+            st = film.render(k)
+            assert st["local_pool"] == s.scene.info()["local_pool"]
+            n, rays, paths = n + k, rays + st["rays"], paths + st["paths"]
+            assert_same_frame(film.image(out_f64=True), s.ref(n)[0], f"{variant} {part} after {n}")
+        assert n == 32
+        check_final(s, film, 32, rays, paths, f"{variant} {part}")
+        film.close()
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_the_film_equals_the_one_shot_render_and_leaves_plain_renders_alone(variant):
+    s = Setup(*variant)
+    one, ost = rayrs_amd.render(s.scene, s.cam, 32, BOUNCES, SEED, sample_chunk=C, out_f64=True)
+    plain_before, pst = rayrs_amd.render(s.scene, s.cam, 5, BOUNCES, SEED, out_f64=True)
+    assert_same_frame(plain_before, s.ref(5, 0)[0], "plain render before")
+    film = s.film()
+    film.render(8)
+    plain_between, pst2 = rayrs_amd.render(s.scene, s.cam, 5, BOUNCES, SEED, out_f64=True)   # shares the pool and the item sums
+    assert_same_frame(plain_between, plain_before, "plain render between two passes")
+    assert (pst2["rays"], pst2["nan_pixels"], pst2["neg_pixels"]) == (pst["rays"], pst["nan_pixels"], pst["neg_pixels"])
+    film.render(24)
+    assert_same_frame(film.image(out_f64=True), one, "film against rayrs_render")
+    assert_same_frame(one, s.ref(32)[0], "rayrs_render against the oracle")
+    st = film.status(0.2)
+    assert (st["rays"], st["paths"], st["nan_pixels"], st["neg_pixels"]) == (ost["rays"], ost["paths"], ost["nan_pixels"], ost["neg_pixels"])
+    after, _ = rayrs_amd.render(s.scene, s.cam, 32, BOUNCES, SEED, sample_chunk=C, out_f64=True)
+    assert_same_frame(after, one, "plain render after the film")
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_a_short_last_chunk_closes_the_film(variant):
+    s = Setup(*variant)
+    film = s.film()
+    a = film.render(16)
+    b = film.render(14)
+    img, st = check_final(s, film, 30, a["rays"] + b["rays"], a["paths"] + b["paths"], f"{variant} (16, 14)")
+    assert st["closed"] == 1 and st["full_chunks"] == 7
+    for n in (4, 2, 0):
+        with pytest.raises(_ffi.RayrsError) as e:
+            film.render(n)
+        assert e.value.status == -1
+    assert_same_frame(film.image(out_f64=True), img, "after the refused passes")
+    assert film.status(0.2) == st
+    with pytest.raises(_ffi.RayrsError) as e:       # n = 0 on an open film, and reading an empty one
+        s.film().render(0)
+    assert e.value.status == -1
+    with pytest.raises(_ffi.RayrsError):
+        s.film().image()
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_noise_counts_are_the_oracles(variant):
+    s = Setup(*variant)
+    rgb = _film.named_traces(s.name, 32)
+    film = s.film()
+    film.render(4)
+    for tau in _film.TAUS:   # M = 1: every pixel is unconverged
+        st = film.status(tau)
+        assert (st["unconverged"], st["nonfinite"], st["full_chunks"]) == (W * H, 0, 1)
+    film.render(12)
+    seen = []
+    for n in (16, 32):
+        frame, s1, s2, m = _film.expectation(rgb, C, n)
+        assert_same_frame(film.image(out_f64=True), frame, f"{variant} frame from traces at {n}")
+        for tau in _film.TAUS:
+            st = film.status(tau)
+            want = _film.noise_counts(s1, s2, m, tau)
+            print(f"{variant} N={n} tau={tau}: unconverged {st['unconverged']} nonfinite {st['nonfinite']} oracle {want}")
+            assert (st["unconverged"], st["nonfinite"], st["full_chunks"]) == (want[0], want[1], m), (variant, n, tau)
+            seen.append(st["unconverged"])
+        if n == 16:
+            film.render(16)
+    assert 0 < seen[1] < W * H and 0 < seen[4] < W * H   # tau = 0.2 after 16 and 32: not satisfied by a count of 0 or of all
+
+
+def test_noise_counts_with_non_finite_pixels():
+    """A scene of tests/_nonfinite.py whose oracle frame has NaN pixels: they are in nonfinite and nan_pixels, not in
+    unconverged; the counts are the oracle-derived ones; two partitions agree with the oracle NaN-aware and with each
+    other bit for bit."""
+    desc = N.FAMILIES["emit_inf_red"][0]()
+    cam_args, objs, heur, env = desc
+    osc, ocam = _oracle.OracleScene(objs, 1e-6, 1e6, heur, env), _oracle.OracleCamera(*cam_args)
+    ref, ost = osc.render(ocam, 16, N.BUDGET, SEED, sample_chunk=C)
+    assert ost["nan_pixels"] > 0
+    rgb = _film.traces(osc, ocam, 16, SEED, N.BUDGET)
+    frame, s1, s2, m = _film.expectation(rgb, C, 16)
+    N.assert_same_frame_nan_aware(frame, ref, "reconstruction")
+    nan_px = np.isnan(ref).any(axis=2)
+    assert not (np.isfinite(s1) & np.isfinite(s2))[nan_px].any()
+    for local_pool in (0, 1):
+        scene = rayrs_amd.Scene(objs, 1e-6, 1e6, heur, env, device=0)
+        scene.set_tuning(local_pool=local_pool)
+        cam = rayrs_amd.Camera(*cam_args)
+        frames = []
+        for part in ((16,), (4, 12)):
+            film = rayrs_amd.Film(scene, cam, sample_chunk=C, max_bounces=N.BUDGET, seed=SEED)
+            for k in part:
+                film.render(k)
+            img = film.image(out_f64=True)
+            N.assert_same_frame_nan_aware(img, ref, f"local_pool={local_pool} {part}")
+            frames.append(img)
+            for tau in _film.TAUS:
+                st = film.status(tau)
+                want = _film.noise_counts(s1, s2, m, tau)
+                assert (st["unconverged"], st["nonfinite"]) == want, (local_pool, part, tau)
+                assert st["nan_pixels"] == ost["nan_pixels"] == int(nan_px.sum()) and st["neg_pixels"] == ost["neg_pixels"]
+                assert st["nonfinite"] >= st["nan_pixels"] and st["unconverged"] + st["nonfinite"] <= N.W * N.H
+        assert np.array_equal(frames[0].view(np.uint64), frames[1].view(np.uint64))
+
+
+CHILD = r"""
+import json, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
+import _film, rayrs_amd
+name, local_pool, state, out = sys.argv[3], int(sys.argv[4]), sys.argv[5], sys.argv[6]
+cam_args, objs, heur, env = _film.DESCS[name]()
+scene = rayrs_amd.Scene(objs, 1e-6, 1e6, heur, env, device=0)
+scene.set_tuning(local_pool=local_pool)
+film = rayrs_amd.Film(scene, rayrs_amd.Camera(*cam_args), sample_chunk=_film.C, max_bounces=_film.BOUNCES, seed=_film.SEED)
+film.load(state)
+film.render(16)
+np.save(out + ".npy", film.image(out_f64=True))
+json.dump(film.status(0.2), open(out + ".json", "w"))
+"""
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_a_checkpoint_continues_in_a_new_film_and_in_a_fresh_process(variant, tmp_path):
+    s = Setup(*variant)
+    whole = s.film()
+    a = whole.render(16)
+    b = whole.render(16)
+    img, st = check_final(s, whole, 32, a["rays"] + b["rays"], a["paths"] + b["paths"], "uninterrupted")
+    first = s.film()
+    first.render(16)
+    path = tmp_path / "film.state"
+    first.save(path)
+    assert os.path.getsize(path) == len(first.state())
+    first.close()
+    # a new Scene and Film in this process
+    s2 = Setup(*variant)
+    again = s2.film()
+    again.load(path)
+    assert again.status(0.2)["samples"] == 16
+    assert_same_frame(again.image(out_f64=True), s.ref(16)[0], "loaded film")
+    again.render(16)
+    assert_same_frame(again.image(out_f64=True), img, "continued in a new film")
+    assert again.status(0.2) == st
+    # a child process started fresh
+    out = str(tmp_path / "child")
+    r = subprocess.run([sys.executable, "-c", CHILD, os.path.dirname(HERE), HERE, variant[0], str(variant[1]), str(path), out],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert_same_frame(np.load(out + ".npy"), img, "continued in a child process")
+    assert json.load(open(out + ".json")) == st
+    # an image made with other settings, a truncated one, another version word: refused, nothing changes
+    image = again.state()
+    before_img, before_st = again.image(out_f64=True), again.status(0.2)
+    cam2 = rayrs_amd.Camera(*scenes.camera_for_resolution(s.desc[0], W + 8, H))
+    others = [s2.film(), rayrs_amd.Film(s2.scene, s2.cam, sample_chunk=C, max_bounces=BOUNCES, seed=SEED + 1),
+              s2.film(sample_chunk=8), rayrs_amd.Film(s2.scene, cam2, sample_chunk=C, max_bounces=BOUNCES, seed=SEED),
+              s2.film(tile_rank=1, tile_ranks=2), s2.film(fast_traversal=True),
+              rayrs_amd.Film(s2.scene, s2.cam, sample_chunk=C, max_bounces=BOUNCES - 1, seed=SEED)]
+    others[0].set_state(image)   # the same settings: accepted
+    assert_same_frame(others[0].image(out_f64=True), before_img, "state_set with equal settings")
+    for other in others[1:]:
+        other.render(4)
+        keep_img, keep_st = other.image(out_f64=True), other.status(0.2)
+        with pytest.raises(_ffi.RayrsError) as e:
+            other.set_state(image)
+        assert e.value.status == -1
+        assert np.array_equal(other.image(out_f64=True).view(np.uint64), keep_img.view(np.uint64)) and other.status(0.2) == keep_st
+    bad_version = bytearray(image)
+    bad_version[4] ^= 1
+    for bad in (image[:-8], image[:40], image + b"\0" * 8, bytes(bad_version)):
+        with pytest.raises(_ffi.RayrsError) as e:
+            again.set_state(bad)
+        assert e.value.status == -1
+    assert_same_frame(again.image(out_f64=True), before_img, "after the refused images")
+    assert again.status(0.2) == before_st
+    small = np.zeros(16, dtype=np.uint8)
+    assert _ffi.lib().rayrs_film_state_get(again._h, small.ctypes.data, 16) == -1
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_tile_shares_add_up_to_the_frame(variant):
+    s = Setup(*variant)
+    ref, ost = s.ref(16)
+    rgb = _film.named_traces(s.name, 32)
+    _, s1, s2, m = _film.expectation(rgb, C, 16)
+    total, rays, unconverged = np.zeros_like(ref), 0, 0
+    for r in range(3):
+        film = s.film(tile_rank=r, tile_ranks=3)
+        rays += film.render(8)["rays"] + film.render(8)["rays"]
+        img = film.image(out_f64=True)
+        mask = tiles.tile_mask(W, H, r, 3)
+        assert film.pixels() == int(mask.sum())
+        assert (img[~mask] == 0).all() and not np.signbit(img[~mask]).any()
+        assert np.array_equal(img[mask].view(np.uint64), ref[mask].view(np.uint64)), r
+        total += img
+        st = film.status(0.2)
+        assert (st["unconverged"], st["nonfinite"]) == _film.noise_counts(s1, s2, m, 0.2, mask), r
+        unconverged += st["unconverged"]
+    assert_same_frame(total, ref, "the three shares summed")
+    assert rays == ost["rays"] and unconverged == _film.noise_counts(s1, s2, m, 0.2)[0]
+
+
+def test_the_fast_walk_serves_a_film():
+    s = Setup("mesh", 0)
+    ref, ost = s.osc.use_product_walk(s.scene, fast=True).render(s.ocam, 16, BOUNCES, SEED, sample_chunk=C, traversal=2)
+    film = s.film(fast_traversal=True)
+    a = film.render(4)
+    b = film.render(12)
+    assert a["exact_walk"] == 0 and b["exact_walk"] == 0
+    assert_same_frame(film.image(out_f64=True), ref, "fast walk")
+    assert a["rays"] + b["rays"] == ost["rays"]
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_ragged_edges(variant):
+    s = Setup(*variant, w=61, h=19)
+    assert (s.cam.x_pixels(), s.cam.y_pixels()) == (61, 19)
+    film = s.film()
+    a = film.render(8)
+    b = film.render(8)
+    check_final(s, film, 16, a["rays"] + b["rays"], a["paths"] + b["paths"], f"{variant} 61x19")
+    rgb = _film.traces(s.osc, s.ocam, 16)
+    _, s1, s2, m = _film.expectation(rgb, C, 16)
+    st = film.status(0.2)
+    assert (st["unconverged"], st["nonfinite"]) == _film.noise_counts(s1, s2, m, 0.2)
+    assert film.pixels() == 61 * 19
+
+
+def test_render_until_stops_where_the_oracle_says():
+    s = Setup("sphere", 0)
+    rgb = _film.named_traces("sphere", 64)
+    unconverged = {n: _film.noise_counts(*_film.expectation(rgb, C, n)[1:], 0.5)[0] for n in range(8, 65, 8)}
+    print("unconverged at tau = 0.5 after n samples:", unconverged)
+    stop = next((n for n in range(8, 65, 8) if unconverged[n] == 0), None)
+    assert stop is not None and 8 < stop < 64, unconverged   # neither at once nor on the budget
+    film = s.film()
+    seen = []
+    st, why = rayrs_amd.render_until(film, 0.5, 0.0, pass_samples=8, max_samples=64, on_pass=lambda f, x: seen.append(x["unconverged"]))
+    assert why == "converged" and st["samples"] == stop and st["unconverged"] == 0
+    assert seen == [unconverged[n] for n in range(8, stop + 1, 8)]
+    assert_same_frame(film.image(out_f64=True), s.ref(stop)[0], "the frame render_until leaves")
+    film = s.film()
+    st, why = rayrs_amd.render_until(film, 0.5, 0.0, pass_samples=8, max_samples=8)
+    assert why == "max_samples" and st["samples"] == 8 and st["unconverged"] == unconverged[8] > 0
+
+
+def run_cli(args, cwd):
+    cwd.mkdir()
+    r = subprocess.run([CLI] + args, cwd=cwd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    return r.stdout, (cwd / "diffuse_single_sphere.png").read_bytes(), (cwd / "diffuse_single_sphere.hdr").read_bytes()
+
+
+def test_command_line_passes_and_noise_stop(tmp_path):
+    io.save_hdr(tmp_path / "env.hdr", procedural.make_hdri(64, 32))
+    base = [str(tmp_path / "env.hdr"), "64", "--scene", "diffuse_single_sphere", "--seed", "9"]
+    _, png_plain, hdr_plain = run_cli(base + ["--sample-chunk", "4"], tmp_path / "plain")
+    out, png_film, hdr_film = run_cli(base + ["--sample-chunk", "4", "--pass", "16"], tmp_path / "film")
+    assert png_film == png_plain and hdr_film == hdr_plain
+    assert out.count("Pass: ") == 4 and "Samples per pixel: 64" in out
+    # the files the library's writers make from rayrs_amd.render(..., sample_chunk=4)
+    cam_args, objs, heur = scenes.diffuse_single_sphere()
+    scene = rayrs_amd.Scene(objs, 1e-6, 1e6, heur, io.load_hdr(tmp_path / "env.hdr"), device=0)
+    cam = rayrs_amd.Camera(*cam_args)
+    img, _ = rayrs_amd.render(scene, cam, 64, 50, seed=9, sample_chunk=4)
+    io.save_png(tmp_path / "lib.png", io.to_raw_bytes(img)[0])
+    io.save_hdr(tmp_path / "lib.hdr", img)
+    assert (tmp_path / "lib.png").read_bytes() == png_plain and (tmp_path / "lib.hdr").read_bytes() == hdr_plain
+    # --sample-chunk alone changes nothing else: without it the program renders the reference's sequential sum
+    _, png_seq, _ = run_cli(base, tmp_path / "seq")
+    img0, _ = rayrs_amd.render(scene, cam, 64, 50, seed=9)
+    io.save_png(tmp_path / "lib0.png", io.to_raw_bytes(img0)[0])
+    assert (tmp_path / "lib0.png").read_bytes() == png_seq
+    # --until-noise: a tau at which the film stops neither after the first pass nor at the full 64, found through Python
+    taus = (0.95, 0.9, 0.85, 0.8, 0.7, 0.6, 0.5, 0.4)
+    film = rayrs_amd.Film(scene, cam, sample_chunk=4, max_bounces=50, seed=9)
+    first_zero = {}
+    for n in range(8, 65, 8):
+        film.render(8)
+        for tau in taus:
+            if tau not in first_zero and film.status(tau)["unconverged"] == 0:
+                first_zero[tau] = n
+    print("samples at which every finite pixel is converged, by tau:", first_zero)
+    tau = next((t for t in taus if 8 < first_zero.get(t, 64) < 64), None)
+    if tau is None:   # no such tau at the program's image size: the two counts are compared all the same
+        tau = 0.5
+    film = rayrs_amd.Film(scene, cam, sample_chunk=4, max_bounces=50, seed=9)
+    st, why = rayrs_amd.render_until(film, tau, 0.0, pass_samples=8, max_samples=64)
+    out, _, _ = run_cli(base + ["--until-noise", repr(tau), "--pass", "8"], tmp_path / "noise")
+    stopped = int(re.search(r"Samples per pixel: (\d+)", out).group(1))
+    assert stopped == st["samples"], (tau, why)
+    if tau in first_zero and 8 < first_zero[tau] < 64:
+        assert why == "converged" and stopped == first_zero[tau]
+    # films are single-device here
+    r = subprocess.run([CLI] + base + ["--pass", "8", "--gpus", "2"], cwd=tmp_path, capture_output=True, text=True)
+    assert r.returncode == 1 and "single-device" in r.stderr
