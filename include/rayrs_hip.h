@@ -420,7 +420,23 @@ int rayrs_scene_set_tuning(rayrs_scene* scene, const rayrs_tuning* tuning);
  * estimated from their sample variance, is at most tau times the mean.  No square root and no division, so the count
  * is exactly reproducible.  A pixel whose S1 or S2 is not finite counts in `nonfinite` and not in `unconverged`;
  * `unconverged` = the pixels of the film's share that are neither converged nor non-finite.  With M < 2 every finite
- * pixel is unconverged. */
+ * pixel is unconverged.
+ *
+ * ADAPTIVE PASSES.  The film keeps a sample count N_t per 8x8 tile of the frame (the tile is the unit of a tile share and
+ * of the film's records), and rayrs_film_render_adaptive adds samples only to the tiles that are still noisy.  THE
+ * CONTRACT PER TILE: after any sequence of passes, the pixels of tile t that rayrs_film_read returns are, bit for bit in
+ * both formats, the pixels rayrs_render returns for spp = N_t, sample_chunk = c and the same seed, max_bounces, tile
+ * share and walk -- a tile may stop at its own sample count because of the two facts THE CONTRACT above rests on.
+ * SELECTION: a pass of n samples takes tile t of the share iff N_t + n <= max_tile_samples and at least one pixel of the
+ * tile inside the image is unconverged at tau by NOISE above, with M = M_t = N_t / c, the tile's own full chunks; a
+ * non-finite pixel keeps no tile active, and neither does the padding of an edge tile.  The selected tiles are sampled
+ * in ascending tile order, so a pass's work is a function of the film's state alone.
+ *   On a film whose tiles differ: the status's noise counts use each tile's own M_t in the same predicate;
+ * rayrs_film_status.samples is the largest N_t and full_chunks that divided by c; rays and paths stay the sums over
+ * all passes; nan_pixels and neg_pixels are of the running sums as they stand; rayrs_film_read divides tile t by N_t.
+ * rayrs_film_render(film, n) adds n samples to every tile from its own N_t, closes the film if n % c != 0, and its limit
+ * is (largest N_t) + n < 2^30.  A film that only ever saw passes that took every tile behaves exactly as one that saw
+ * rayrs_film_render alone. */
 typedef struct rayrs_film rayrs_film;
 
 typedef struct {            /* zero-initialise */
@@ -448,13 +464,24 @@ void rayrs_film_destroy(rayrs_film* film);
 /* Adds the samples N .. N+n-1 to every pixel of the film's share.  Synchronous.  pass_stats (may be NULL): as
  * rayrs_render's, for this pass alone (its nan_pixels / neg_pixels are 0: they are the status's). */
 int rayrs_film_render(rayrs_film* film, uint32_t n, rayrs_render_stats* pass_stats);
+/* Selects the tiles of the film's share with N_t + n <= max_tile_samples (0 = no cap but the 30-bit cursor) in which at
+ * least one in-image pixel is unconverged at tau (NOISE, with M = N_t / c), and adds the samples N_t .. N_t + n - 1 to
+ * every pixel of each selected tile.  n > 0 and n % c == 0 (an adaptive pass never closes a film); a closed film, a bad
+ * tau or n: RAYRS_INVALID_ARG, nothing changes.  *active_tiles = the number selected; 0 is RAYRS_OK with no launch and
+ * pass_stats zeroed.  On an empty film every tile is selected (M = 0: every finite pixel is unconverged).  Synchronous;
+ * active_tiles and pass_stats may be NULL. */
+int rayrs_film_render_adaptive(rayrs_film* film, uint32_t n, double tau, uint32_t max_tile_samples,
+                               uint64_t* active_tiles, rayrs_render_stats* pass_stats);
+/* N_t for the tiles_x * tiles_y tiles of the frame (tiles_x = ceil(x_pixels / 8)), row-major; 0 for tiles outside the
+ * share.  Returns the number of tiles; writes min(that, cap). */
+uint64_t rayrs_film_tile_samples(rayrs_film* film, uint32_t* out, uint64_t cap);
 /* The frame as it stands: running sum * (1 / N) as RAYRS_OUT_F32 or RAYRS_OUT_F64 into a HOST buffer of
  * y_pixels*x_pixels*3 elements.  RAYRS_INVALID_ARG on an empty film. */
 int rayrs_film_read(rayrs_film* film, uint32_t out_format, void* out_host);
 /* tau: finite and >= 0. */
 int rayrs_film_status_get(rayrs_film* film, double tau, rayrs_film_status* out);
-/* Checkpoint: an opaque, versioned byte image of the film -- sums, statistics, counters and the settings it was created
- * with.  rayrs_film_state_set accepts only an image of this library's image version whose recorded image size, c, seed,
+/* Checkpoint: an opaque, versioned byte image of the film -- sums, statistics, counters, the per-tile sample counts (4
+ * bytes per tile of the frame; image version 2, images of version 1 are refused) and the settings it was created with.  rayrs_film_state_set accepts only an image of this library's image version whose recorded image size, c, seed,
  * max_bounces, tile share and walk equal the film's, and whose length is exactly rayrs_film_state_bytes; otherwise
  * RAYRS_INVALID_ARG and the film is unchanged.  The scene and the camera themselves are NOT recorded: continuing on
  * another scene or view is the caller's error. */
@@ -466,7 +493,8 @@ int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes);
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
  * rayrs_render_stats.hot_*, rayrs_scene_export_hot_tree, rayrs_obj_load_spheres.  7: the progressive film (rayrs_film_*, rayrs_film_params,
- * rayrs_film_status; no existing struct changed).  The layout table below begins with this
+ * rayrs_film_status; no existing struct changed); still 7 with rayrs_film_render_adaptive and rayrs_film_tile_samples: entry points
+ * were added, no struct or existing call changed.  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

@@ -24,6 +24,7 @@ SYMBOLS = [
     "rayrs_frame_sample_chunk", "rayrs_render", "rayrs_render_launch", "rayrs_render_finish", "rayrs_render_multi",
     "rayrs_film_create", "rayrs_film_destroy", "rayrs_film_render", "rayrs_film_read", "rayrs_film_status_get",
     "rayrs_film_state_bytes", "rayrs_film_state_get", "rayrs_film_state_set",
+    "rayrs_film_render_adaptive", "rayrs_film_tile_samples",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -198,6 +199,9 @@ def lib():
     L.rayrs_film_state_bytes.restype = C.c_uint64
     L.rayrs_film_state_get.argtypes = [vp, vp, C.c_uint64]
     L.rayrs_film_state_set.argtypes = [vp, vp, C.c_uint64]
+    L.rayrs_film_render_adaptive.argtypes = [vp, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(RenderStats)]
+    L.rayrs_film_tile_samples.argtypes = [vp, vp, C.c_uint64]
+    L.rayrs_film_tile_samples.restype = C.c_uint64
     L.rayrs_test_math.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
     L.rayrs_test_rng.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
     L.rayrs_test_intersect.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp]

@@ -478,8 +478,30 @@ class Film:
         _ffi.check(self._L.rayrs_film_render(self._h, int(n), C.byref(st)), "rayrs_film_render")
         return st.as_dict()
 
+    def render_adaptive(self, n: int, tau: float, max_tile_samples: int = 0):
+        """Adds n samples (a multiple of sample_chunk) to the 8x8 tiles of the share that hold a pixel unconverged at
+        tau and at most max_tile_samples - n samples (0: no cap).  Returns (active_tiles, stats); no tile selected is
+        (0, zeroed stats) and leaves the film as it is."""
+        st, active = _ffi.RenderStats(), C.c_uint64(0)
+        _ffi.check(self._L.rayrs_film_render_adaptive(self._h, int(n), float(tau), int(max_tile_samples), C.byref(active),
+                                                      C.byref(st)), "rayrs_film_render_adaptive")
+        return int(active.value), st.as_dict()
+
+    def tile_samples(self):
+        """Samples per 8x8 tile of the frame, (tiles_y, tiles_x) uint32; 0 outside the film's share."""
+        ty, tx = (self.camera.y_pixels() + 7) // 8, (self.camera.x_pixels() + 7) // 8
+        out = np.zeros((ty, tx), dtype=np.uint32)
+        if int(self._L.rayrs_film_tile_samples(self._h, out.ctypes.data, out.size)) != out.size:
+            raise RuntimeError("rayrs_film_tile_samples: the film has another number of tiles than its camera")
+        return out
+
+    def sample_map(self):
+        """Samples per pixel, (y_pixels, x_pixels) uint32: tile_samples() spread over the pixels."""
+        per_tile = self.tile_samples()
+        return np.repeat(np.repeat(per_tile, 8, axis=0), 8, axis=1)[:self.camera.y_pixels(), :self.camera.x_pixels()].copy()
+
     def image(self, out_f64: bool = False):
-        """The frame as it stands: (y_pixels, x_pixels, 3), f32 or f64."""
+        """The frame as it stands: (y_pixels, x_pixels, 3), f32 or f64 (a tile's sum over its own sample count)."""
         out = np.zeros((self.camera.y_pixels(), self.camera.x_pixels(), 3), dtype=np.float64 if out_f64 else np.float32)
         _ffi.check(self._L.rayrs_film_read(self._h, 1 if out_f64 else 0, out.ctypes.data), "rayrs_film_read")
         return out
@@ -530,12 +552,16 @@ class Film:
 
 
 def render_until(film, tau: float, max_unconverged_fraction: float = 0.0, pass_samples: int = 16, max_samples: int = 1024,
-                 time_budget_s: Optional[float] = None, on_pass=None):
+                 time_budget_s: Optional[float] = None, on_pass=None, adaptive: bool = False):
     """Adds passes of pass_samples samples (rounded up to a multiple of the film's sample_chunk) until at most
     max_unconverged_fraction of its pixels are unconverged at tau ("converged"), or the next
     pass would take the film beyond max_samples ("max_samples"), or time_budget_s seconds have passed ("time_budget").
     on_pass(film, status) is called after every pass.  Returns (status, reason); the status is film.status(tau) as it
-    stands, with "pixels" added."""
+    stands, with "pixels" added.
+    adaptive: the passes are film.render_adaptive(step, tau, max_samples) -- only the tiles that still hold an unconverged
+    pixel get samples, none beyond max_samples -- and "max_samples" is a pass that selects no tile while pixels are still
+    unconverged; the status then also has "active_tiles" of the last pass, "tile_samples_min" and "tile_samples_max" over
+    the share's tiles, and "pixel_samples", the samples summed over the share's pixels."""
     import time
     c = int(film.sample_chunk)
     step = -(-int(pass_samples) // c) * c
@@ -552,16 +578,31 @@ def render_until(film, tau: float, max_unconverged_fraction: float = 0.0, pass_s
         if done(st):
             reason = "converged"
             break
-        if st["closed"] or st["samples"] + step > max_samples:
+        if st["closed"] or (max_samples < step if adaptive else st["samples"] + step > max_samples):
             reason = "max_samples"
             break
         if time_budget_s is not None and time.monotonic() - t0 >= time_budget_s:
             reason = "time_budget"
             break
-        film.render(step)
+        if adaptive:
+            active, _ = film.render_adaptive(step, tau, max_samples)
+            if active == 0:  # every tile that is still noisy has its max_samples
+                reason = "max_samples"
+                break
+        else:
+            film.render(step)
         st = film.status(tau)
+        if adaptive:
+            st = dict(st, active_tiles=active)
         if on_pass is not None:
             on_pass(film, st)
     st = dict(st)
     st["pixels"] = pixels
+    if adaptive:
+        from . import tiles
+        cam = film.camera
+        per_pixel = film.sample_map()[tiles.tile_mask(cam.x_pixels(), cam.y_pixels(), film.tile_rank, film.tile_ranks)]
+        st["tile_samples_min"] = int(per_pixel.min()) if per_pixel.size else 0
+        st["tile_samples_max"] = int(per_pixel.max()) if per_pixel.size else 0
+        st["pixel_samples"] = int(per_pixel.astype(np.uint64).sum())
     return st, reason

@@ -709,9 +709,10 @@ struct FramePlan {
     FilmPassDev film;
 };
 
-// The frame's items: the (pixel, chunk) pairs of this rank's 8x8 tiles (the caller refuses 2^32 of them and more).
+// The frame's items: the (pixel, chunk) pairs of this rank's 8x8 tiles (the caller refuses 2^32 of them and more) -- or,
+// for a film pass over a tile list, of the list's tiles.
 static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
-                                 void* out_device) {
+                                 const FilmPassDev* film, void* out_device) {
     RenderDev rp;
     std::memset(&rp, 0, sizeof(rp));
     rp.spp = params->spp;
@@ -725,7 +726,11 @@ static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* c
     rp.tiles_x = (camera->x_pixels + 7) / 8;
     rp.tiles_y = (camera->y_pixels + 7) / 8;
     const uint64_t n_tiles = (uint64_t)rp.tiles_x * rp.tiles_y;
-    const uint64_t n_local = n_tiles > rp.tile_rank ? (n_tiles - rp.tile_rank + rp.tile_ranks - 1) / rp.tile_ranks : 0;
+    uint64_t n_local = n_tiles > rp.tile_rank ? (n_tiles - rp.tile_rank + rp.tile_ranks - 1) / rp.tile_ranks : 0;
+    if (film && film->list) {  // (at most the share's tiles)
+        n_local = film->n_list < n_local ? film->n_list : n_local;
+        rp.tile_list = film->list;
+    }
     rp.n_local_tiles = (uint32_t)n_local;
     rp.total_items = n_local * rp.nchunks * 64ull;
     rp.inv_nchunks = 1.0 / (double)rp.nchunks;
@@ -739,9 +744,9 @@ static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* c
 }
 
 static int plan_frame(const rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
-                      void* out_device, FramePlan& p) {
+                      const FilmPassDev* film, void* out_device, FramePlan& p) {
     const rayrs_lab_tuning& lab = scene->lab;
-    RenderDev& rp = p.rp = make_render_dev(scene, camera, params, sample0, out_device);
+    RenderDev& rp = p.rp = make_render_dev(scene, camera, params, sample0, film, out_device);
     if (rp.total_items >= (1ull << 32)) return RAYRS_UNSUPPORTED;
     // Item sums: 24 bytes per (pixel, chunk) item, added per pixel in chunk order by the resolve kernel.  The streaming
     // kernels finish items in no particular order, so the array covers the frame.  The local-pool route renders the frame
@@ -897,7 +902,8 @@ static int enqueue_streaming(rayrs_scene* scene, const FramePlan& p, const WfDev
 
 // A frame, or a film's pass: the samples sample0 .. sample0 + params->spp - 1 of every pixel of the share, summed per chunk
 // of that window.  film == nullptr: the chunk sums are resolved into out_device (rayrs_render_launch, sample0 = 0); else
-// they are added to the film's records and out_device is not used.
+// they are added to the film's records and out_device is not used.  A film pass with a tile list covers the list's tiles
+// only, each from its own sample count (sample0 is not used): the plan -- items, pool, grids -- is sized by the list.
 extern "C++" int rayrs::render_enqueue(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
                                        const FilmPassDev* film, void* out_device, void* hip_stream) {
     RAYRS_GUARDED({
@@ -920,9 +926,9 @@ extern "C++" int rayrs::render_enqueue(rayrs_scene* scene, const rayrs_camera* c
     }
 
     FramePlan p;
-    RAYRS_TRY(plan_frame(scene, camera, params, sample0, out_device, p));
+    RAYRS_TRY(plan_frame(scene, camera, params, sample0, film, out_device, p));
     p.is_film = film != nullptr;
-    p.film = film ? *film : FilmPassDev{nullptr, 0u, 0u};
+    p.film = film ? *film : FilmPassDev{};
     scene->last_exact = p.exact;
 
     // ---- what the plan needs of the scene's buffers, which only grow (nothing of the route the frame does not take)

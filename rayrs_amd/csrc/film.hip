@@ -35,7 +35,12 @@ __global__ void __launch_bounds__(256) film_accumulate_kernel(CameraDev cam, Ren
     if (idx >= (uint64_t)n_lt * 64u) return;
     const uint32_t pit = (uint32_t)(idx & 63u);
     const uint32_t lt = lt0 + (uint32_t)(idx >> 6);
-    const uint32_t tile = lt * rp.tile_ranks + rp.tile_rank;
+    uint32_t tile = lt * rp.tile_ranks + rp.tile_rank, n_before = rp.sample0;
+    bool first = fp.first != 0u;
+    if (rp.tile_list) {  // the pass's tile lt, and what it holds: an empty tile's first chunk sum is assigned
+        const TileRef t = rp.tile_list[lt];
+        tile = t.tile, n_before = t.samples, first = t.samples == 0u;
+    }
     const uint32_t row = (tile / rp.tiles_x) * 8u + (pit >> 3);
     const uint32_t col = (tile % rp.tiles_x) * 8u + (pit & 7u);
     if (row >= cam.H || col >= cam.W) return;  // padding of an edge tile: its record stays zero
@@ -44,7 +49,7 @@ __global__ void __launch_bounds__(256) film_accumulate_kernel(CameraDev cam, Ren
     const uint32_t n = rp.nchunks, full = fp.full_chunks;
     Rec r;
     uint32_t k = 0;
-    if (fp.first) {  // the first chunk sum a pixel ever gets is assigned, as resolve_kernel's (a -0 stays -0)
+    if (first) {  // the first chunk sum a pixel ever gets is assigned, as resolve_kernel's (a -0 stays -0)
         r.x = src[0], r.y = src[1], r.z = src[2];
         const double c = (r.x + r.y) + r.z;
         r.s1 = full ? c : 0.0;
@@ -67,13 +72,14 @@ __global__ void __launch_bounds__(256) film_accumulate_kernel(CameraDev cam, Ren
     for (; k < n; k++, src += ITEM_STRIDE) add_chunk(r, src[0], src[1], src[2], k < full);
     rec[FILM_SX * 64u] = r.x, rec[FILM_SY * 64u] = r.y, rec[FILM_SZ * 64u] = r.z;
     rec[FILM_S1 * 64u] = r.s1, rec[FILM_S2 * 64u] = r.s2;
+    if (pit == 0u) fp.tile_n[tile] = n_before + rp.spp;  // (pixel 0 of a tile of the frame is in the image)
 }
 
 // One pass over the records of the rank's tiles.  Per lane the tests of main.rs:81-87 on the running sum and the
 // converged predicate of include/rayrs_hip.h (no square root, no division: the count is exactly reproducible); per wave a
 // ballot and a population count, and one atomic add per counter that has anything to add.
-__global__ void __launch_bounds__(256) film_status_kernel(CameraDev cam, RenderDev rp, const double* recs, double m, double tau2,
-                                                          FilmCounts* counts) {
+__global__ void __launch_bounds__(256) film_status_kernel(CameraDev cam, RenderDev rp, const double* recs, const uint32_t* tile_n,
+                                                          uint32_t c, double tau2, FilmCounts* counts) {
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t pit = (uint32_t)(idx & 63u);
     const uint32_t lt = (uint32_t)(idx >> 6);
@@ -81,6 +87,8 @@ __global__ void __launch_bounds__(256) film_status_kernel(CameraDev cam, RenderD
     const uint32_t tile = valid ? lt * rp.tile_ranks + rp.tile_rank : 0u;
     const uint32_t row = (tile / rp.tiles_x) * 8u + (pit >> 3);
     const uint32_t col = (tile % rp.tiles_x) * 8u + (pit & 7u);
+    const uint32_t n_t = valid ? tile_n[tile] : 0u;
+    const double m = (double)(n_t / c);  // the tile's own full chunks
     valid = valid && row < cam.H && col < cam.W;
     bool nan = false, neg = false, unconverged = false, nonfinite = false;
     if (valid) {
@@ -100,18 +108,21 @@ __global__ void __launch_bounds__(256) film_status_kernel(CameraDev cam, RenderD
         if (b_neg) atomicAdd(&counts->neg_pixels, (unsigned long long)__popcll(b_neg));
         if (b_unc) atomicAdd(&counts->unconverged, (unsigned long long)__popcll(b_unc));
         if (b_nf) atomicAdd(&counts->nonfinite, (unsigned long long)__popcll(b_nf));
+        if (n_t) atomicMax(&counts->max_samples, n_t);
     }
 }
 
 // The frame as it stands: one lane per pixel in image order, so that the frame is written in whole lines; a lane reads
 // its record's three sums where its tile keeps them (eight lanes share a 64-byte run of a plane).
-__global__ void __launch_bounds__(256) film_read_kernel(CameraDev cam, uint32_t tiles_x, const double* recs, double inv_n,
+__global__ void __launch_bounds__(256) film_read_kernel(CameraDev cam, uint32_t tiles_x, const double* recs, const uint32_t* tile_n,
                                                         uint32_t out_format, void* out) {
     const uint64_t pix = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= (uint64_t)cam.W * cam.H) return;
     const uint32_t row = (uint32_t)(pix / cam.W), col = (uint32_t)(pix % cam.W);
     const uint32_t tile = (row >> 3) * tiles_x + (col >> 3);
     const double* rec = recs + (size_t)tile * FILM_TILE_DOUBLES + ((row & 7u) * 8u + (col & 7u));
+    const uint32_t n_t = tile_n[tile];
+    const double inv_n = n_t ? 1.0 / (double)n_t : 0.0;  // (a tile without samples holds zeros: +0)
     const double x = rec[FILM_SX * 64u] * inv_n, y = rec[FILM_SY * 64u] * inv_n, z = rec[FILM_SZ * 64u] * inv_n;  // main.rs:89
     if (out_format == RAYRS_OUT_F64) {
         double* dst = reinterpret_cast<double*>(out) + pix * 3;
@@ -122,6 +133,76 @@ __global__ void __launch_bounds__(256) film_read_kernel(CameraDev cam, uint32_t 
     }
 }
 
+// The tiles an adaptive pass samples.  One wave per tile of the share, reading the records as film_status_kernel does and
+// the same predicate with the tile's own M_t: one ballot says whether any in-image pixel is unconverged (a non-finite
+// pixel is not, and padding never is).  The flag also needs room for n more samples below the cap.
+__global__ void __launch_bounds__(256) film_select_kernel(CameraDev cam, RenderDev rp, const double* recs, const uint32_t* tile_n,
+                                                          uint32_t c, uint32_t n, uint32_t cap, double tau2, uint32_t all,
+                                                          uint32_t* flags) {
+    const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t pit = (uint32_t)(idx & 63u);
+    const uint32_t lt = (uint32_t)(idx >> 6);
+    const bool in_share = idx < (uint64_t)rp.n_local_tiles * 64u;  // wave-uniform
+    const uint32_t tile = in_share ? lt * rp.tile_ranks + rp.tile_rank : 0u;
+    const uint32_t row = (tile / rp.tiles_x) * 8u + (pit >> 3);
+    const uint32_t col = (tile % rp.tiles_x) * 8u + (pit & 7u);
+    const uint32_t n_t = in_share ? tile_n[tile] : 0u;
+    const double m = (double)(n_t / c);
+    bool unconverged = false;
+    if (in_share && !all && row < cam.H && col < cam.W) {
+        const double* rec = recs + (size_t)tile * FILM_TILE_DOUBLES + pit;
+        const double s1 = rec[FILM_S1 * 64u], s2 = rec[FILM_S2 * 64u];
+        const bool nonfinite = !(__builtin_isfinite(s1) && __builtin_isfinite(s2));
+        const double s11 = s1 * s1;
+        const bool converged = m >= 2.0 && m * s2 - s11 <= ((tau2 * s11)) * (m - 1.0);
+        unconverged = !nonfinite && !converged;
+    }
+    const unsigned long long b_unc = __ballot(unconverged);
+    if (in_share && pit == 0u) flags[lt] = (all || (b_unc != 0ull && (uint64_t)n_t + n <= cap)) ? 1u : 0u;
+}
+
+// flags -> the list of (tile, N_t) in ascending tile order, by a scan: where a tile lands in the list, and with it the
+// numbering of the pass's items, depends on the film's state alone, never on the order in which waves finish.  One
+// workgroup walks the share 1024 tiles at a time: a ballot and a population count per wave, the sixteen wave totals
+// through LDS, the running base in a register.  (65536 tiles, a 2048 x 2048 frame, are 64 steps.)
+constexpr uint32_t COMPACT_THREADS = 1024;
+__global__ void __launch_bounds__(COMPACT_THREADS) film_compact_kernel(RenderDev rp, const uint32_t* flags, const uint32_t* tile_n,
+                                                                       TileRef* list, FilmSelect* sel) {
+    __shared__ uint32_t s_wave[COMPACT_THREADS / 64u];
+    __shared__ uint32_t s_max;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    if (tid == 0u) s_max = 0u;
+    uint32_t base = 0u, most = 0u;
+    for (uint32_t start = 0u; start < rp.n_local_tiles; start += COMPACT_THREADS) {
+        const uint32_t lt = start + tid;
+        const bool valid = lt < rp.n_local_tiles;
+        const uint32_t tile = valid ? lt * rp.tile_ranks + rp.tile_rank : 0u;
+        const uint32_t n_t = valid ? tile_n[tile] : 0u;
+        const bool flagged = valid && flags[lt] != 0u;
+        most = n_t > most ? n_t : most;
+        const unsigned long long b = __ballot(flagged);
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        if ((tid & 63u) == 0u) s_wave[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t before = 0u, total = 0u;
+        for (uint32_t w = 0u; w < COMPACT_THREADS / 64u; w++) {
+            const uint32_t v = s_wave[w];
+            before += w < wave ? v : 0u;
+            total += v;
+        }
+        if (flagged) {  // (base + before + below < the flagged tiles so far <= n_local_tiles: inside the list)
+            TileRef t;
+            t.tile = tile, t.samples = n_t;
+            list[base + before + below] = t;
+        }
+        base += total;
+        __syncthreads();
+    }
+    atomicMax(&s_max, most);
+    __syncthreads();
+    if (tid == 0u) sel->n_active = base, sel->max_samples = s_max;
+}
+
 hipError_t launch_film_accumulate(const CameraDev& cam, const RenderDev& rp, const FilmPassDev& fp, uint32_t lt0, uint32_t n_lt,
                                   hipStream_t stream) {
     const uint64_t n = (uint64_t)n_lt * 64u;
@@ -130,21 +211,35 @@ hipError_t launch_film_accumulate(const CameraDev& cam, const RenderDev& rp, con
     return hipGetLastError();
 }
 
-hipError_t launch_film_status(const CameraDev& cam, const RenderDev& rp, const double* rec, uint64_t m, double tau2,
-                              FilmCounts* counts, hipStream_t stream) {
+hipError_t launch_film_status(const CameraDev& cam, const RenderDev& rp, const double* rec, const uint32_t* tile_n, uint32_t c,
+                              double tau2, FilmCounts* counts, hipStream_t stream) {
     const uint64_t n = (uint64_t)rp.n_local_tiles * 64u;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(film_status_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, cam, rp, rec, (double)m, tau2,
+    hipLaunchKernelGGL(film_status_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, cam, rp, rec, tile_n, c, tau2,
                        counts);
     return hipGetLastError();
 }
 
-hipError_t launch_film_read(const CameraDev& cam, uint32_t tiles_x, const double* rec, double inv_n, uint32_t out_format,
+hipError_t launch_film_read(const CameraDev& cam, uint32_t tiles_x, const double* rec, const uint32_t* tile_n, uint32_t out_format,
                             void* out, hipStream_t stream) {
     const uint64_t n = (uint64_t)cam.W * cam.H;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(film_read_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, cam, tiles_x, rec, inv_n,
+    hipLaunchKernelGGL(film_read_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, cam, tiles_x, rec, tile_n,
                        out_format, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_film_select(const CameraDev& cam, const RenderDev& rp, const double* rec, const uint32_t* tile_n, uint32_t c,
+                              uint32_t n, uint32_t cap, double tau2, uint32_t all, uint32_t* flags, TileRef* list, FilmSelect* sel,
+                              hipStream_t stream) {
+    const uint64_t threads = (uint64_t)rp.n_local_tiles * 64u;
+    if (threads) {
+        hipLaunchKernelGGL(film_select_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, cam, rp, rec, tile_n, c, n,
+                           cap, tau2, all, flags);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(film_compact_kernel, dim3(1), dim3(COMPACT_THREADS), 0, stream, rp, flags, tile_n, list, sel);
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <vector>
 
 #include "../../include/rayrs_hip.h"
 #include "film.h"
@@ -15,9 +16,10 @@
 using namespace rayrs;
 
 namespace {
-// The checkpoint image: this header, then the film's records as they lie on the device (film.h).
+// The checkpoint image: this header, then the film's records as they lie on the device (film.h), then N_t of every tile
+// of the frame, row-major, 4 bytes each (version 2; version 1 had no per-tile counts).
 constexpr uint32_t STATE_MAGIC = 0x4d4c4652u;  // "RFLM"
-constexpr uint32_t STATE_VERSION = 1;
+constexpr uint32_t STATE_VERSION = 2;
 struct StateHeader {
     uint32_t magic, version;
     uint32_t x_pixels, y_pixels;
@@ -25,7 +27,7 @@ struct StateHeader {
     uint64_t seed;
     uint32_t tile_rank, tile_ranks;
     uint32_t fast_traversal, closed;
-    uint64_t samples, full_chunks, rays, paths;
+    uint64_t samples, full_chunks, rays, paths;  // samples: the largest N_t
     uint64_t record_bytes;
 };
 static_assert(sizeof(StateHeader) == 88, "StateHeader");
@@ -37,14 +39,23 @@ struct rayrs_film {
     rayrs_camera camera = {};
     rayrs_film_params prm = {};    // as given, defaults filled in
     uint32_t tiles_x = 0, tiles_y = 0;
-    uint64_t samples = 0, full_chunks = 0, rays = 0, paths = 0;
+    // samples: N of a uniform film; once the tiles differ, the largest N_t as last read from the device (film_max_samples)
+    uint64_t samples = 0, rays = 0, paths = 0;
+    bool uniform = true;  // every tile of the share holds `samples` samples (no adaptive pass has left any out yet)
     bool closed = false;
     DevBuf d_rec;     // film.h: 40 bytes per pixel of the frame's tiles
+    DevBuf d_tile_n;  // N_t: one word per tile of the frame, 0 outside the share
+    DevBuf d_flags;   // an adaptive pass: one word per tile of the share (film_select_kernel) ...
+    DevBuf d_list;    // ... and the list made of them, one TileRef per tile of the share at most
+    DevBuf d_select;  // one FilmSelect
     DevBuf d_counts;  // one FilmCounts
     DevBuf d_out;     // the frame rayrs_film_read copies out, grown on demand
     PinnedBuf h_stage;
     bool has_stage = false;
     size_t record_bytes() const { return (size_t)tiles_x * tiles_y * FILM_TILE_DOUBLES * sizeof(double); }
+    size_t n_tiles() const { return (size_t)tiles_x * tiles_y; }
+    size_t count_bytes() const { return n_tiles() * sizeof(uint32_t); }
+    uint64_t full_chunks() const { return samples / prm.sample_chunk; }
     StateHeader header() const {
         StateHeader h;
         std::memset(&h, 0, sizeof(h));
@@ -53,7 +64,7 @@ struct rayrs_film {
         h.sample_chunk = prm.sample_chunk, h.max_bounces = prm.max_bounces, h.seed = prm.seed;
         h.tile_rank = prm.tile_rank, h.tile_ranks = prm.tile_ranks, h.fast_traversal = prm.fast_traversal;
         h.closed = closed ? 1u : 0u;
-        h.samples = samples, h.full_chunks = full_chunks, h.rays = rays, h.paths = paths;
+        h.samples = samples, h.full_chunks = full_chunks(), h.rays = rays, h.paths = paths;
         h.record_bytes = record_bytes();
         return h;
     }
@@ -78,6 +89,52 @@ static int film_enter(rayrs_film* f) {
         HIP_TRY(hipStreamSynchronize(s->last_stream));
         s->pending = false;
     }
+    return RAYRS_OK;
+}
+
+// Makes the list of a pass over some of the share's tiles (film.hip): those an adaptive pass of n samples selects at tau
+// under the cap, or all of them.  One word of the result comes back through the scene's pinned words -- the list's length,
+// which the pass is planned from, or (all) the largest N_t, which bounds the pass -- and that copy is the only wait.
+static int film_select(rayrs_film* f, uint32_t n, uint32_t cap, double tau, bool all, uint32_t* word) {
+    const RenderDev rp = film_tiles(f);
+    HIP_TRY(f->d_flags.reserve((size_t)rp.n_local_tiles * sizeof(uint32_t)));
+    HIP_TRY(f->d_list.reserve((size_t)rp.n_local_tiles * sizeof(TileRef)));
+    const CameraDev cam = make_camera_dev(&f->camera);
+    FilmSelect* sel = f->d_select.as<FilmSelect>();
+    HIP_TRY(launch_film_select(cam, rp, f->d_rec.as<double>(), f->d_tile_n.as<uint32_t>(), f->prm.sample_chunk, n, cap, tau * tau,
+                               all ? 1u : 0u, f->d_flags.as<uint32_t>(), f->d_list.as<TileRef>(), sel, nullptr));
+    uint32_t* h_word = f->scene->pool.h_live.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(h_word, all ? &sel->max_samples : &sel->n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    *word = *h_word;
+    return RAYRS_OK;
+}
+
+// One pass of n samples: over the list film_select has just made (n_list tiles, each from its own N_t), or, n_list == 0,
+// over the whole share of a uniform film from `samples`.
+static int film_pass(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_render_stats* st) {
+    const uint32_t c = film->prm.sample_chunk;
+    rayrs_render_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.spp = n;  // the pass's window: its chunks are chunks N/c .. of the one-shot frame, N being a multiple of c
+    p.max_bounces = film->prm.max_bounces;
+    p.seed = film->prm.seed;
+    p.sample_chunk = c;  // (c >= n: the window is one chunk, full if n == c)
+    p.tile_rank = film->prm.tile_rank, p.tile_ranks = film->prm.tile_ranks;
+    p.out_format = RAYRS_OUT_F64;
+    p.fast_traversal = film->prm.fast_traversal;
+    FilmPassDev fp;
+    std::memset(&fp, 0, sizeof(fp));
+    fp.rec = film->d_rec.as<double>();
+    fp.first = film->samples == 0 ? 1u : 0u;
+    fp.full_chunks = n / c;
+    fp.tile_n = film->d_tile_n.as<uint32_t>();
+    fp.list = n_list ? film->d_list.as<TileRef>() : nullptr;
+    fp.n_list = n_list;
+    // the accumulate kernel follows the pass's path rounds on the same stream: no host round trip in between
+    RAYRS_TRY(render_enqueue(film->scene, &film->camera, &p, n_list ? 0u : (uint32_t)film->samples, &fp, nullptr, nullptr));
+    RAYRS_TRY(rayrs_render_finish(film->scene, st));
+    film->rays += st->rays, film->paths += st->paths;
     return RAYRS_OK;
 }
 
@@ -113,6 +170,9 @@ int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayr
     HIP_TRY(hipSetDevice(scene->device));
     HIP_TRY(f->d_rec.reserve(f->record_bytes()));
     HIP_TRY(hipMemset(f->d_rec.as<>(), 0, f->record_bytes()));
+    HIP_TRY(f->d_tile_n.reserve(f->count_bytes()));
+    HIP_TRY(hipMemset(f->d_tile_n.as<>(), 0, f->count_bytes()));
+    HIP_TRY(f->d_select.reserve(sizeof(FilmSelect)));
     HIP_TRY(f->d_counts.reserve(sizeof(FilmCounts)));
     *out = f.release();
     return RAYRS_OK;
@@ -130,32 +190,57 @@ int rayrs_film_render(rayrs_film* film, uint32_t n, rayrs_render_stats* pass_sta
     RAYRS_GUARDED({
     if (!film || n == 0 || film->closed) return RAYRS_INVALID_ARG;
     const uint32_t c = film->prm.sample_chunk;
-    if (film->samples > SLOT_SAMPLE_MASK || n > SLOT_SAMPLE_MASK - (uint32_t)film->samples) return RAYRS_UNSUPPORTED;
+    if (n > SLOT_SAMPLE_MASK) return RAYRS_UNSUPPORTED;
+    if (film->uniform && (film->samples > SLOT_SAMPLE_MASK || n > SLOT_SAMPLE_MASK - (uint32_t)film->samples)) return RAYRS_UNSUPPORTED;
     RAYRS_TRY(film_enter(film));
-    rayrs_render_params p;
-    std::memset(&p, 0, sizeof(p));
-    p.spp = n;  // the pass's window: its chunks are chunks N/c .. of the one-shot frame, N being a multiple of c
-    p.max_bounces = film->prm.max_bounces;
-    p.seed = film->prm.seed;
-    p.sample_chunk = c;  // (c >= n: the window is one chunk, full if n == c)
-    p.tile_rank = film->prm.tile_rank, p.tile_ranks = film->prm.tile_ranks;
-    p.out_format = RAYRS_OUT_F64;
-    p.fast_traversal = film->prm.fast_traversal;
-    FilmPassDev fp;
-    fp.rec = film->d_rec.as<double>();
-    fp.first = film->samples == 0 ? 1u : 0u;
-    fp.full_chunks = n / c;
-    // the accumulate kernel follows the pass's path rounds on the same stream: no host round trip in between
-    RAYRS_TRY(render_enqueue(film->scene, &film->camera, &p, (uint32_t)film->samples, &fp, nullptr, nullptr));
+    uint32_t n_list = 0;
+    if (!film->uniform) {  // every tile of the share from its own N_t: a pass over the list of them all
+        uint32_t most = 0;
+        RAYRS_TRY(film_select(film, n, 0u, 0.0, true, &most));
+        film->samples = most;
+        if (most > SLOT_SAMPLE_MASK || n > SLOT_SAMPLE_MASK - most) return RAYRS_UNSUPPORTED;
+        n_list = film_tiles(film).n_local_tiles;
+    }
     rayrs_render_stats st;
-    RAYRS_TRY(rayrs_render_finish(film->scene, &st));
+    RAYRS_TRY(film_pass(film, n, n_list, &st));
     film->samples += n;
-    film->full_chunks += n / c;
-    film->rays += st.rays, film->paths += st.paths;
     if (n % c != 0u) film->closed = true;
     if (pass_stats) *pass_stats = st;
     return RAYRS_OK;
     })
+}
+
+int rayrs_film_render_adaptive(rayrs_film* film, uint32_t n, double tau, uint32_t max_tile_samples, uint64_t* active_tiles,
+                               rayrs_render_stats* pass_stats) {
+    RAYRS_GUARDED({
+    if (!film || n == 0 || film->closed || !(tau >= 0.0) || !std::isfinite(tau)) return RAYRS_INVALID_ARG;
+    if (n % film->prm.sample_chunk != 0u) return RAYRS_INVALID_ARG;
+    RAYRS_TRY(film_enter(film));
+    const uint32_t cap = max_tile_samples != 0u && max_tile_samples < SLOT_SAMPLE_MASK ? max_tile_samples : SLOT_SAMPLE_MASK;
+    uint32_t active = 0;
+    RAYRS_TRY(film_select(film, n, cap, tau, false, &active));
+    rayrs_render_stats st;
+    std::memset(&st, 0, sizeof(st));
+    if (active != 0u) {
+        RAYRS_TRY(film_pass(film, n, active, &st));
+        if (film->uniform && active == film_tiles(film).n_local_tiles) film->samples += n;  // every tile went on
+        else film->uniform = false;
+    }
+    if (active_tiles) *active_tiles = active;
+    if (pass_stats) *pass_stats = st;
+    return RAYRS_OK;
+    })
+}
+
+uint64_t rayrs_film_tile_samples(rayrs_film* film, uint32_t* out, uint64_t cap) {
+    if (!film) return 0;
+    const uint64_t n = film->n_tiles();
+    const uint64_t take = cap < n ? cap : n;
+    if (out && take) {
+        if (film_enter(film) != RAYRS_OK) return 0;
+        if (film->d_tile_n.download(out, (size_t)take * sizeof(uint32_t)) != hipSuccess) return 0;
+    }
+    return n;
 }
 
 int rayrs_film_read(rayrs_film* film, uint32_t out_format, void* out_host) {
@@ -166,7 +251,7 @@ int rayrs_film_read(rayrs_film* film, uint32_t out_format, void* out_host) {
     const size_t bytes = (size_t)film->camera.x_pixels * film->camera.y_pixels * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4);
     HIP_TRY(film->d_out.reserve(bytes));
     const CameraDev cam = make_camera_dev(&film->camera);
-    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), 1.0 / (double)film->samples, out_format,
+    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), out_format,
                              film->d_out.as<>(), nullptr));
     HIP_TRY(film->d_out.download(out_host, bytes));
     return RAYRS_OK;
@@ -180,11 +265,13 @@ int rayrs_film_status_get(rayrs_film* film, double tau, rayrs_film_status* out) 
     const CameraDev cam = make_camera_dev(&film->camera);
     const RenderDev rp = film_tiles(film);
     HIP_TRY(hipMemsetAsync(film->d_counts.as<>(), 0, sizeof(FilmCounts), nullptr));
-    HIP_TRY(launch_film_status(cam, rp, film->d_rec.as<double>(), film->full_chunks, tau * tau, film->d_counts.as<FilmCounts>(), nullptr));
+    HIP_TRY(launch_film_status(cam, rp, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), film->prm.sample_chunk, tau * tau,
+                               film->d_counts.as<FilmCounts>(), nullptr));
     FilmCounts c;
     HIP_TRY(film->d_counts.download(&c, sizeof(c)));
+    if (!film->uniform) film->samples = c.max_samples;  // the largest N_t
     std::memset(out, 0, sizeof(*out));
-    out->samples = film->samples, out->full_chunks = film->full_chunks;
+    out->samples = film->samples, out->full_chunks = film->full_chunks();
     out->rays = film->rays, out->paths = film->paths;
     out->nan_pixels = c.nan_pixels, out->neg_pixels = c.neg_pixels;
     out->unconverged = c.unconverged, out->nonfinite = c.nonfinite;
@@ -193,13 +280,26 @@ int rayrs_film_status_get(rayrs_film* film, double tau, rayrs_film_status* out) 
     })
 }
 
-uint64_t rayrs_film_state_bytes(const rayrs_film* film) { return film ? sizeof(StateHeader) + film->record_bytes() : 0; }
+uint64_t rayrs_film_state_bytes(const rayrs_film* film) {
+    return film ? sizeof(StateHeader) + film->record_bytes() + film->count_bytes() : 0;
+}
 
 int rayrs_film_state_get(rayrs_film* film, void* out_host, uint64_t cap) {
     RAYRS_GUARDED({
     if (!film || !out_host || cap < rayrs_film_state_bytes(film)) return RAYRS_INVALID_ARG;
     RAYRS_TRY(film_enter(film));
     RAYRS_TRY(film_stage(film));
+    uint8_t* counts = static_cast<uint8_t*>(out_host) + sizeof(StateHeader) + film->record_bytes();
+    HIP_TRY(film->d_tile_n.download(counts, film->count_bytes()));
+    if (!film->uniform) {
+        uint32_t most = 0;
+        for (size_t t = 0; t < film->n_tiles(); t++) {
+            uint32_t n_t;
+            std::memcpy(&n_t, counts + t * sizeof(uint32_t), sizeof(n_t));
+            most = n_t > most ? n_t : most;
+        }
+        film->samples = most;
+    }
     const StateHeader h = film->header();
     uint8_t* dst = static_cast<uint8_t*>(out_host);
     std::memcpy(dst, &h, sizeof(h));
@@ -226,13 +326,30 @@ int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes) 
         h.max_bounces != mine.max_bounces || h.seed != mine.seed || h.tile_rank != mine.tile_rank ||
         h.tile_ranks != mine.tile_ranks || h.fast_traversal != mine.fast_traversal)
         return RAYRS_INVALID_ARG;
-    if (h.record_bytes != mine.record_bytes || bytes != sizeof(StateHeader) + h.record_bytes) return RAYRS_INVALID_ARG;
+    if (h.record_bytes != mine.record_bytes || bytes != rayrs_film_state_bytes(film)) return RAYRS_INVALID_ARG;
     // counters that no sequence of passes leaves behind: not this library's image
     const uint64_t c = mine.sample_chunk;
     if (h.closed > 1u || h.samples > SLOT_SAMPLE_MASK || h.full_chunks != h.samples / c || (h.closed == 0u) != (h.samples % c == 0u))
         return RAYRS_INVALID_ARG;
+    // ... and per-tile counts that none leaves: nothing outside the share; in an open film whole chunks, in a closed one
+    // the same short chunk everywhere; the largest is the header's
+    std::vector<uint32_t> counts(film->n_tiles());
+    std::memcpy(counts.data(), static_cast<const uint8_t*>(in_host) + sizeof(h) + h.record_bytes, film->count_bytes());
+    uint32_t most = 0;
+    bool same = true;
+    for (size_t t = 0; t < counts.size(); t++) {
+        const bool mine_t = t % mine.tile_ranks == mine.tile_rank;
+        if (!mine_t && counts[t] != 0u) return RAYRS_INVALID_ARG;
+        if (!mine_t) continue;
+        if (counts[t] > SLOT_SAMPLE_MASK || counts[t] % c != h.samples % c) return RAYRS_INVALID_ARG;
+        if ((counts[t] == 0u) != (h.samples == 0u)) return RAYRS_INVALID_ARG;  // a pass on an empty film takes every tile
+        most = counts[t] > most ? counts[t] : most;
+        same = same && counts[t] == h.samples;
+    }
+    if (most != h.samples && !counts.empty() && mine.tile_rank < counts.size()) return RAYRS_INVALID_ARG;
     RAYRS_TRY(film_enter(film));
     RAYRS_TRY(film_stage(film));
+    HIP_TRY(film->d_tile_n.upload(counts.data(), film->count_bytes()));
     const uint8_t* src = static_cast<const uint8_t*>(in_host) + sizeof(h);
     uint8_t* dst = film->d_rec.as<uint8_t>();
     for (size_t at = 0, total = film->record_bytes(); at < total; at += STAGE_BYTES) {
@@ -241,7 +358,8 @@ int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes) 
         HIP_TRY(hipMemcpyAsync(dst + at, film->h_stage.as<void>(), piece, hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipStreamSynchronize(nullptr));
     }
-    film->samples = h.samples, film->full_chunks = h.full_chunks, film->rays = h.rays, film->paths = h.paths;
+    film->samples = h.samples, film->rays = h.rays, film->paths = h.paths;
+    film->uniform = same;
     film->closed = h.closed != 0u;
     return RAYRS_OK;
     })

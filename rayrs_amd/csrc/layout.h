@@ -166,6 +166,13 @@ struct Counters {
 #endif
 };
 
+// One tile of an adaptive film pass (film.hip film_compact_kernel): the tile of the frame, and the samples it holds so far,
+// which is where its window of the pass begins.
+struct alignas(8) TileRef {
+    uint32_t tile, samples;
+};
+static_assert(sizeof(TileRef) == 8, "TileRef");
+
 struct RenderDev {
     uint32_t spp, max_bounces;
     uint64_t seed;
@@ -187,6 +194,10 @@ struct RenderDev {
     unsigned long long* next_item;  // device-wide item counter
     Counters* counters;
     void* out;
+    // null: local tile lt is tile lt * tile_ranks + tile_rank and every window begins at sample0.  Else n_local_tiles
+    // entries (a film pass over some of the share's tiles, each from its own sample count): local tile lt is
+    // tile_list[lt].tile and its window begins at tile_list[lt].samples (item_geometry below)
+    const TileRef* tile_list;
 };
 
 // n / d and n % d for a launch-constant d with 1/d at hand: the quotient of the f64 product is
@@ -211,11 +222,16 @@ RR_LAYOUT_FN void item_geometry(const RenderDev& rp, uint32_t item, uint32_t& ro
                                 uint32_t& s_end) {
     const uint32_t pit = item & 63u;
     uint32_t chunk, tile_col;
-    const uint32_t tile = udiv_by(item >> 6, rp.nchunks, rp.inv_nchunks, chunk) * rp.tile_ranks + rp.tile_rank;
+    const uint32_t lt = udiv_by(item >> 6, rp.nchunks, rp.inv_nchunks, chunk);
+    uint32_t tile = lt * rp.tile_ranks + rp.tile_rank, s0 = rp.sample0;
+    if (rp.tile_list) {  // (uniform over the launch; an item that is none reads entry 0: local_pool.hip asks before it knows)
+        const TileRef t = rp.tile_list[lt < rp.n_local_tiles ? lt : 0u];
+        tile = t.tile, s0 = t.samples;
+    }
     row = udiv_by(tile, rp.tiles_x, rp.inv_tiles_x, tile_col) * 8u + (pit >> 3);
     col = tile_col * 8u + (pit & 7u);
-    const uint32_t w_end = rp.sample0 + rp.spp;  // the window's end (at most 2^30 - 1: checked at launch)
-    s_begin = rp.sample0 + chunk * rp.chunk;
+    const uint32_t w_end = s0 + rp.spp;  // the window's end (at most 2^30 - 1: checked at launch)
+    s_begin = s0 + chunk * rp.chunk;
     s_end = s_begin + rp.chunk < w_end ? s_begin + rp.chunk : w_end;
 }
 

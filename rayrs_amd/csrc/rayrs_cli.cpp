@@ -126,7 +126,7 @@ int main(int argc, char** argv) {
     uint32_t max_bounces = 50;  // main.rs:77
     uint32_t fast_traversal = 0;  // rayrs_render_params.fast_traversal: 0 = the reference's visit set by construction
     uint32_t sample_chunk = 0, pass = 0;
-    bool chunk_given = false, until_noise = false;
+    bool chunk_given = false, until_noise = false, adaptive = false;
     double tau = 0.0;
     std::vector<int> devices;
     int i = 2;
@@ -136,8 +136,14 @@ int main(int argc, char** argv) {
         if (end != argv[i] && *end == '\0' && v > 0) spp = (uint32_t)v;  // unwrap_or_else(|_| SPP), main.rs:133
         i++;
     }
-    for (; i + 1 < argc; i += 2) {
+    for (; i < argc; i += 2) {
         const std::string opt = argv[i];
+        if (opt == "--adaptive") {  // the one option without a value
+            adaptive = true;
+            i--;
+            continue;
+        }
+        if (i + 1 >= argc) break;
         if (opt == "--scene") scene_name = argv[i + 1];
         else if (opt == "--seed") seed = std::strtoull(argv[i + 1], nullptr, 0);
         else if (opt == "--device") device = std::atoi(argv[i + 1]);
@@ -170,6 +176,10 @@ int main(int argc, char** argv) {
     const bool use_film = pass != 0 || until_noise;
     if (use_film && !devices.empty()) {
         std::fprintf(stderr, "--pass / --until-noise render through a film, which is single-device: use --device, not --gpus / --devices\n");
+        return 1;
+    }
+    if (adaptive && !until_noise) {
+        std::fprintf(stderr, "--adaptive samples the tiles that are still noisy at a tau: give --until-noise TAU\n");
         return 1;
     }
     if (use_film && (!chunk_given || sample_chunk == 0)) sample_chunk = 4;
@@ -258,6 +268,38 @@ int main(int argc, char** argv) {
         rayrs_film_status fs;
         std::memset(&fs, 0, sizeof fs);
         uint32_t done = 0;
+        // --adaptive: passes over the tiles that still hold an unconverged pixel, none beyond spp samples, until every
+        // finite pixel is converged or no tile is left to take a pass (rayrs_amd.render_until(adaptive=True))
+        while (adaptive) {
+            if ((st = rayrs_film_status_get(film, tau, &fs)) != RAYRS_OK) return fail("film status", st);
+            if (fs.samples > 0 && fs.unconverged == 0) break;
+            uint64_t active = 0;
+            rayrs_render_stats ps;
+            if (spp < pass) break;
+            if ((st = rayrs_film_render_adaptive(film, pass, tau, spp, &active, &ps)) != RAYRS_OK) return fail("film pass", st);
+            if (active == 0) break;
+            if ((st = rayrs_film_read(film, RAYRS_OUT_F32, rgb.data())) != RAYRS_OK) return fail("film read", st);
+            if ((st = rayrs_film_status_get(film, tau, &fs)) != RAYRS_OK) return fail("film status", st);
+            std::printf("Pass: %llu active tiles, at most %llu samples, %llu pixels unconverged, %llu not finite\n",
+                        (unsigned long long)active, (unsigned long long)fs.samples, (unsigned long long)fs.unconverged,
+                        (unsigned long long)fs.nonfinite);
+            if (write_files(false) != RAYRS_OK) return 1;
+        }
+        if (adaptive) {
+            std::vector<uint32_t> per_tile((size_t)rayrs_film_tile_samples(film, nullptr, 0));
+            rayrs_film_tile_samples(film, per_tile.data(), per_tile.size());
+            const uint32_t tiles_x = (cam.x_pixels + 7u) / 8u;
+            uint64_t lo = ~0ull, hi = 0, sum = 0;
+            for (uint32_t r = 0; r < cam.y_pixels; r++)
+                for (uint32_t c = 0; c < cam.x_pixels; c++) {
+                    const uint64_t v = per_tile[(size_t)(r / 8u) * tiles_x + c / 8u];
+                    lo = v < lo ? v : lo, hi = v > hi ? v : hi, sum += v;
+                }
+            std::printf("Samples per pixel: min %llu, mean %.3f, max %llu\n", (unsigned long long)lo,
+                        (double)sum / ((double)cam.x_pixels * cam.y_pixels), (unsigned long long)hi);
+            if (hi == 0) return fail("film pass", RAYRS_INVALID_ARG);  // (spp below one pass: nothing was rendered)
+            done = spp;
+        }
         while (done < spp) {
             const uint32_t n = spp - done < pass ? spp - done : pass;  // (a short last pass closes the film: it is the last)
             rayrs_render_stats ps;
@@ -270,7 +312,7 @@ int main(int argc, char** argv) {
             if (done < spp && write_files(false) != RAYRS_OK) return 1;
             if (until_noise && fs.unconverged == 0) break;
         }
-        std::printf("Samples per pixel: %u\n", done);
+        if (!adaptive) std::printf("Samples per pixel: %u\n", done);
         stats.rays = fs.rays, stats.paths = fs.paths, stats.nan_pixels = fs.nan_pixels, stats.neg_pixels = fs.neg_pixels;
         rayrs_film_destroy(film);
     } else if (scenes.size() == 1)

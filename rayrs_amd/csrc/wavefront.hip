@@ -196,7 +196,7 @@ RR_DEV void wave_atomic_add(unsigned long long* dst, unsigned long long v) {
 }
 
 // ---- kernel arguments, re-read where they are used ----
-// The gen, hit and miss kernels take (SceneDev, CameraDev, RenderDev, WfDev) by value: 488 bytes of scalars, loop invariants
+// The gen, hit and miss kernels take (SceneDev, CameraDev, RenderDev, WfDev) by value: 496 bytes of scalars, loop invariants
 // all.  Left to itself the compiler loads them at the kernel's entry, runs out of scalar registers in the hit kernel's loop,
 // parks them in lanes of a vector register and fetches each back with a v_readlane -- a VECTOR instruction per dword -- where
 // it is used: 330 of them in next_sample and finish_rays.  The arguments sit in memory already (the kernarg segment, served
