@@ -489,12 +489,71 @@ uint64_t rayrs_film_state_bytes(const rayrs_film* film);
 int rayrs_film_state_get(rayrs_film* film, void* out_host, uint64_t cap);
 int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes);
 
+/* ---- first-hit feature buffers and a feature-guided denoiser: something to look at while a film converges, and the
+ * depth / normal / albedo / object planes external denoisers and compositing want.  Neither touches a path kernel: the
+ * features of a sample depend on (scene, camera, seed, pixel, sample index) only, so a kernel of their own recomputes them.
+ *
+ * FEATURES.  For pixel (row, col) and sample index s the primary ray is made exactly as a render makes it -- the path key
+ * of (seed, pixel, s), then Camera::generate_primary_ray (lib.rs:202) with the render's flipped indices -- and the scene is
+ * queried ONCE with z_near, z_far and the requested walk (the camera rule of rayrs_render_params.fast_traversal applies as
+ * it does for a render).  Per-sample values on a hit of object obj at t:
+ *     coverage_s = 1.0      depth_s = t
+ *     normal_s   = obj.geom.normal(r.point(t)): what radiance hands to Material::evaluate (lib.rs:528-529), NOT flipped
+ *                  towards the viewer
+ *     albedo_s   = the rayrs_material.color the object was created with; (0,0,0) for RAYRS_MAT_NO_REFLECT
+ * and on a miss all four are +0.  Per pixel and plane the sum over s = 0 .. F-1 is SEQUENTIAL, in sample order, the first
+ * value assigned and the rest added, f64, unfused; the output is sum * (1.0 / (double)F).  (A sequential sum: there is no
+ * chunk rule.)  The `object` plane (u32) holds the object hit by SAMPLE 0, in insertion order as rayrs_scene_export_bvh's
+ * prim_object numbers them; a miss is 0xFFFFFFFF.  Pixels outside a tile share read +0 and 0xFFFFFFFF.
+ *
+ * DENOISER.  An edge-avoiding a-trous filter (Dammertz et al. 2010), specified to the operation.  Inputs per pixel: colour
+ * c (3 f64), normal n, albedo a, depth z; scalars: L levels and kn, ka, kz, kc >= 0, the reciprocals of squared sigmas (the
+ * filter never divides by a sigma); constants h[0] = 3/8, h[1] = 1/4, h[2] = 1/16.  Level k = 0 .. L-1 has step 2^k and
+ * kc_k = kc * 4^k, formed on the host, reads the colour of level k-1 (level 0: the input) and the same features.  For pixel
+ * p = (y, x):
+ *   - if a component of c_p is not finite, c'_p = c_p;
+ *   - else num = (0,0,0), den = 0, and for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = (y + dy*step, x + dx*step):
+ *       skip q if it lies outside the image; skip q if a component of c_q is not finite;
+ *       dn = ((n_p.x-n_q.x)^2 + (n_p.y-n_q.y)^2) + (n_p.z-n_q.z)^2, da likewise on a, dc likewise on this level's c,
+ *       dz = (z_p-z_q)*(z_p-z_q);
+ *       e = ((dn*kn + da*ka) + dz*kz) + dc*kc_k;   skip q if e is not finite;
+ *       w = (h[|dy|]*h[|dx|]) * rr_exp(-e)   (include/rayrs_numeric.h);
+ *       num += c_q * w per component (the product first, then the sum); den += w;
+ *   - if den == 0 (the pixel's own features are NaN), c'_p = c_p; else c'_p = num / den, an f64 division per component.
+ * A feature plane that is absent (NULL) contributes no term.  No albedo demodulation, no variance-guided weight, nothing
+ * temporal.
+ *
+ * Refusals, all decided before the device is touched: RAYRS_INVALID_ARG for samples = 0 or >= 2^30, levels outside 1 .. 16,
+ * a k that is negative or not finite, fast_traversal > 1, a bad tile share, rayrs_film_denoise on an empty film or on a film
+ * with tile_ranks > 1 (the filter needs a pixel's neighbours); RAYRS_UNSUPPORTED for an image side > 65535; then
+ * RAYRS_NO_DEVICE for a host-only scene. */
+
+/* planes may be NULL = not wanted; host buffers; normal, albedo: H*W*3 f64, depth, coverage: H*W f64, object: H*W u32 */
+int rayrs_render_features(rayrs_scene* scene, const rayrs_camera* camera, uint32_t samples, uint64_t seed, uint32_t tile_rank,
+                          uint32_t tile_ranks, uint32_t fast_traversal, double* normal, double* albedo, double* depth,
+                          double* coverage, uint32_t* object);
+/* The same with the film's camera, seed, share and walk; independent of how many samples the film holds.  A film keeps the
+ * features it made last on the device (8 doubles and a word per pixel), keyed by `samples`; the checkpoint image carries
+ * none of it, and neither this call nor rayrs_film_denoise changes anything a later pass, rayrs_film_read,
+ * rayrs_film_status_get or rayrs_film_state_get returns. */
+int rayrs_film_features(rayrs_film* film, uint32_t samples, double* normal, double* albedo, double* depth, double* coverage,
+                        uint32_t* object);
+/* The frame rayrs_film_read(RAYRS_OUT_F64) returns, filtered on the device with the normal, albedo and depth of
+ * `feature_samples` samples; out_host as rayrs_film_read's, RAYRS_OUT_F32 being the f64 result converted at the store. */
+int rayrs_film_denoise(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz, double kc,
+                       uint32_t out_format, void* out_host);
+/* The filter alone, on any frame, on HIP device `device`: host f64 buffers (color, out: h*w*3; normal, albedo: h*w*3;
+ * depth: h*w), feature planes may be NULL. */
+int rayrs_image_denoise(int device, uint32_t w, uint32_t h, const double* color, const double* normal, const double* albedo,
+                        const double* depth, uint32_t levels, double kn, double ka, double kz, double kc, double* out);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
  * rayrs_render_stats.hot_*, rayrs_scene_export_hot_tree, rayrs_obj_load_spheres.  7: the progressive film (rayrs_film_*, rayrs_film_params,
  * rayrs_film_status; no existing struct changed); still 7 with rayrs_film_render_adaptive and rayrs_film_tile_samples: entry points
- * were added, no struct or existing call changed.  The layout table below begins with this
+ * were added, no struct or existing call changed; and with rayrs_render_features, rayrs_film_features, rayrs_film_denoise and
+ * rayrs_image_denoise, for the same reason.  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

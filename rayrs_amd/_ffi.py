@@ -25,6 +25,7 @@ SYMBOLS = [
     "rayrs_film_create", "rayrs_film_destroy", "rayrs_film_render", "rayrs_film_read", "rayrs_film_status_get",
     "rayrs_film_state_bytes", "rayrs_film_state_get", "rayrs_film_state_set",
     "rayrs_film_render_adaptive", "rayrs_film_tile_samples",
+    "rayrs_render_features", "rayrs_film_features", "rayrs_film_denoise", "rayrs_image_denoise",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -202,6 +203,15 @@ def lib():
     L.rayrs_film_render_adaptive.argtypes = [vp, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(RenderStats)]
     L.rayrs_film_tile_samples.argtypes = [vp, vp, C.c_uint64]
     L.rayrs_film_tile_samples.restype = C.c_uint64
+    # (an older build of the same ABI version, loaded through RAYRS_HIP_LIB by the same-box A/B scripts, has no features or
+    # denoiser: it loads, and a call of one of the four raises AttributeError -- build() asks the tree's library for every symbol)
+    for name, args in (("rayrs_render_features", [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  vp, vp, vp, vp, vp]),
+                       ("rayrs_film_features", [vp, C.c_uint32, vp, vp, vp, vp, vp]),
+                       ("rayrs_film_denoise", [vp, C.c_uint32, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, vp]),
+                       ("rayrs_image_denoise", [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32] + [C.c_double] * 4 + [vp])):
+        if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
+            getattr(L, name).argtypes = args
     L.rayrs_test_math.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
     L.rayrs_test_rng.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
     L.rayrs_test_intersect.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp]
@@ -224,6 +234,8 @@ def lib():
     L.rayrs_ppm_save.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32]
     L.rayrs_png_save.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32]
     for name in SYMBOLS:
+        if not hasattr(L, name) and "RAYRS_HIP_LIB" in os.environ:
+            continue
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rayrs_strerror",):
             fn.restype = C.c_int

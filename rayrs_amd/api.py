@@ -453,6 +453,78 @@ def render_finish(scene: Scene) -> dict:
     return st.as_dict()
 
 
+# ---- first-hit features and the feature-guided filter (include/rayrs_hip.h FEATURES, DENOISER)
+
+# Starting points for the filter's sigmas, chosen by eye on the docs/renders scenes at 16 to 64 samples; nothing more.  A
+# sigma is the distance at which a tap's weight has fallen to 1/e: of unit normals, of albedo, of depth as a fraction of
+# the scene's root-box diagonal, of colour at level 0 (each level halves the colour sigma: kc_k = kc * 4^k).
+SIGMA_NORMAL = 0.25
+SIGMA_ALBEDO = 0.1
+SIGMA_DEPTH_FRACTION = 0.02
+SIGMA_COLOR = 0.6
+
+
+def _k(sigma) -> float:
+    """1 / sigma^2; None or inf: the term is switched off."""
+    if sigma is None or sigma == float("inf"):
+        return 0.0
+    sigma = float(sigma)
+    return 1.0 / (sigma * sigma)
+
+
+def scene_sigma_depth(scene: "Scene") -> float:
+    """The default depth sigma: SIGMA_DEPTH_FRACTION of the scene's root-box diagonal."""
+    b = scene.info()["root_box"]
+    dx, dy, dz = b[1] - b[0], b[3] - b[2], b[5] - b[4]
+    diag = float(np.sqrt(dx * dx + dy * dy + dz * dz))
+    return SIGMA_DEPTH_FRACTION * diag if np.isfinite(diag) and diag > 0.0 else None
+
+
+def _feature_planes(H, W):
+    return {"normal": np.zeros((H, W, 3)), "albedo": np.zeros((H, W, 3)), "depth": np.zeros((H, W)),
+            "coverage": np.zeros((H, W)), "object": np.zeros((H, W), dtype=np.uint32)}
+
+
+def render_features(scene: Scene, camera: Camera, samples: int = 16, seed: int = 0x5EED, tile_rank: int = 0,
+                    tile_ranks: int = 1, fast_traversal: bool = False) -> dict:
+    """First-hit feature buffers of the view, averaged over `samples` samples per pixel: a dict of "normal" and "albedo"
+    (H, W, 3) f64, "depth" and "coverage" (H, W) f64 and "object" (H, W) uint32 -- the object sample 0 hit, in insertion
+    order, 0xFFFFFFFF for none.  Pixels outside the tile share read 0 and 0xFFFFFFFF."""
+    out = _feature_planes(camera.y_pixels(), camera.x_pixels())
+    _ffi.check(scene._L.rayrs_render_features(scene._h, C.byref(camera.desc), int(samples), int(seed), int(tile_rank),
+                                              int(tile_ranks), int(fast_traversal), out["normal"].ctypes.data,
+                                              out["albedo"].ctypes.data, out["depth"].ctypes.data, out["coverage"].ctypes.data,
+                                              out["object"].ctypes.data), "rayrs_render_features")
+    return out
+
+
+def denoise(color, normal=None, albedo=None, depth=None, levels: int = 5, sigma_normal=SIGMA_NORMAL,
+            sigma_albedo=SIGMA_ALBEDO, sigma_depth=None, sigma_color=SIGMA_COLOR, device: int = 0):
+    """The edge-avoiding a-trous filter of include/rayrs_hip.h (DENOISER) on any (H, W, 3) frame, on the GPU; returns
+    the filtered f64 frame.  A feature plane that is None contributes no term; a sigma that is None or inf switches its
+    term off (sigma_depth has no default here: depth has no scale without a scene)."""
+    color = np.ascontiguousarray(color, dtype=np.float64)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise ValueError("color must be (H, W, 3)")
+    H, W = color.shape[:2]
+
+    def plane(a, shape):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"feature plane must be {shape}")
+        return a
+
+    normal, albedo, depth = plane(normal, (H, W, 3)), plane(albedo, (H, W, 3)), plane(depth, (H, W))
+    out = np.zeros((H, W, 3))
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    _ffi.check(_ffi.lib().rayrs_image_denoise(int(device), W, H, color.ctypes.data, ptr(normal), ptr(albedo), ptr(depth),
+                                              int(levels), _k(sigma_normal), _k(sigma_albedo), _k(sigma_depth),
+                                              _k(sigma_color), out.ctypes.data), "rayrs_image_denoise")
+    return out
+
+
 class Film:
     """A progressive film (include/rayrs_hip.h rayrs_film_*): samples are added to it pass by pass, and after passes
     that add up to N samples image() is, bit for bit, render(scene, camera, N, sample_chunk=sample_chunk) with the same
@@ -504,6 +576,29 @@ class Film:
         """The frame as it stands: (y_pixels, x_pixels, 3), f32 or f64 (a tile's sum over its own sample count)."""
         out = np.zeros((self.camera.y_pixels(), self.camera.x_pixels(), 3), dtype=np.float64 if out_f64 else np.float32)
         _ffi.check(self._L.rayrs_film_read(self._h, 1 if out_f64 else 0, out.ctypes.data), "rayrs_film_read")
+        return out
+
+    def features(self, samples: int = 16) -> dict:
+        """render_features() with the film's camera, seed, tile share and walk; independent of the samples the film holds,
+        and without effect on them."""
+        out = _feature_planes(self.camera.y_pixels(), self.camera.x_pixels())
+        _ffi.check(self._L.rayrs_film_features(self._h, int(samples), out["normal"].ctypes.data, out["albedo"].ctypes.data,
+                                               out["depth"].ctypes.data, out["coverage"].ctypes.data, out["object"].ctypes.data),
+                   "rayrs_film_features")
+        return out
+
+    def denoised(self, levels: int = 5, feature_samples: int = 16, sigma_normal=SIGMA_NORMAL, sigma_albedo=SIGMA_ALBEDO,
+                 sigma_depth="scene", sigma_color=SIGMA_COLOR, out_f64: bool = False):
+        """image(out_f64=True) filtered on the device with the normal, albedo and depth of `feature_samples` samples
+        (include/rayrs_hip.h DENOISER); f32, or f64 with out_f64.  The film itself is unchanged.  The default sigmas
+        are starting points chosen by eye (SIGMA_* above), sigma_depth a fraction of the scene's root-box diagonal; None or
+        inf switches a term off."""
+        if isinstance(sigma_depth, str):
+            sigma_depth = scene_sigma_depth(self.scene)
+        out = np.zeros((self.camera.y_pixels(), self.camera.x_pixels(), 3), dtype=np.float64 if out_f64 else np.float32)
+        _ffi.check(self._L.rayrs_film_denoise(self._h, int(feature_samples), int(levels), _k(sigma_normal), _k(sigma_albedo),
+                                              _k(sigma_depth), _k(sigma_color), 1 if out_f64 else 0, out.ctypes.data),
+                   "rayrs_film_denoise")
         return out
 
     def status(self, tau: float = 0.0) -> dict:

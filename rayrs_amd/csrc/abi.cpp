@@ -619,7 +619,7 @@ extern "C++" SceneDev rayrs::make_scene_dev(const rayrs_scene* s, bool exact) {
 // is thousands of small-primitive sizes long and makes the bet all the same -- the fast walk stays a bet.
 constexpr double RAYRS_FAR_DIAGONALS = 8.0;
 constexpr double RAYRS_FAR_PRIMITIVES = 4096.0;
-static bool camera_is_far(const rayrs_scene* s, const rayrs_camera* c) {
+extern "C++" bool rayrs::camera_is_far(const rayrs_scene* s, const rayrs_camera* c) {
     const double* b = s->flat.root_box;
     double d2 = 0.0, e2 = 0.0;
     for (int a = 0; a < 3; a++) {

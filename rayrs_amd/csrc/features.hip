@@ -1,0 +1,166 @@
+// features.hip -- first-hit feature buffers and the feature-guided a-trous filter (include/rayrs_hip.h FEATURES and
+// DENOISER).  Neither kernel is part of a render: the features of a sample depend on (scene, camera, seed, pixel, sample
+// index) only, so they are recomputed here from the device functions the path kernels use (device_path.h) instead of
+// being carried through the path rounds, whose kernels sit at their register bound.
+#include <hip/hip_runtime.h>
+
+#include "device_path.h"
+#include "feature_kernels.h"
+
+namespace rayrs {
+
+// One wave per 8x8 tile of the share, one lane per pixel, as the film kernels map them: a wave's primary rays leave
+// through neighbouring pixels and walk the same records.  A lane runs its pixel's samples in sample order with the eight
+// running sums in registers -- the first sample's values assigned, the others added, f64, nothing fused -- and stores
+// sum * (1 / samples).  The lanes of an edge tile's padding trace the nearest pixel of the image beside them and store
+// nothing, so that every lane of a wave is in every query (the triangle and hot-group tests vote across the wave).
+template <bool COMPACT>
+__global__ void __launch_bounds__(256) features_kernel(SceneDev sc, CameraDev cam, FeatureDev fd) {
+    extern __shared__ uint32_t lds_stack[];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // sc.stack_lds entries of the stack in LDS, the rest in the strip `spill` (as in the traversal kernel)
+    const LaneStack stack{lds_stack + (size_t)wave * (sc.stack_lds + 1u) * 64u + lane, fd.spill + i, sc.stack_lds,
+                          gridDim.x * blockDim.x};
+    const uint32_t lt = (uint32_t)(i >> 6);
+    if (lt >= fd.n_local_tiles) return;  // (wave-uniform)
+    const uint32_t tile = lt * fd.tile_ranks + fd.tile_rank;
+    const uint32_t row = (tile / fd.tiles_x) * 8u + (lane >> 3);
+    const uint32_t col = (tile % fd.tiles_x) * 8u + (lane & 7u);
+    const bool inside = row < cam.H && col < cam.W;
+    const uint32_t r = row < cam.H ? row : cam.H - 1u, c = col < cam.W ? col : cam.W - 1u;
+    const uint64_t pixel = (uint64_t)r * cam.W + c;
+    V3 n_sum = mk(0.0, 0.0, 0.0), a_sum = mk(0.0, 0.0, 0.0);
+    double z_sum = 0.0, cov_sum = 0.0;
+    uint32_t first_prim = 0xffffffffu;
+    for (uint32_t s = 0; s < fd.samples; s++) {
+        Rng rng{rr_path_key(fd.seed, pixel, (uint64_t)s), 0};
+        V3 o, d;
+        primary_ray(cam, cam.H - r, cam.W - c, rng, o, d);  // image origin is upper left, camera origin lower right (main.rs:74-75)
+        double t = 0.0;
+        uint32_t prim = 0xffffffffu;
+        WorkCount wc{0, 0, 0, 0, 0};
+        const bool hit = sc.exact ? bvh_intersect<COMPACT, false, true>(sc, o, d, stack, t, prim, wc)
+                                  : bvh_intersect<COMPACT, false, false>(sc, o, d, stack, t, prim, wc);
+        V3 n = mk(0.0, 0.0, 0.0), a = mk(0.0, 0.0, 0.0);
+        double z = 0.0, cov = 0.0;
+        if (hit) {
+            const PrimRec<COMPACT> rec = load_prim<COMPACT>(sc.prims, prim);
+            const V3 position = v_add(o, v_scale(d, t));
+            n = prim_normal<COMPACT>(rec, position);  // what radiance hands to Material::evaluate (lib.rs:528-529): not flipped
+            const SurfaceDev* surf = sc.surfaces + (rec.tag() >> 8);
+            const int32_t kind = surf->kind;
+            const double* col3 = kind >= RAYRS_MAT_COOK_TORRANCE && kind <= RAYRS_MAT_COOK_TORRANCE_GLASS ? surf->ct_color : surf->color;
+            a = kind == RAYRS_MAT_NO_REFLECT ? mk(0.0, 0.0, 0.0) : mk(col3[0], col3[1], col3[2]);
+            z = t, cov = 1.0;
+        }
+        if (s == 0u) {
+            n_sum = n, a_sum = a, z_sum = z, cov_sum = cov;
+            first_prim = hit ? prim : 0xffffffffu;
+        } else {
+            n_sum = v_add(n_sum, n), a_sum = v_add(a_sum, a);
+            z_sum += z, cov_sum += cov;
+        }
+    }
+    if (!inside) return;
+    const size_t pix = (size_t)row * cam.W + col;
+    const double inv = fd.inv_samples;
+    fd.normal[3 * pix] = n_sum.x * inv, fd.normal[3 * pix + 1] = n_sum.y * inv, fd.normal[3 * pix + 2] = n_sum.z * inv;
+    fd.albedo[3 * pix] = a_sum.x * inv, fd.albedo[3 * pix + 1] = a_sum.y * inv, fd.albedo[3 * pix + 2] = a_sum.z * inv;
+    fd.depth[pix] = z_sum * inv;
+    fd.coverage[pix] = cov_sum * inv;
+    fd.prim[pix] = first_prim;
+}
+
+// One level of the edge-avoiding a-trous filter (Dammertz et al. 2010) exactly as include/rayrs_hip.h DENOISER states it:
+// 5 x 5 taps `step` pixels apart, the weight of a tap the B3-spline's times rr_exp(-e), e the feature and colour
+// distances in the header's operation order.  One lane per pixel, a wave 64 consecutive pixels of a row (its 25 colour
+// reads are 25 runs of 1536 bytes); neighbouring rows and the next level's wider taps meet in L2, not in LDS.
+constexpr uint32_t ATROUS_BX = 64, ATROUS_BY = 4;
+
+RR_DEV bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
+RR_DEV double dist2(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+__global__ void __launch_bounds__(ATROUS_BX * ATROUS_BY) atrous_kernel(AtrousDev a) {
+    const uint32_t x = blockIdx.x * ATROUS_BX + threadIdx.x;
+    const uint32_t y = blockIdx.y * ATROUS_BY + threadIdx.y;
+    if (x >= a.w || y >= a.h) return;
+    const size_t p = (size_t)y * a.w + x;
+    const double cx = a.color[3 * p], cy = a.color[3 * p + 1], cz = a.color[3 * p + 2];
+    double ox = cx, oy = cy, oz = cz;
+    if (finite3(cx, cy, cz)) {
+        const bool has_n = a.normal != nullptr, has_a = a.albedo != nullptr, has_z = a.depth != nullptr;  // (uniform)
+        double npx = 0.0, npy = 0.0, npz = 0.0, apx = 0.0, apy = 0.0, apz = 0.0, zp = 0.0;
+        if (has_n) npx = a.normal[3 * p], npy = a.normal[3 * p + 1], npz = a.normal[3 * p + 2];
+        if (has_a) apx = a.albedo[3 * p], apy = a.albedo[3 * p + 1], apz = a.albedo[3 * p + 2];
+        if (has_z) zp = a.depth[p];
+        constexpr double h[3] = {0.375, 0.25, 0.0625};
+        double nx = 0.0, ny = 0.0, nz = 0.0, den = 0.0;
+        const int step = (int)a.step;  // at most 2^15: y + 2 * step stays far inside an int
+#pragma unroll
+        for (int dy = -2; dy <= 2; dy++) {
+            const int qy = (int)y + dy * step;
+            if (qy < 0 || qy >= (int)a.h) continue;
+#pragma unroll
+            for (int dx = -2; dx <= 2; dx++) {
+                const int qx = (int)x + dx * step;
+                if (qx < 0 || qx >= (int)a.w) continue;
+                const size_t q = (size_t)qy * a.w + (uint32_t)qx;
+                const double qcx = a.color[3 * q], qcy = a.color[3 * q + 1], qcz = a.color[3 * q + 2];
+                if (!finite3(qcx, qcy, qcz)) continue;
+                // an absent plane's term is +0: every term is >= +0 or NaN, so adding it changes no bit of e
+                double dn = 0.0, da = 0.0, dz = 0.0;
+                if (has_n) dn = dist2(npx, npy, npz, a.normal[3 * q], a.normal[3 * q + 1], a.normal[3 * q + 2]);
+                if (has_a) da = dist2(apx, apy, apz, a.albedo[3 * q], a.albedo[3 * q + 1], a.albedo[3 * q + 2]);
+                if (has_z) {
+                    const double zq = a.depth[q];
+                    dz = (zp - zq) * (zp - zq);
+                }
+                const double dc = dist2(cx, cy, cz, qcx, qcy, qcz);
+                const double e = ((dn * a.kn + da * a.ka) + dz * a.kz) + dc * a.kc;
+                if (!__builtin_isfinite(e)) continue;
+                const double w = (h[dy < 0 ? -dy : dy] * h[dx < 0 ? -dx : dx]) * rr_exp(-e);
+                nx += qcx * w, ny += qcy * w, nz += qcz * w;
+                den += w;
+            }
+        }
+        if (den != 0.0) ox = nx / den, oy = ny / den, oz = nz / den;  // (den == 0: the pixel's own features are NaN)
+    }
+    if (a.out_f32) {
+        float* dst = reinterpret_cast<float*>(a.out) + 3 * p;  // image.rs:224-229
+        dst[0] = (float)ox, dst[1] = (float)oy, dst[2] = (float)oz;
+    } else {
+        double* dst = reinterpret_cast<double*>(a.out) + 3 * p;
+        dst[0] = ox, dst[1] = oy, dst[2] = oz;
+    }
+}
+
+hipError_t launch_features(bool compact, const SceneDev& sc, const CameraDev& cam, const FeatureDev& fd, hipStream_t stream) {
+    if (fd.n_local_tiles == 0u || fd.samples == 0u) return hipSuccess;
+    const uint32_t lds = 4u * 64u * (sc.stack_lds + 1u) * 4u;  // four waves' stacks, + the spare entry
+    const uint32_t blocks = (uint32_t)(features_threads(fd.n_local_tiles) / 256u);
+    if (compact) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&features_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        hipLaunchKernelGGL(features_kernel<true>, dim3(blocks), dim3(256), lds, stream, sc, cam, fd);
+    } else {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&features_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        hipLaunchKernelGGL(features_kernel<false>, dim3(blocks), dim3(256), lds, stream, sc, cam, fd);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_atrous(const AtrousDev& a, hipStream_t stream) {
+    if (a.w == 0u || a.h == 0u) return hipSuccess;
+    // (a.h <= 65535: the grid's y dimension holds it)
+    hipLaunchKernelGGL(atrous_kernel, dim3((a.w + ATROUS_BX - 1u) / ATROUS_BX, (a.h + ATROUS_BY - 1u) / ATROUS_BY),
+                       dim3(ATROUS_BX, ATROUS_BY), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace rayrs

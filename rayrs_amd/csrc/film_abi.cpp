@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rayrs_hip.h"
+#include "features_host.hpp"
 #include "film.h"
 #include "scene_internal.hpp"
 
@@ -52,6 +53,12 @@ struct rayrs_film {
     DevBuf d_out;     // the frame rayrs_film_read copies out, grown on demand
     PinnedBuf h_stage;
     bool has_stage = false;
+    // The features of the film's view (rayrs_film_features, rayrs_film_denoise), kept on the device under the sample count
+    // they were made with: they depend on the film's camera, seed, share and walk, never on the samples it holds.  Not
+    // part of the checkpoint image.
+    FeatureBufs feat;
+    uint32_t feat_samples = 0;  // 0 = none yet
+    DevBuf d_ping, d_pong;      // the filter's two colour buffers
     size_t record_bytes() const { return (size_t)tiles_x * tiles_y * FILM_TILE_DOUBLES * sizeof(double); }
     size_t n_tiles() const { return (size_t)tiles_x * tiles_y; }
     size_t count_bytes() const { return n_tiles() * sizeof(uint32_t); }
@@ -276,6 +283,52 @@ int rayrs_film_status_get(rayrs_film* film, double tau, rayrs_film_status* out) 
     out->nan_pixels = c.nan_pixels, out->neg_pixels = c.neg_pixels;
     out->unconverged = c.unconverged, out->nonfinite = c.nonfinite;
     out->closed = film->closed ? 1u : 0u;
+    return RAYRS_OK;
+    })
+}
+
+// the film's features for `samples` samples, made now unless the film holds them
+static int film_features(rayrs_film* f, uint32_t samples) {
+    if (f->feat_samples == samples) return RAYRS_OK;
+    f->feat_samples = 0;
+    RAYRS_TRY(features_run(f->scene, &f->camera, samples, f->prm.seed, f->prm.tile_rank, f->prm.tile_ranks, f->prm.fast_traversal,
+                           f->feat));
+    f->feat_samples = samples;
+    return RAYRS_OK;
+}
+
+int rayrs_film_features(rayrs_film* film, uint32_t samples, double* normal, double* albedo, double* depth, double* coverage,
+                        uint32_t* object) {
+    RAYRS_GUARDED({
+    if (!film) return RAYRS_INVALID_ARG;
+    RAYRS_TRY(features_check(&film->camera, samples, film->prm.tile_rank, film->prm.tile_ranks, film->prm.fast_traversal));
+    RAYRS_TRY(film_enter(film));
+    RAYRS_TRY(film_features(film, samples));
+    RAYRS_TRY(features_download(film->scene, &film->camera, film->feat, normal, albedo, depth, coverage, object));
+    return RAYRS_OK;
+    })
+}
+
+int rayrs_film_denoise(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz, double kc,
+                       uint32_t out_format, void* out_host) {
+    RAYRS_GUARDED({
+    if (!film || !out_host || film->samples == 0) return RAYRS_INVALID_ARG;
+    if (out_format != RAYRS_OUT_F32 && out_format != RAYRS_OUT_F64) return RAYRS_INVALID_ARG;
+    if (film->prm.tile_ranks > 1u) return RAYRS_INVALID_ARG;  // the filter needs a pixel's neighbours
+    RAYRS_TRY(denoise_check(levels, kn, ka, kz, kc));
+    RAYRS_TRY(features_check(&film->camera, feature_samples, film->prm.tile_rank, film->prm.tile_ranks, film->prm.fast_traversal));
+    RAYRS_TRY(film_enter(film));
+    RAYRS_TRY(film_features(film, feature_samples));
+    // the frame rayrs_film_read(RAYRS_OUT_F64) returns, left on the device
+    const uint32_t w = film->camera.x_pixels, h = film->camera.y_pixels;
+    HIP_TRY(film->d_out.reserve((size_t)w * h * 3 * sizeof(double)));
+    const CameraDev cam = make_camera_dev(&film->camera);
+    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), RAYRS_OUT_F64,
+                             film->d_out.as<>(), nullptr));
+    void* result = nullptr;
+    RAYRS_TRY(denoise_run(w, h, film->d_out.as<double>(), film->feat.normal.as<double>(), film->feat.albedo.as<double>(),
+                          film->feat.depth.as<double>(), levels, kn, ka, kz, kc, out_format, film->d_ping, film->d_pong, &result));
+    HIP_TRY(hipMemcpy(out_host, result, (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4), hipMemcpyDeviceToHost));
     return RAYRS_OK;
     })
 }

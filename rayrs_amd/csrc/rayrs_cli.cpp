@@ -2,6 +2,13 @@
 //
 //     rayrs hdri_path [spp] [--scene NAME] [--seed N] [--device N] [--max-bounces N] [--fast-traversal 0|1]
 //                           [--gpus N | --devices a,b,...] [--sample-chunk C] [--pass N] [--until-noise TAU]
+//                           [--denoise [LEVELS]] [--features]
+//
+// --denoise additionally writes <scene>_denoised.png and .hdr: the final frame (as f64) through the feature-guided a-trous
+// filter of include/rayrs_hip.h (DENOISER), LEVELS levels (default 5), with the normal, albedo and depth of 16 samples and
+// the starting-point sigmas of rayrs_amd/api.py (SIGMA_*).  --features additionally writes <scene>_normal.png
+// (0.5 n + 0.5, no gamma), <scene>_albedo.png and <scene>_depth.hdr.  <scene>.png and <scene>.hdr are the same bytes
+// with and without either.
 //
 // --sample-chunk C sums a pixel's samples in chunks of C (rayrs_render_params.sample_chunk; default 0: the reference's one
 // sequential sum).  --pass N renders through a progressive film (rayrs_film_*) in passes of N samples, rounded up to a
@@ -21,6 +28,7 @@
 // clamped/NaN/negative pixel counts.  The reference picks the scene by editing main();
 // --scene selects among the same functions of test_scenes.rs.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -128,6 +136,11 @@ int main(int argc, char** argv) {
     uint32_t sample_chunk = 0, pass = 0;
     bool chunk_given = false, until_noise = false, adaptive = false;
     double tau = 0.0;
+    bool want_denoise = false, want_features = false;
+    uint32_t denoise_levels = 5;
+    constexpr uint32_t FEATURE_SAMPLES = 16;
+    // starting points chosen by eye, as rayrs_amd/api.py SIGMA_*: normal, albedo, depth as a fraction of the root-box diagonal, colour
+    constexpr double SIGMA_NORMAL = 0.25, SIGMA_ALBEDO = 0.1, SIGMA_DEPTH_FRACTION = 0.02, SIGMA_COLOR = 0.6;
     std::vector<int> devices;
     int i = 2;
     if (i < argc && argv[i][0] != '-') {
@@ -141,6 +154,19 @@ int main(int argc, char** argv) {
         if (opt == "--adaptive") {  // the one option without a value
             adaptive = true;
             i--;
+            continue;
+        }
+        if (opt == "--features") {
+            want_features = true;
+            i--;
+            continue;
+        }
+        if (opt == "--denoise") {  // the level count is optional
+            want_denoise = true;
+            char* end = nullptr;
+            const unsigned long v = i + 1 < argc ? std::strtoul(argv[i + 1], &end, 10) : 0ul;
+            if (i + 1 < argc && end != argv[i + 1] && *end == '\0') denoise_levels = (uint32_t)v;
+            else i--;
             continue;
         }
         if (i + 1 >= argc) break;
@@ -239,8 +265,49 @@ int main(int argc, char** argv) {
     params.tile_ranks = 1;
     params.out_format = RAYRS_OUT_F32;
     params.fast_traversal = fast_traversal;
-    std::vector<float> rgb((size_t)cam.x_pixels * cam.y_pixels * 3, 0.f);
+    const size_t npix = (size_t)cam.x_pixels * cam.y_pixels;
+    std::vector<float> rgb(npix * 3, 0.f);
     std::vector<uint8_t> bytes(rgb.size());
+    // --denoise filters the f64 frame: a plain render is then asked for f64 and converted here, which is the conversion
+    // the f32 output format makes at its store -- the same <scene>.png and <scene>.hdr
+    std::vector<double> rgb64(want_denoise && !use_film ? npix * 3 : 0);
+    std::vector<float> extra(want_denoise || want_features ? npix * 3 : 0);
+    auto write_extra = [&](const char* suffix, double gamma, bool png) -> int {
+        const std::string name = scene_name + suffix + (png ? ".png" : ".hdr");
+        if (!png) return rayrs_hdr_save(name.c_str(), extra.data(), cam.x_pixels, cam.y_pixels);
+        uint64_t counts[3];
+        rayrs_image_to_bytes(extra.data(), cam.x_pixels, cam.y_pixels, gamma, bytes.data(), counts);
+        return rayrs_png_save(name.c_str(), bytes.data(), cam.x_pixels, cam.y_pixels);
+    };
+    double kn = 1.0 / (SIGMA_NORMAL * SIGMA_NORMAL), ka = 1.0 / (SIGMA_ALBEDO * SIGMA_ALBEDO), kc = 1.0 / (SIGMA_COLOR * SIGMA_COLOR), kz = 0.0;
+    {
+        rayrs_scene_info_t info;
+        if ((st = rayrs_scene_info(scene, &info)) != RAYRS_OK) return fail("scene info", st);
+        const double* b = info.root_box;
+        const double dx = b[1] - b[0], dy = b[3] - b[2], dz = b[5] - b[4];
+        const double diag = std::sqrt(dx * dx + dy * dy + dz * dz);
+        if (std::isfinite(diag) && diag > 0.0) {
+            const double sigma = SIGMA_DEPTH_FRACTION * diag;
+            kz = 1.0 / (sigma * sigma);
+        }
+    }
+    // the feature files, from the planes of FEATURE_SAMPLES samples
+    auto write_features = [&](const std::vector<double>& normal, const std::vector<double>& albedo, const std::vector<double>& depth) -> int {
+        int s;
+        for (size_t k = 0; k < npix * 3; k++) extra[k] = (float)(0.5 * normal[k] + 0.5);
+        if ((s = write_extra("_normal", 1.0, true)) != RAYRS_OK) return fail("normal png", s), s;
+        for (size_t k = 0; k < npix * 3; k++) extra[k] = (float)albedo[k];
+        if ((s = write_extra("_albedo", 1. / 2.2, true)) != RAYRS_OK) return fail("albedo png", s), s;
+        for (size_t k = 0; k < npix; k++) extra[3 * k] = extra[3 * k + 1] = extra[3 * k + 2] = (float)depth[k];
+        if ((s = write_extra("_depth", 1.0, false)) != RAYRS_OK) return fail("depth hdr", s), s;
+        return RAYRS_OK;
+    };
+    auto write_denoised = [&]() -> int {  // extra holds the filtered frame as f32
+        int s;
+        if ((s = write_extra("_denoised", 1. / 2.2, true)) != RAYRS_OK) return fail("denoised png", s), s;
+        if ((s = write_extra("_denoised", 1.0, false)) != RAYRS_OK) return fail("denoised hdr", s), s;
+        return RAYRS_OK;
+    };
     // <scene>.png (gamma 1/2.2) and <scene>.hdr from rgb; the counts of image.rs:218-220 once, for the final frame
     auto write_files = [&](bool final_frame) -> int {
         uint64_t counts[3];
@@ -314,11 +381,28 @@ int main(int argc, char** argv) {
         }
         if (!adaptive) std::printf("Samples per pixel: %u\n", done);
         stats.rays = fs.rays, stats.paths = fs.paths, stats.nan_pixels = fs.nan_pixels, stats.neg_pixels = fs.neg_pixels;
+        if (want_features) {
+            std::vector<double> normal(npix * 3), albedo(npix * 3), depth(npix);
+            if ((st = rayrs_film_features(film, FEATURE_SAMPLES, normal.data(), albedo.data(), depth.data(), nullptr, nullptr)) != RAYRS_OK)
+                return fail("film features", st);
+            if (write_features(normal, albedo, depth) != RAYRS_OK) return 1;
+        }
+        if (want_denoise) {
+            if ((st = rayrs_film_denoise(film, FEATURE_SAMPLES, denoise_levels, kn, ka, kz, kc, RAYRS_OUT_F32, extra.data())) != RAYRS_OK)
+                return fail("film denoise", st);
+            if (write_denoised() != RAYRS_OK) return 1;
+        }
         rayrs_film_destroy(film);
-    } else if (scenes.size() == 1)
-        st = rayrs_render(scene, &cam, &params, rgb.data(), &stats);
-    else
-        st = rayrs_render_multi(scenes.data(), (uint32_t)scenes.size(), &cam, &params, rgb.data(), &stats);
+    } else {
+        if (want_denoise) params.out_format = RAYRS_OUT_F64;
+        void* frame = want_denoise ? (void*)rgb64.data() : (void*)rgb.data();
+        if (scenes.size() == 1)
+            st = rayrs_render(scene, &cam, &params, frame, &stats);
+        else
+            st = rayrs_render_multi(scenes.data(), (uint32_t)scenes.size(), &cam, &params, frame, &stats);
+        if (want_denoise)
+            for (size_t k = 0; k < npix * 3; k++) rgb[k] = (float)rgb64[k];  // image.rs:224-229
+    }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (st != RAYRS_OK) return fail("render", st);
     if (stats.nan_pixels) std::fprintf(stderr, "NaN pixel detected\n");       // main.rs:81-83
@@ -327,6 +411,21 @@ int main(int argc, char** argv) {
     std::printf("Rays: %llu (%.1f Mray/s)\n", (unsigned long long)stats.rays, (double)stats.rays / secs / 1e6);
 
     if (write_files(true) != RAYRS_OK) return 1;
+    if (!use_film && (want_denoise || want_features)) {
+        std::vector<double> normal(npix * 3), albedo(npix * 3), depth(npix);
+        if ((st = rayrs_render_features(scene, &cam, FEATURE_SAMPLES, seed, 0, 1, fast_traversal, normal.data(), albedo.data(),
+                                        depth.data(), nullptr, nullptr)) != RAYRS_OK)
+            return fail("features", st);
+        if (want_features && write_features(normal, albedo, depth) != RAYRS_OK) return 1;
+        if (want_denoise) {
+            std::vector<double> out64(npix * 3);
+            if ((st = rayrs_image_denoise(devices[0], cam.x_pixels, cam.y_pixels, rgb64.data(), normal.data(), albedo.data(),
+                                          depth.data(), denoise_levels, kn, ka, kz, kc, out64.data())) != RAYRS_OK)
+                return fail("denoise", st);
+            for (size_t k = 0; k < npix * 3; k++) extra[k] = (float)out64[k];
+            if (write_denoised() != RAYRS_OK) return 1;
+        }
+    }
     for (rayrs_scene* sc : scenes) rayrs_scene_destroy(sc);
     return 0;
 }

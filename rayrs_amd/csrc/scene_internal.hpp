@@ -91,6 +91,8 @@ int scene_upload(rayrs_scene* s);
 // what a render hands its kernels, for the self tests too (abi.cpp)
 SceneDev make_scene_dev(const rayrs_scene* s, bool exact);
 CameraDev make_camera_dev(const rayrs_camera* c);
+// the camera rule of rayrs_render_params.fast_traversal: such a frame takes the default walk whatever it asked for (abi.cpp)
+bool camera_is_far(const rayrs_scene* s, const rayrs_camera* c);
 uint32_t trav_settings(const rayrs_scene* s, bool exact, uint32_t np, RenderDev& rp);
 constexpr size_t POOL_SLOT_BYTES = sizeof(PathSlot) + 4 * sizeof(double) + 1u;  // a slot record, its light entry, its state byte
 WfDev pool_wf(const DevBuf& block, uint32_t np, const DevBuf& ctl, uint32_t trav_blocks, const DevBuf& spill);

@@ -2,9 +2,9 @@
 
 usage: python scripts/kernel_disasm_diff.py OLD_DIR NEW_DIR [NAME ...]
 
-OLD_DIR / NEW_DIR hold kernels.o, wavefront.o and local_pool.o of two builds (e.g. a copy of rayrs_amd/csrc/*.o made
+OLD_DIR / NEW_DIR hold kernels.o, wavefront.o, local_pool.o and film.o of two builds (e.g. a copy of rayrs_amd/csrc/*.o made
 before a change, and rayrs_amd/csrc after `make`).  Every kernel whose symbol contains one of NAME (default: the kernels
-a render and rayrs_test_intersect run) is disassembled from both builds and compared instruction by instruction, with
+a render and rayrs_test_intersect run; `all`: every kernel of the four objects) is disassembled from both builds and compared instruction by instruction, with
 addresses, branch targets, pc-relative symbol offsets and the alignment padding behind a kernel's last instruction
 normalised away.  Exit status 1 when one of them differs."""
 import os
@@ -14,7 +14,7 @@ import sys
 import tempfile
 
 LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
-OBJECTS = ("kernels", "wavefront", "local_pool")
+OBJECTS = ("kernels", "wavefront", "local_pool", "film")
 DEFAULT = ("wf_init", "wf_gen", "wf_trav", "wf_hit", "wf_miss", "lp_path", "test_intersect")
 
 
@@ -55,7 +55,7 @@ def main():
             a = disassemble(os.path.join(old_dir, o + ".o"), tmp)
             b = disassemble(os.path.join(new_dir, o + ".o"), tmp)
             for k in sorted(set(a) | set(b)):
-                if not any(n in k for n in names):
+                if "all" not in names and not any(n in k for n in names):
                     continue
                 if a.get(k) == b.get(k):
                     same += 1
