@@ -520,8 +520,8 @@ int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes);
  *       w = (h[|dy|]*h[|dx|]) * rr_exp(-e)   (include/rayrs_numeric.h);
  *       num += c_q * w per component (the product first, then the sum); den += w;
  *   - if den == 0 (the pixel's own features are NaN), c'_p = c_p; else c'_p = num / den, an f64 division per component.
- * A feature plane that is absent (NULL) contributes no term.  No albedo demodulation, no variance-guided weight, nothing
- * temporal.
+ * A feature plane that is absent (NULL) contributes no term.  No albedo demodulation, nothing temporal; the weight that is
+ * guided by the film's own noise estimate is the GUIDED FILTER below.
  *
  * Refusals, all decided before the device is touched: RAYRS_INVALID_ARG for samples = 0 or >= 2^30, levels outside 1 .. 16,
  * a k that is negative or not finite, fast_traversal > 1, a bad tile share, rayrs_film_denoise on an empty film or on a film
@@ -547,13 +547,77 @@ int rayrs_film_denoise(rayrs_film* film, uint32_t feature_samples, uint32_t leve
 int rayrs_image_denoise(int device, uint32_t w, uint32_t h, const double* color, const double* normal, const double* albedo,
                         const double* depth, uint32_t levels, double kn, double ka, double kz, double kc, double* out);
 
+/* ---- the film's noise estimate per pixel, and an a-trous filter guided by it: the spatial half of SVGF (Schied et al.
+ * 2017).  The film's tiles differ in noise by construction after adaptive passes; here a tap's luminance difference is
+ * divided by the pixel's own estimated standard deviation, and the variance is carried through the levels so that later
+ * levels know how much noise is left.  Nothing here touches a path kernel, and there is no albedo demodulation.
+ *
+ * NOISE PLANE.  For pixel p in tile t of the film's share, with c the film's chunk, M = N_t / c (integer division) and
+ * m = (double)M, S1 and S2 the pixel's sums of NOISE above:
+ *   - outside the share: v = +0;
+ *   - M < 2, or S1 or S2 not finite: v = +infinity -- selected, never computed: no NaN is ever generated, so the plane's
+ *     bit patterns are comparable across machines;
+ *   - otherwise d = m*S2 - S1*S1; if d is not finite, v = +infinity; else if !(d > 0), v = +0; else
+ *       v = d / (((m*m)*(m-1.0)) * ((double)c*(double)c))
+ *     one f64 division, unfused, in this order.
+ * This is the batch-means variance of Y = (r+g)+b of the frame rayrs_film_read returns: the sample variance of the M chunk
+ * sums, over M for their mean, over c*c for the per-sample scale.  On a CLOSED film the short last chunk is in the mean
+ * (the frame) and not in the variance (S1, S2 and M count full chunks only).
+ *
+ * GUIDED FILTER.  Inputs per pixel: colour c (3 f64), variance v (1 f64: the variance of Y(c) = (c.x+c.y)+c.z), and the
+ * optional normal n, albedo a, depth z exactly as DENOISER has them; scalars: L levels and kn, ka, kz, kv >= 0; constants
+ * h[0] = 3/8, h[1] = 1/4, h[2] = 1/16, g[0] = 1/2, g[1] = 1/4 and RAYRS_GUIDED_EPS = 2^-33.  Level k = 0 .. L-1 has step
+ * 2^k and reads the colour AND the variance of level k-1 (level 0: the inputs) and the same features.  For pixel p = (y, x):
+ *   - if a component of c_p is not finite, c'_p = c_p and v'_p = v_p;
+ *   - else the prefiltered variance, over the 3 x 3 ADJACENT pixels (distance 1, not step): gs = 0, gw = 0, and for
+ *     dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), q = (y + dy, x + dx):
+ *       skip q if it lies outside the image; skip q if a component of c_q is not finite; skip q unless v_q >= 0 (which
+ *       drops NaN and negatives and keeps +infinity);
+ *       wt = g[|dy|]*g[|dx|];  gs += v_q*wt;  gw += wt;
+ *     r_p = (gw == 0) ? +0 : kv / (gs/gw + RAYRS_GUIDED_EPS) -- two divisions per pixel and level, none per tap;
+ *   - Yp = (c_p.x+c_p.y)+c_p.z, num = (0,0,0), den = 0, vs = 0, and for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner),
+ *     q = (y + dy*step, x + dx*step), the DENOISER order:
+ *       skip q if it lies outside the image; skip q if a component of c_q is not finite; skip q unless v_q >= 0;
+ *       dn, da, dz as DENOISER's;  Yq = (c_q.x+c_q.y)+c_q.z;  dl = Yp - Yq;
+ *       e = ((dn*kn + da*ka) + dz*kz) + (dl*dl)*r_p;   skip q if e is not finite;
+ *       w = (h[|dy|]*h[|dx|]) * rr_exp(-e);
+ *       num += c_q * w per component (the product first, then the sum); den += w;
+ *       ww = w*w;  vs += (ww == 0) ? +0 : v_q*ww   (the guard keeps 0 * infinity out);
+ *   - if den == 0 or den*den == 0, c'_p = c_p and v'_p = v_p; else c'_p = num / den per component and
+ *     v'_p = vs / (den*den).
+ * An absent feature plane contributes no term; there is no kc.  Two consequences: where every variance is +infinity,
+ * r_p = +0 everywhere and the colour output is, bit for bit, DENOISER's with kc = 0 -- so a film with fewer than two full
+ * chunks falls back to the purely feature-guided filter; and on a flat frame with uniform variance and no features one
+ * level multiplies an interior pixel's variance by (70/256)^2, the sum of the squared 5 x 5 weights.
+ *
+ * Refusals mirror rayrs_film_denoise and rayrs_image_denoise and are decided before the device is touched:
+ * RAYRS_INVALID_ARG for levels outside 1 .. 16, a k that is negative or not finite, a NULL colour, variance or out, an
+ * empty image, an empty film, a bad out_format, and for the filter on a film with tile_ranks > 1 (rayrs_film_noise accepts
+ * a share); RAYRS_UNSUPPORTED for an image side > 65535; then RAYRS_NO_DEVICE.  Neither film call changes anything a
+ * later pass, rayrs_film_read, rayrs_film_status_get or rayrs_film_state_get returns. */
+#define RAYRS_GUIDED_EPS 0x1p-33
+
+/* NOISE PLANE into a host buffer of y_pixels*x_pixels f64, row-major.  RAYRS_INVALID_ARG on an empty film. */
+int rayrs_film_noise(rayrs_film* film, double* variance_host);
+/* The frame rayrs_film_read(RAYRS_OUT_F64) returns and the plane rayrs_film_noise returns through GUIDED FILTER on the
+ * device, with the features of `feature_samples` samples; out_host as rayrs_film_denoise's; out_variance (may be NULL):
+ * the last level's variance, H*W f64. */
+int rayrs_film_denoise_guided(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz,
+                              double kv, uint32_t out_format, void* out_host, double* out_variance);
+/* The filter alone, on any frame, on HIP device `device`: host f64 buffers (color, out: h*w*3; variance: h*w; normal,
+ * albedo: h*w*3; depth: h*w); feature planes and out_variance (h*w) may be NULL. */
+int rayrs_image_denoise_guided(int device, uint32_t w, uint32_t h, const double* color, const double* variance,
+                               const double* normal, const double* albedo, const double* depth, uint32_t levels,
+                               double kn, double ka, double kz, double kv, double* out, double* out_variance);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
  * rayrs_render_stats.hot_*, rayrs_scene_export_hot_tree, rayrs_obj_load_spheres.  7: the progressive film (rayrs_film_*, rayrs_film_params,
  * rayrs_film_status; no existing struct changed); still 7 with rayrs_film_render_adaptive and rayrs_film_tile_samples: entry points
  * were added, no struct or existing call changed; and with rayrs_render_features, rayrs_film_features, rayrs_film_denoise and
- * rayrs_image_denoise, for the same reason.  The layout table below begins with this
+ * rayrs_image_denoise, for the same reason, and with rayrs_film_noise, rayrs_film_denoise_guided and
+ * rayrs_image_denoise_guided.  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

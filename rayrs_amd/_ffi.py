@@ -26,6 +26,7 @@ SYMBOLS = [
     "rayrs_film_state_bytes", "rayrs_film_state_get", "rayrs_film_state_set",
     "rayrs_film_render_adaptive", "rayrs_film_tile_samples",
     "rayrs_render_features", "rayrs_film_features", "rayrs_film_denoise", "rayrs_image_denoise",
+    "rayrs_film_noise", "rayrs_film_denoise_guided", "rayrs_image_denoise_guided",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -204,12 +205,16 @@ def lib():
     L.rayrs_film_tile_samples.argtypes = [vp, vp, C.c_uint64]
     L.rayrs_film_tile_samples.restype = C.c_uint64
     # (an older build of the same ABI version, loaded through RAYRS_HIP_LIB by the same-box A/B scripts, has no features or
-    # denoiser: it loads, and a call of one of the four raises AttributeError -- build() asks the tree's library for every symbol)
+    # denoiser: it loads, and a call of one of them raises AttributeError -- build() asks the tree's library for every symbol)
     for name, args in (("rayrs_render_features", [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   vp, vp, vp, vp, vp]),
                        ("rayrs_film_features", [vp, C.c_uint32, vp, vp, vp, vp, vp]),
                        ("rayrs_film_denoise", [vp, C.c_uint32, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, vp]),
-                       ("rayrs_image_denoise", [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32] + [C.c_double] * 4 + [vp])):
+                       ("rayrs_image_denoise", [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32] + [C.c_double] * 4 + [vp]),
+                       ("rayrs_film_noise", [vp, vp]),
+                       ("rayrs_film_denoise_guided", [vp, C.c_uint32, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, vp, vp]),
+                       ("rayrs_image_denoise_guided", [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32] + [C.c_double] * 4
+                        + [vp, vp])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     L.rayrs_test_math.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint64, vp]

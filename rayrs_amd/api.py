@@ -462,6 +462,9 @@ SIGMA_NORMAL = 0.25
 SIGMA_ALBEDO = 0.1
 SIGMA_DEPTH_FRACTION = 0.02
 SIGMA_COLOR = 0.6
+# The guided filter's luminance sigma, in estimated standard deviations of the pixel (kv = 1 / 16): SVGF's value (Schied et
+# al. 2017), a starting point and not tuned here.
+SIGMA_LUMINANCE = 4.0
 
 
 def _k(sigma) -> float:
@@ -523,6 +526,39 @@ def denoise(color, normal=None, albedo=None, depth=None, levels: int = 5, sigma_
                                               int(levels), _k(sigma_normal), _k(sigma_albedo), _k(sigma_depth),
                                               _k(sigma_color), out.ctypes.data), "rayrs_image_denoise")
     return out
+
+
+def denoise_guided(color, variance, normal=None, albedo=None, depth=None, levels: int = 5, sigma_normal=SIGMA_NORMAL,
+                   sigma_albedo=SIGMA_ALBEDO, sigma_depth=None, sigma_luminance=SIGMA_LUMINANCE, device: int = 0,
+                   return_variance: bool = False):
+    """The variance-guided a-trous filter of include/rayrs_hip.h (GUIDED FILTER) on any (H, W, 3) frame with the (H, W)
+    variance of its channel sums, on the GPU; returns the filtered f64 frame, or (frame, variance after the last level) with
+    return_variance.  Planes and sigmas as denoise(); sigma_luminance is in standard deviations of the pixel."""
+    color = np.ascontiguousarray(color, dtype=np.float64)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise ValueError("color must be (H, W, 3)")
+    H, W = color.shape[:2]
+
+    def plane(a, shape):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"plane must be {shape}")
+        return a
+
+    if variance is None:
+        raise ValueError("variance must be (H, W)")
+    variance = plane(variance, (H, W))
+    normal, albedo, depth = plane(normal, (H, W, 3)), plane(albedo, (H, W, 3)), plane(depth, (H, W))
+    out = np.zeros((H, W, 3))
+    out_var = np.zeros((H, W)) if return_variance else None
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    _ffi.check(_ffi.lib().rayrs_image_denoise_guided(int(device), W, H, color.ctypes.data, variance.ctypes.data, ptr(normal),
+                                                     ptr(albedo), ptr(depth), int(levels), _k(sigma_normal), _k(sigma_albedo),
+                                                     _k(sigma_depth), _k(sigma_luminance), out.ctypes.data, ptr(out_var)),
+               "rayrs_image_denoise_guided")
+    return (out, out_var) if return_variance else out
 
 
 class Film:
@@ -600,6 +636,33 @@ class Film:
                                               _k(sigma_depth), _k(sigma_color), 1 if out_f64 else 0, out.ctypes.data),
                    "rayrs_film_denoise")
         return out
+
+    def noise(self):
+        """The film's noise estimate per pixel, (y_pixels, x_pixels) f64 (include/rayrs_hip.h NOISE PLANE): the batch-means
+        variance of the channel sum of the frame image() returns; +inf where a tile holds fewer than two full chunks, 0
+        outside the film's share."""
+        out = np.zeros((self.camera.y_pixels(), self.camera.x_pixels()))
+        _ffi.check(self._L.rayrs_film_noise(self._h, out.ctypes.data), "rayrs_film_noise")
+        return out
+
+    def denoised_guided(self, levels: int = 5, feature_samples: int = 16, sigma_normal=SIGMA_NORMAL, sigma_albedo=SIGMA_ALBEDO,
+                        sigma_depth="scene", sigma_luminance=SIGMA_LUMINANCE, out_f64: bool = False,
+                        return_variance: bool = False):
+        """image(out_f64=True) filtered on the device with noise() and the normal, albedo and depth of `feature_samples`
+        samples (include/rayrs_hip.h GUIDED FILTER): a tap's luminance difference is measured in the pixel's own estimated
+        standard deviations, so tiles that stopped at different sample counts are each filtered by their own noise.  f32,
+        or f64 with out_f64; with return_variance (frame, the variance left after the last level).  The film itself is
+        unchanged.  Sigmas as denoised(); where noise() is +inf the result is denoised(sigma_color=None)."""
+        if isinstance(sigma_depth, str):
+            sigma_depth = scene_sigma_depth(self.scene)
+        H, W = self.camera.y_pixels(), self.camera.x_pixels()
+        out = np.zeros((H, W, 3), dtype=np.float64 if out_f64 else np.float32)
+        out_var = np.zeros((H, W)) if return_variance else None
+        _ffi.check(self._L.rayrs_film_denoise_guided(self._h, int(feature_samples), int(levels), _k(sigma_normal), _k(sigma_albedo),
+                                                     _k(sigma_depth), _k(sigma_luminance), 1 if out_f64 else 0, out.ctypes.data,
+                                                     None if out_var is None else out_var.ctypes.data),
+                   "rayrs_film_denoise_guided")
+        return (out, out_var) if return_variance else out
 
     def status(self, tau: float = 0.0) -> dict:
         """samples, full_chunks, rays, paths, nan_pixels, neg_pixels, closed, and for this tau the batch-means noise

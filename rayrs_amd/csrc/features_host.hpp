@@ -1,10 +1,12 @@
 // features_host.hpp -- the host side of features.hip, shared by features_abi.cpp (rayrs_render_features,
-// rayrs_image_denoise) and film_abi.cpp (rayrs_film_features, rayrs_film_denoise).
+// rayrs_image_denoise) and film_abi.cpp (rayrs_film_features, rayrs_film_denoise); and of guided.hip's filter, shared by
+// guided_abi.cpp (rayrs_image_denoise_guided) and film_abi.cpp (rayrs_film_denoise_guided).
 #pragma once
 #include <cstdint>
 
 #include "device_mem.hpp"
 #include "feature_kernels.h"
+#include "guided_kernels.h"
 #include "scene_internal.hpp"
 
 namespace rayrs {
@@ -30,5 +32,15 @@ int denoise_check(uint32_t levels, double kn, double ka, double kz, double kc);
 int denoise_run(uint32_t w, uint32_t h, const double* d_color, const double* d_normal, const double* d_albedo, const double* d_depth,
                 uint32_t levels, double kn, double ka, double kz, double kc, uint32_t out_format, DevBuf& ping, DevBuf& pong,
                 void** result);
+
+// The guided filter's working buffers: the two record frames, and the last level's colour and variance planes.
+struct GuidedBufs {
+    DevBuf ping, pong, color, variance;
+};
+// A pack and `levels` launches on the null stream: level 0 reads the records packed from d_color and d_variance (neither
+// is written), the last level stores b.color in out_format and, with want_variance, b.variance.
+int guided_run(uint32_t w, uint32_t h, const double* d_color, const double* d_variance, const double* d_normal, const double* d_albedo,
+               const double* d_depth, uint32_t levels, double kn, double ka, double kz, double kv, uint32_t out_format,
+               bool want_variance, GuidedBufs& b);
 
 }  // namespace rayrs

@@ -59,6 +59,8 @@ struct rayrs_film {
     FeatureBufs feat;
     uint32_t feat_samples = 0;  // 0 = none yet
     DevBuf d_ping, d_pong;      // the filter's two colour buffers
+    DevBuf d_var;               // the noise plane (rayrs_film_noise, rayrs_film_denoise_guided), grown on demand
+    GuidedBufs guided;          // the guided filter's record frames and its last level's planes
     size_t record_bytes() const { return (size_t)tiles_x * tiles_y * FILM_TILE_DOUBLES * sizeof(double); }
     size_t n_tiles() const { return (size_t)tiles_x * tiles_y; }
     size_t count_bytes() const { return n_tiles() * sizeof(uint32_t); }
@@ -329,6 +331,60 @@ int rayrs_film_denoise(rayrs_film* film, uint32_t feature_samples, uint32_t leve
     RAYRS_TRY(denoise_run(w, h, film->d_out.as<double>(), film->feat.normal.as<double>(), film->feat.albedo.as<double>(),
                           film->feat.depth.as<double>(), levels, kn, ka, kz, kc, out_format, film->d_ping, film->d_pong, &result));
     HIP_TRY(hipMemcpy(out_host, result, (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4), hipMemcpyDeviceToHost));
+    return RAYRS_OK;
+    })
+}
+
+// the noise plane of the film as it stands into d_var (include/rayrs_hip.h NOISE PLANE); pixels outside the share read +0
+static int film_noise_plane(rayrs_film* f) {
+    const size_t bytes = (size_t)f->camera.x_pixels * f->camera.y_pixels * sizeof(double);
+    HIP_TRY(f->d_var.reserve(bytes));
+    HIP_TRY(hipMemsetAsync(f->d_var.as<>(), 0, bytes, nullptr));
+    const RenderDev rp = film_tiles(f);
+    FilmNoiseDev n;
+    std::memset(&n, 0, sizeof(n));
+    n.rec = f->d_rec.as<double>(), n.tile_n = f->d_tile_n.as<uint32_t>();
+    n.variance = f->d_var.as<double>();
+    n.w = f->camera.x_pixels, n.h = f->camera.y_pixels;
+    n.tiles_x = f->tiles_x, n.n_local_tiles = rp.n_local_tiles;
+    n.tile_rank = rp.tile_rank, n.tile_ranks = rp.tile_ranks;
+    n.c = f->prm.sample_chunk;
+    HIP_TRY(launch_film_noise(n, nullptr));
+    return RAYRS_OK;
+}
+
+int rayrs_film_noise(rayrs_film* film, double* variance_host) {
+    RAYRS_GUARDED({
+    if (!film || !variance_host || film->samples == 0) return RAYRS_INVALID_ARG;
+    RAYRS_TRY(film_enter(film));
+    RAYRS_TRY(film_noise_plane(film));
+    HIP_TRY(film->d_var.download(variance_host, (size_t)film->camera.x_pixels * film->camera.y_pixels * sizeof(double)));
+    return RAYRS_OK;
+    })
+}
+
+int rayrs_film_denoise_guided(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz, double kv,
+                              uint32_t out_format, void* out_host, double* out_variance) {
+    RAYRS_GUARDED({
+    if (!film || !out_host || film->samples == 0) return RAYRS_INVALID_ARG;
+    if (out_format != RAYRS_OUT_F32 && out_format != RAYRS_OUT_F64) return RAYRS_INVALID_ARG;
+    if (film->prm.tile_ranks > 1u) return RAYRS_INVALID_ARG;  // the filter needs a pixel's neighbours
+    RAYRS_TRY(denoise_check(levels, kn, ka, kz, kv));  // the same rule for kv as for kc
+    RAYRS_TRY(features_check(&film->camera, feature_samples, film->prm.tile_rank, film->prm.tile_ranks, film->prm.fast_traversal));
+    RAYRS_TRY(film_enter(film));
+    RAYRS_TRY(film_features(film, feature_samples));
+    // the frame rayrs_film_read(RAYRS_OUT_F64) returns and the plane rayrs_film_noise returns, left on the device
+    const uint32_t w = film->camera.x_pixels, h = film->camera.y_pixels;
+    HIP_TRY(film->d_out.reserve((size_t)w * h * 3 * sizeof(double)));
+    const CameraDev cam = make_camera_dev(&film->camera);
+    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), RAYRS_OUT_F64,
+                             film->d_out.as<>(), nullptr));
+    RAYRS_TRY(film_noise_plane(film));
+    RAYRS_TRY(guided_run(w, h, film->d_out.as<double>(), film->d_var.as<double>(), film->feat.normal.as<double>(),
+                         film->feat.albedo.as<double>(), film->feat.depth.as<double>(), levels, kn, ka, kz, kv, out_format,
+                         out_variance != nullptr, film->guided));
+    HIP_TRY(film->guided.color.download(out_host, (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4)));
+    if (out_variance) HIP_TRY(film->guided.variance.download(out_variance, (size_t)w * h * sizeof(double)));
     return RAYRS_OK;
     })
 }

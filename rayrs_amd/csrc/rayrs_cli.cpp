@@ -2,13 +2,19 @@
 //
 //     rayrs hdri_path [spp] [--scene NAME] [--seed N] [--device N] [--max-bounces N] [--fast-traversal 0|1]
 //                           [--gpus N | --devices a,b,...] [--sample-chunk C] [--pass N] [--until-noise TAU]
-//                           [--denoise [LEVELS]] [--features]
+//                           [--denoise [LEVELS]] [--features] [--denoise-guided [LEVELS]] [--noise]
 //
 // --denoise additionally writes <scene>_denoised.png and .hdr: the final frame (as f64) through the feature-guided a-trous
 // filter of include/rayrs_hip.h (DENOISER), LEVELS levels (default 5), with the normal, albedo and depth of 16 samples and
 // the starting-point sigmas of rayrs_amd/api.py (SIGMA_*).  --features additionally writes <scene>_normal.png
 // (0.5 n + 0.5, no gamma), <scene>_albedo.png and <scene>_depth.hdr.  <scene>.png and <scene>.hdr are the same bytes
 // with and without either.
+//
+// --denoise-guided additionally writes <scene>_guided.png and .hdr: the film's frame through the variance-guided filter of
+// include/rayrs_hip.h (GUIDED FILTER), LEVELS levels (default 5), with the film's own noise plane, the same features and
+// sigmas and a luminance sigma of 4 standard deviations.  --noise additionally writes <scene>_noise.hdr: the noise plane
+// (NOISE PLANE) on three channels, converted to f32 (+infinity stays +infinity).  Both read a film's statistics, so they
+// need --pass or --until-noise: without one the program prints a usage error, exits with status 2 and writes nothing.
 //
 // --sample-chunk C sums a pixel's samples in chunks of C (rayrs_render_params.sample_chunk; default 0: the reference's one
 // sequential sum).  --pass N renders through a progressive film (rayrs_film_*) in passes of N samples, rounded up to a
@@ -138,6 +144,9 @@ int main(int argc, char** argv) {
     double tau = 0.0;
     bool want_denoise = false, want_features = false;
     uint32_t denoise_levels = 5;
+    bool want_guided = false, want_noise = false;
+    uint32_t guided_levels = 5;
+    constexpr double SIGMA_LUMINANCE = 4.0;  // rayrs_amd/api.py SIGMA_LUMINANCE: SVGF's, in standard deviations of the pixel
     constexpr uint32_t FEATURE_SAMPLES = 16;
     // starting points chosen by eye, as rayrs_amd/api.py SIGMA_*: normal, albedo, depth as a fraction of the root-box diagonal, colour
     constexpr double SIGMA_NORMAL = 0.25, SIGMA_ALBEDO = 0.1, SIGMA_DEPTH_FRACTION = 0.02, SIGMA_COLOR = 0.6;
@@ -159,6 +168,19 @@ int main(int argc, char** argv) {
         if (opt == "--features") {
             want_features = true;
             i--;
+            continue;
+        }
+        if (opt == "--noise") {
+            want_noise = true;
+            i--;
+            continue;
+        }
+        if (opt == "--denoise-guided") {  // the level count is optional
+            want_guided = true;
+            char* end = nullptr;
+            const unsigned long v = i + 1 < argc ? std::strtoul(argv[i + 1], &end, 10) : 0ul;
+            if (i + 1 < argc && end != argv[i + 1] && *end == '\0') guided_levels = (uint32_t)v;
+            else i--;
             continue;
         }
         if (opt == "--denoise") {  // the level count is optional
@@ -207,6 +229,10 @@ int main(int argc, char** argv) {
     if (adaptive && !until_noise) {
         std::fprintf(stderr, "--adaptive samples the tiles that are still noisy at a tau: give --until-noise TAU\n");
         return 1;
+    }
+    if ((want_guided || want_noise) && !use_film) {
+        std::fprintf(stderr, "Usage: --denoise-guided and --noise read a film's noise estimate: give --pass N (or --until-noise TAU)\n");
+        return 2;
     }
     if (use_film && (!chunk_given || sample_chunk == 0)) sample_chunk = 4;
     if (use_film) {
@@ -271,7 +297,7 @@ int main(int argc, char** argv) {
     // --denoise filters the f64 frame: a plain render is then asked for f64 and converted here, which is the conversion
     // the f32 output format makes at its store -- the same <scene>.png and <scene>.hdr
     std::vector<double> rgb64(want_denoise && !use_film ? npix * 3 : 0);
-    std::vector<float> extra(want_denoise || want_features ? npix * 3 : 0);
+    std::vector<float> extra(want_denoise || want_features || want_guided || want_noise ? npix * 3 : 0);
     auto write_extra = [&](const char* suffix, double gamma, bool png) -> int {
         const std::string name = scene_name + suffix + (png ? ".png" : ".hdr");
         if (!png) return rayrs_hdr_save(name.c_str(), extra.data(), cam.x_pixels, cam.y_pixels);
@@ -391,6 +417,21 @@ int main(int argc, char** argv) {
             if ((st = rayrs_film_denoise(film, FEATURE_SAMPLES, denoise_levels, kn, ka, kz, kc, RAYRS_OUT_F32, extra.data())) != RAYRS_OK)
                 return fail("film denoise", st);
             if (write_denoised() != RAYRS_OK) return 1;
+        }
+        if (want_guided) {
+            const double kv = 1.0 / (SIGMA_LUMINANCE * SIGMA_LUMINANCE);
+            if ((st = rayrs_film_denoise_guided(film, FEATURE_SAMPLES, guided_levels, kn, ka, kz, kv, RAYRS_OUT_F32, extra.data(), nullptr)) != RAYRS_OK)
+                return fail("film denoise guided", st);
+            int s;
+            if ((s = write_extra("_guided", 1. / 2.2, true)) != RAYRS_OK) return fail("guided png", s);
+            if ((s = write_extra("_guided", 1.0, false)) != RAYRS_OK) return fail("guided hdr", s);
+        }
+        if (want_noise) {
+            std::vector<double> plane(npix);
+            if ((st = rayrs_film_noise(film, plane.data())) != RAYRS_OK) return fail("film noise", st);
+            for (size_t k = 0; k < npix; k++) extra[3 * k] = extra[3 * k + 1] = extra[3 * k + 2] = (float)plane[k];
+            int s;
+            if ((s = write_extra("_noise", 1.0, false)) != RAYRS_OK) return fail("noise hdr", s);
         }
         rayrs_film_destroy(film);
     } else {
