@@ -501,28 +501,38 @@ def render_features(scene: Scene, camera: Camera, samples: int = 16, seed: int =
     return out
 
 
+def _filter_inputs(color, planes, what, variance=False):
+    """What denoise() and denoise_guided() are given, checked: color as a contiguous f64 (H, W, 3) frame, and each of
+    `planes` -- (array or None, its shape after (H, W)) -- likewise, None staying None.  `what` names a plane that has
+    another shape in the ValueError; with `variance` the first plane is the variance, which may not be None."""
+    color = np.ascontiguousarray(color, dtype=np.float64)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise ValueError("color must be (H, W, 3)")
+    if variance and planes[0][0] is None:
+        raise ValueError("variance must be (H, W)")
+    checked = []
+    for a, tail in planes:
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != color.shape[:2] + tail:
+                raise ValueError(f"{what} must be {color.shape[:2] + tail}")
+        checked.append(a)
+    return color, checked
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
 def denoise(color, normal=None, albedo=None, depth=None, levels: int = 5, sigma_normal=SIGMA_NORMAL,
             sigma_albedo=SIGMA_ALBEDO, sigma_depth=None, sigma_color=SIGMA_COLOR, device: int = 0):
     """The edge-avoiding a-trous filter of include/rayrs_hip.h (DENOISER) on any (H, W, 3) frame, on the GPU; returns
     the filtered f64 frame.  A feature plane that is None contributes no term; a sigma that is None or inf switches its
     term off (sigma_depth has no default here: depth has no scale without a scene)."""
-    color = np.ascontiguousarray(color, dtype=np.float64)
-    if color.ndim != 3 or color.shape[2] != 3:
-        raise ValueError("color must be (H, W, 3)")
+    color, (normal, albedo, depth) = _filter_inputs(color, [(normal, (3,)), (albedo, (3,)), (depth, ())], "feature plane")
     H, W = color.shape[:2]
-
-    def plane(a, shape):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if a.shape != shape:
-            raise ValueError(f"feature plane must be {shape}")
-        return a
-
-    normal, albedo, depth = plane(normal, (H, W, 3)), plane(albedo, (H, W, 3)), plane(depth, (H, W))
     out = np.zeros((H, W, 3))
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    _ffi.check(_ffi.lib().rayrs_image_denoise(int(device), W, H, color.ctypes.data, ptr(normal), ptr(albedo), ptr(depth),
+    _ffi.check(_ffi.lib().rayrs_image_denoise(int(device), W, H, color.ctypes.data, _ptr(normal), _ptr(albedo), _ptr(depth),
                                               int(levels), _k(sigma_normal), _k(sigma_albedo), _k(sigma_depth),
                                               _k(sigma_color), out.ctypes.data), "rayrs_image_denoise")
     return out
@@ -534,29 +544,14 @@ def denoise_guided(color, variance, normal=None, albedo=None, depth=None, levels
     """The variance-guided a-trous filter of include/rayrs_hip.h (GUIDED FILTER) on any (H, W, 3) frame with the (H, W)
     variance of its channel sums, on the GPU; returns the filtered f64 frame, or (frame, variance after the last level) with
     return_variance.  Planes and sigmas as denoise(); sigma_luminance is in standard deviations of the pixel."""
-    color = np.ascontiguousarray(color, dtype=np.float64)
-    if color.ndim != 3 or color.shape[2] != 3:
-        raise ValueError("color must be (H, W, 3)")
+    color, (variance, normal, albedo, depth) = _filter_inputs(
+        color, [(variance, ()), (normal, (3,)), (albedo, (3,)), (depth, ())], "plane", variance=True)
     H, W = color.shape[:2]
-
-    def plane(a, shape):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if a.shape != shape:
-            raise ValueError(f"plane must be {shape}")
-        return a
-
-    if variance is None:
-        raise ValueError("variance must be (H, W)")
-    variance = plane(variance, (H, W))
-    normal, albedo, depth = plane(normal, (H, W, 3)), plane(albedo, (H, W, 3)), plane(depth, (H, W))
     out = np.zeros((H, W, 3))
     out_var = np.zeros((H, W)) if return_variance else None
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    _ffi.check(_ffi.lib().rayrs_image_denoise_guided(int(device), W, H, color.ctypes.data, variance.ctypes.data, ptr(normal),
-                                                     ptr(albedo), ptr(depth), int(levels), _k(sigma_normal), _k(sigma_albedo),
-                                                     _k(sigma_depth), _k(sigma_luminance), out.ctypes.data, ptr(out_var)),
+    _ffi.check(_ffi.lib().rayrs_image_denoise_guided(int(device), W, H, color.ctypes.data, variance.ctypes.data, _ptr(normal),
+                                                     _ptr(albedo), _ptr(depth), int(levels), _k(sigma_normal), _k(sigma_albedo),
+                                                     _k(sigma_depth), _k(sigma_luminance), out.ctypes.data, _ptr(out_var)),
                "rayrs_image_denoise_guided")
     return (out, out_var) if return_variance else out
 
@@ -623,18 +618,22 @@ class Film:
                    "rayrs_film_features")
         return out
 
+    def _filter_ks(self, sigma_normal, sigma_albedo, sigma_depth, sigma_last):
+        """The four k of a filter call from its sigmas; sigma_depth given as a string: the scene's default."""
+        if isinstance(sigma_depth, str):
+            sigma_depth = scene_sigma_depth(self.scene)
+        return _k(sigma_normal), _k(sigma_albedo), _k(sigma_depth), _k(sigma_last)
+
     def denoised(self, levels: int = 5, feature_samples: int = 16, sigma_normal=SIGMA_NORMAL, sigma_albedo=SIGMA_ALBEDO,
                  sigma_depth="scene", sigma_color=SIGMA_COLOR, out_f64: bool = False):
         """image(out_f64=True) filtered on the device with the normal, albedo and depth of `feature_samples` samples
         (include/rayrs_hip.h DENOISER); f32, or f64 with out_f64.  The film itself is unchanged.  The default sigmas
         are starting points chosen by eye (SIGMA_* above), sigma_depth a fraction of the scene's root-box diagonal; None or
         inf switches a term off."""
-        if isinstance(sigma_depth, str):
-            sigma_depth = scene_sigma_depth(self.scene)
         out = np.zeros((self.camera.y_pixels(), self.camera.x_pixels(), 3), dtype=np.float64 if out_f64 else np.float32)
-        _ffi.check(self._L.rayrs_film_denoise(self._h, int(feature_samples), int(levels), _k(sigma_normal), _k(sigma_albedo),
-                                              _k(sigma_depth), _k(sigma_color), 1 if out_f64 else 0, out.ctypes.data),
-                   "rayrs_film_denoise")
+        _ffi.check(self._L.rayrs_film_denoise(self._h, int(feature_samples), int(levels),
+                                              *self._filter_ks(sigma_normal, sigma_albedo, sigma_depth, sigma_color),
+                                              1 if out_f64 else 0, out.ctypes.data), "rayrs_film_denoise")
         return out
 
     def noise(self):
@@ -653,14 +652,12 @@ class Film:
         standard deviations, so tiles that stopped at different sample counts are each filtered by their own noise.  f32,
         or f64 with out_f64; with return_variance (frame, the variance left after the last level).  The film itself is
         unchanged.  Sigmas as denoised(); where noise() is +inf the result is denoised(sigma_color=None)."""
-        if isinstance(sigma_depth, str):
-            sigma_depth = scene_sigma_depth(self.scene)
         H, W = self.camera.y_pixels(), self.camera.x_pixels()
         out = np.zeros((H, W, 3), dtype=np.float64 if out_f64 else np.float32)
         out_var = np.zeros((H, W)) if return_variance else None
-        _ffi.check(self._L.rayrs_film_denoise_guided(self._h, int(feature_samples), int(levels), _k(sigma_normal), _k(sigma_albedo),
-                                                     _k(sigma_depth), _k(sigma_luminance), 1 if out_f64 else 0, out.ctypes.data,
-                                                     None if out_var is None else out_var.ctypes.data),
+        _ffi.check(self._L.rayrs_film_denoise_guided(self._h, int(feature_samples), int(levels),
+                                                     *self._filter_ks(sigma_normal, sigma_albedo, sigma_depth, sigma_luminance),
+                                                     1 if out_f64 else 0, out.ctypes.data, _ptr(out_var)),
                    "rayrs_film_denoise_guided")
         return (out, out_var) if return_variance else out
 

@@ -41,6 +41,14 @@ int hip_fail(hipError_t e, const char* what) {
     g_last_error = std::string(what) + ": " + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? RAYRS_OOM : RAYRS_HIP_ERROR;
 }
+int scene_settle(rayrs_scene* scene) {
+    HIP_TRY(hipSetDevice(scene->device));
+    if (scene->pending && scene->last_stream) {
+        HIP_TRY(hipStreamSynchronize(scene->last_stream));
+        scene->pending = false;
+    }
+    return RAYRS_OK;
+}
 }  // namespace rayrs
 
 static void push_triangle(ObjectList& l, Vec3 p1, Vec3 p2, Vec3 p3, uint32_t surf) {
@@ -402,14 +410,7 @@ int rayrs_scene_clone_to_device(const rayrs_scene* scene, int device, rayrs_scen
 int rayrs_scene_device(const rayrs_scene* scene) { return scene ? scene->device : -1; }
 
 static int scene_quiesce(rayrs_scene* scene) {  // settings change between renders, never under one
-    if (scene->device >= 0) {
-        HIP_TRY(hipSetDevice(scene->device));
-        if (scene->pending && scene->last_stream) {
-            HIP_TRY(hipStreamSynchronize(scene->last_stream));
-            scene->pending = false;
-        }
-    }
-    return RAYRS_OK;
+    return scene->device >= 0 ? scene_settle(scene) : RAYRS_OK;
 }
 
 // A render in flight ends before any member releases what it uses (nothing here touches rayrs_last_error).
@@ -726,7 +727,7 @@ static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* c
     rp.tiles_x = (camera->x_pixels + 7) / 8;
     rp.tiles_y = (camera->y_pixels + 7) / 8;
     const uint64_t n_tiles = (uint64_t)rp.tiles_x * rp.tiles_y;
-    uint64_t n_local = n_tiles > rp.tile_rank ? (n_tiles - rp.tile_rank + rp.tile_ranks - 1) / rp.tile_ranks : 0;
+    uint64_t n_local = rank_tiles(n_tiles, rp.tile_rank, rp.tile_ranks);
     if (film && film->list) {  // (at most the share's tiles)
         n_local = film->n_list < n_local ? film->n_list : n_local;
         rp.tile_list = film->list;
@@ -1025,8 +1026,7 @@ int rayrs_render(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_ren
     if (!scene || !camera || !params || !out_host) return RAYRS_INVALID_ARG;
     if (scene->device < 0) return RAYRS_NO_DEVICE;
     HIP_TRY(hipSetDevice(scene->device));
-    const size_t elem = params->out_format == RAYRS_OUT_F64 ? 8 : 4;
-    const size_t bytes = (size_t)camera->x_pixels * camera->y_pixels * 3 * elem;
+    const size_t bytes = frame_bytes(camera->x_pixels, camera->y_pixels, params->out_format);
     DevBuf d_out;
     HIP_TRY(d_out.upload(out_host, bytes));  // pixels of other ranks' tiles keep the caller's values
     RAYRS_TRY(rayrs_render_launch(scene, camera, params, d_out.as<>(), nullptr));

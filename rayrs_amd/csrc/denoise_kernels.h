@@ -1,6 +1,6 @@
-// guided_kernels.h -- the film's per-pixel noise plane and the variance-guided a-trous filter (include/rayrs_hip.h NOISE
-// PLANE and GUIDED FILTER; rayrs_film_noise, rayrs_film_denoise_guided, rayrs_image_denoise_guided): what guided.hip's
-// kernels are handed, and their launch wrappers.
+// denoise_kernels.h -- the film's per-pixel noise plane and the two a-trous filters (include/rayrs_hip.h DENOISER, NOISE
+// PLANE and GUIDED FILTER; rayrs_film_denoise, rayrs_image_denoise, rayrs_film_noise, rayrs_film_denoise_guided,
+// rayrs_image_denoise_guided): what denoise.hip's kernels are handed, and their launch wrappers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,7 +8,20 @@
 
 namespace rayrs {
 
-// The filter's working frame: one 32-byte record per pixel, row-major, so that a tap's colour and variance are one aligned
+// One level of the feature-guided filter: out = the level's colour, from `color` and the read-only feature planes (each may
+// be null: its term is left out).  kc is this level's kc * 4^level, formed by the host.
+struct AtrousDev {
+    const double* color;   // H * W * 3
+    const double* normal;  // H * W * 3 or null
+    const double* albedo;  // H * W * 3 or null
+    const double* depth;   // H * W or null
+    void* out;             // H * W * 3, f64, or f32 (the f64 result converted at the store) with out_f32
+    uint32_t w, h;
+    uint32_t step, out_f32;
+    double kn, ka, kz, kc;
+};
+
+// The guided filter's working frame: one 32-byte record per pixel, row-major, so that a tap's colour and variance are one aligned
 // 32-byte fetch and the 64 taps of a wave's row one 2 KB run.
 struct GuidedRec {
     double cx, cy, cz, v;
@@ -26,7 +39,7 @@ struct FilmNoiseDev {
     uint32_t c, pad;
 };
 
-// One level of the filter: reads the records of the level before and the read-only feature planes (each may be null: its
+// One level of the variance-guided filter: reads the records of the level before and the read-only feature planes (each may be null: its
 // term is left out).  A level that is not the last writes records; the last one stores the colour (f64, or f32 converted at
 // the store) and, if wanted, the variance as planes.
 struct GuidedDev {
@@ -43,6 +56,7 @@ struct GuidedDev {
     double kn, ka, kz, kv;
 };
 
+hipError_t launch_atrous(const AtrousDev& a, hipStream_t stream);
 hipError_t launch_film_noise(const FilmNoiseDev& n, hipStream_t stream);
 // records = (color, variance) per pixel: level 0's input
 hipError_t launch_guided_pack(const double* color, const double* variance, GuidedRec* out, uint32_t w, uint32_t h, hipStream_t stream);

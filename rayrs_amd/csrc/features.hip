@@ -1,7 +1,7 @@
-// features.hip -- first-hit feature buffers and the feature-guided a-trous filter (include/rayrs_hip.h FEATURES and
-// DENOISER).  Neither kernel is part of a render: the features of a sample depend on (scene, camera, seed, pixel, sample
-// index) only, so they are recomputed here from the device functions the path kernels use (device_path.h) instead of
-// being carried through the path rounds, whose kernels sit at their register bound.
+// features.hip -- first-hit feature buffers (include/rayrs_hip.h FEATURES).  The kernel is not part of a render: the
+// features of a sample depend on (scene, camera, seed, pixel, sample index) only, so they are recomputed here from the
+// device functions the path kernels use (device_path.h) instead of being carried through the path rounds, whose kernels
+// sit at their register bound.
 #include <hip/hip_runtime.h>
 
 #include "device_path.h"
@@ -73,72 +73,6 @@ __global__ void __launch_bounds__(256) features_kernel(SceneDev sc, CameraDev ca
     fd.prim[pix] = first_prim;
 }
 
-// One level of the edge-avoiding a-trous filter (Dammertz et al. 2010) exactly as include/rayrs_hip.h DENOISER states it:
-// 5 x 5 taps `step` pixels apart, the weight of a tap the B3-spline's times rr_exp(-e), e the feature and colour
-// distances in the header's operation order.  One lane per pixel, a wave 64 consecutive pixels of a row (its 25 colour
-// reads are 25 runs of 1536 bytes); neighbouring rows and the next level's wider taps meet in L2, not in LDS.
-constexpr uint32_t ATROUS_BX = 64, ATROUS_BY = 4;
-
-RR_DEV bool finite3(double x, double y, double z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
-RR_DEV double dist2(double ax, double ay, double az, double bx, double by, double bz) {
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-__global__ void __launch_bounds__(ATROUS_BX * ATROUS_BY) atrous_kernel(AtrousDev a) {
-    const uint32_t x = blockIdx.x * ATROUS_BX + threadIdx.x;
-    const uint32_t y = blockIdx.y * ATROUS_BY + threadIdx.y;
-    if (x >= a.w || y >= a.h) return;
-    const size_t p = (size_t)y * a.w + x;
-    const double cx = a.color[3 * p], cy = a.color[3 * p + 1], cz = a.color[3 * p + 2];
-    double ox = cx, oy = cy, oz = cz;
-    if (finite3(cx, cy, cz)) {
-        const bool has_n = a.normal != nullptr, has_a = a.albedo != nullptr, has_z = a.depth != nullptr;  // (uniform)
-        double npx = 0.0, npy = 0.0, npz = 0.0, apx = 0.0, apy = 0.0, apz = 0.0, zp = 0.0;
-        if (has_n) npx = a.normal[3 * p], npy = a.normal[3 * p + 1], npz = a.normal[3 * p + 2];
-        if (has_a) apx = a.albedo[3 * p], apy = a.albedo[3 * p + 1], apz = a.albedo[3 * p + 2];
-        if (has_z) zp = a.depth[p];
-        constexpr double h[3] = {0.375, 0.25, 0.0625};
-        double nx = 0.0, ny = 0.0, nz = 0.0, den = 0.0;
-        const int step = (int)a.step;  // at most 2^15: y + 2 * step stays far inside an int
-#pragma unroll
-        for (int dy = -2; dy <= 2; dy++) {
-            const int qy = (int)y + dy * step;
-            if (qy < 0 || qy >= (int)a.h) continue;
-#pragma unroll
-            for (int dx = -2; dx <= 2; dx++) {
-                const int qx = (int)x + dx * step;
-                if (qx < 0 || qx >= (int)a.w) continue;
-                const size_t q = (size_t)qy * a.w + (uint32_t)qx;
-                const double qcx = a.color[3 * q], qcy = a.color[3 * q + 1], qcz = a.color[3 * q + 2];
-                if (!finite3(qcx, qcy, qcz)) continue;
-                // an absent plane's term is +0: every term is >= +0 or NaN, so adding it changes no bit of e
-                double dn = 0.0, da = 0.0, dz = 0.0;
-                if (has_n) dn = dist2(npx, npy, npz, a.normal[3 * q], a.normal[3 * q + 1], a.normal[3 * q + 2]);
-                if (has_a) da = dist2(apx, apy, apz, a.albedo[3 * q], a.albedo[3 * q + 1], a.albedo[3 * q + 2]);
-                if (has_z) {
-                    const double zq = a.depth[q];
-                    dz = (zp - zq) * (zp - zq);
-                }
-                const double dc = dist2(cx, cy, cz, qcx, qcy, qcz);
-                const double e = ((dn * a.kn + da * a.ka) + dz * a.kz) + dc * a.kc;
-                if (!__builtin_isfinite(e)) continue;
-                const double w = (h[dy < 0 ? -dy : dy] * h[dx < 0 ? -dx : dx]) * rr_exp(-e);
-                nx += qcx * w, ny += qcy * w, nz += qcz * w;
-                den += w;
-            }
-        }
-        if (den != 0.0) ox = nx / den, oy = ny / den, oz = nz / den;  // (den == 0: the pixel's own features are NaN)
-    }
-    if (a.out_f32) {
-        float* dst = reinterpret_cast<float*>(a.out) + 3 * p;  // image.rs:224-229
-        dst[0] = (float)ox, dst[1] = (float)oy, dst[2] = (float)oz;
-    } else {
-        double* dst = reinterpret_cast<double*>(a.out) + 3 * p;
-        dst[0] = ox, dst[1] = oy, dst[2] = oz;
-    }
-}
-
 hipError_t launch_features(bool compact, const SceneDev& sc, const CameraDev& cam, const FeatureDev& fd, hipStream_t stream) {
     if (fd.n_local_tiles == 0u || fd.samples == 0u) return hipSuccess;
     const uint32_t lds = 4u * 64u * (sc.stack_lds + 1u) * 4u;  // four waves' stacks, + the spare entry
@@ -152,14 +86,6 @@ hipError_t launch_features(bool compact, const SceneDev& sc, const CameraDev& ca
                                   (int)lds);
         hipLaunchKernelGGL(features_kernel<false>, dim3(blocks), dim3(256), lds, stream, sc, cam, fd);
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_atrous(const AtrousDev& a, hipStream_t stream) {
-    if (a.w == 0u || a.h == 0u) return hipSuccess;
-    // (a.h <= 65535: the grid's y dimension holds it)
-    hipLaunchKernelGGL(atrous_kernel, dim3((a.w + ATROUS_BX - 1u) / ATROUS_BX, (a.h + ATROUS_BY - 1u) / ATROUS_BY),
-                       dim3(ATROUS_BX, ATROUS_BY), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -1,9 +1,8 @@
-// features_abi.cpp -- first-hit feature buffers and the a-trous filter of include/rayrs_hip.h (rayrs_render_features,
-// rayrs_image_denoise) and what film_abi.cpp's rayrs_film_features / rayrs_film_denoise share with them: the refusals,
-// a features pass into device planes, the copy to the host, the filter's levels (features.hip).
+// features_abi.cpp -- first-hit feature buffers of include/rayrs_hip.h (rayrs_render_features) and what film_abi.cpp's
+// rayrs_film_features and filters share with it: the refusals, a features pass into device planes (features.hip), the
+// copy to the host.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -47,7 +46,7 @@ int features_run(rayrs_scene* scene, const rayrs_camera* camera, uint32_t sample
     fd.tile_rank = tile_rank, fd.tile_ranks = tile_ranks;
     fd.tiles_x = (camera->x_pixels + 7u) / 8u;
     const uint64_t n_tiles = (uint64_t)fd.tiles_x * ((camera->y_pixels + 7u) / 8u);
-    fd.n_local_tiles = n_tiles > tile_rank ? (uint32_t)((n_tiles - tile_rank + tile_ranks - 1) / tile_ranks) : 0u;
+    fd.n_local_tiles = rank_tiles(n_tiles, tile_rank, tile_ranks);
     fd.seed = seed;
     fd.inv_samples = 1.0 / (double)samples;
     fd.normal = b.normal.as<double>(), fd.albedo = b.albedo.as<double>();
@@ -77,39 +76,6 @@ int features_download(const rayrs_scene* scene, const rayrs_camera* camera, cons
     return RAYRS_OK;
 }
 
-int denoise_check(uint32_t levels, double kn, double ka, double kz, double kc) {
-    if (levels < 1u || levels > 16u) return RAYRS_INVALID_ARG;
-    for (const double k : {kn, ka, kz, kc})
-        if (!(k >= 0.0) || !std::isfinite(k)) return RAYRS_INVALID_ARG;
-    return RAYRS_OK;
-}
-
-int denoise_run(uint32_t w, uint32_t h, const double* d_color, const double* d_normal, const double* d_albedo, const double* d_depth,
-                uint32_t levels, double kn, double ka, double kz, double kc, uint32_t out_format, DevBuf& ping, DevBuf& pong,
-                void** result) {
-    const size_t bytes = (size_t)w * h * 3 * sizeof(double);
-    HIP_TRY(ping.reserve(bytes));
-    if (levels > 1u) HIP_TRY(pong.reserve(bytes));
-    AtrousDev a;
-    std::memset(&a, 0, sizeof(a));
-    a.color = d_color;
-    a.normal = d_normal, a.albedo = d_albedo, a.depth = d_depth;
-    a.w = w, a.h = h;
-    a.kn = kn, a.ka = ka, a.kz = kz;
-    double kc_k = kc;  // kc * 4^level: a power of two times kc, the same bits however it is formed
-    for (uint32_t level = 0; level < levels; level++, kc_k *= 4.0) {
-        DevBuf& dst = (level & 1u) ? pong : ping;
-        a.out = dst.as<>();
-        a.step = 1u << level;
-        a.kc = kc_k;
-        a.out_f32 = level + 1u == levels && out_format == RAYRS_OUT_F32 ? 1u : 0u;
-        HIP_TRY(launch_atrous(a, nullptr));
-        a.color = dst.as<double>();
-        *result = dst.as<>();
-    }
-    return RAYRS_OK;
-}
-
 }  // namespace rayrs
 
 extern "C" {
@@ -121,36 +87,10 @@ int rayrs_render_features(rayrs_scene* scene, const rayrs_camera* camera, uint32
     if (!scene || !camera) return RAYRS_INVALID_ARG;
     RAYRS_TRY(features_check(camera, samples, tile_rank, tile_ranks, fast_traversal));
     if (scene->device < 0) return RAYRS_NO_DEVICE;
-    HIP_TRY(hipSetDevice(scene->device));
-    if (scene->pending && scene->last_stream) {  // behind whatever the scene still has in flight
-        HIP_TRY(hipStreamSynchronize(scene->last_stream));
-        scene->pending = false;
-    }
+    RAYRS_TRY(scene_settle(scene));
     FeatureBufs b;
     RAYRS_TRY(features_run(scene, camera, samples, seed, tile_rank, tile_ranks, fast_traversal, b));
     RAYRS_TRY(features_download(scene, camera, b, normal, albedo, depth, coverage, object));
-    return RAYRS_OK;
-    })
-}
-
-int rayrs_image_denoise(int device, uint32_t w, uint32_t h, const double* color, const double* normal, const double* albedo,
-                        const double* depth, uint32_t levels, double kn, double ka, double kz, double kc, double* out) {
-    RAYRS_GUARDED({
-    if (!color || !out || w == 0u || h == 0u) return RAYRS_INVALID_ARG;
-    RAYRS_TRY(denoise_check(levels, kn, ka, kz, kc));
-    if (w > 65535u || h > 65535u) return RAYRS_UNSUPPORTED;
-    if (device < 0) return RAYRS_NO_DEVICE;
-    HIP_TRY(hipSetDevice(device));
-    const size_t npix = (size_t)w * h;
-    DevBuf d_color, d_normal, d_albedo, d_depth, ping, pong;
-    HIP_TRY(d_color.upload(color, npix * 3 * sizeof(double)));
-    if (normal) HIP_TRY(d_normal.upload(normal, npix * 3 * sizeof(double)));
-    if (albedo) HIP_TRY(d_albedo.upload(albedo, npix * 3 * sizeof(double)));
-    if (depth) HIP_TRY(d_depth.upload(depth, npix * sizeof(double)));
-    void* result = nullptr;
-    RAYRS_TRY(denoise_run(w, h, d_color.as<double>(), d_normal.as<double>(), d_albedo.as<double>(), d_depth.as<double>(), levels, kn,
-                          ka, kz, kc, RAYRS_OUT_F64, ping, pong, &result));
-    HIP_TRY(hipMemcpy(out, result, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
     return RAYRS_OK;
     })
 }

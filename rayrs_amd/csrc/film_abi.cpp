@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rayrs_hip.h"
+#include "denoise_host.hpp"
 #include "features_host.hpp"
 #include "film.h"
 #include "scene_internal.hpp"
@@ -58,9 +59,8 @@ struct rayrs_film {
     // part of the checkpoint image.
     FeatureBufs feat;
     uint32_t feat_samples = 0;  // 0 = none yet
-    DevBuf d_ping, d_pong;      // the filter's two colour buffers
     DevBuf d_var;               // the noise plane (rayrs_film_noise, rayrs_film_denoise_guided), grown on demand
-    GuidedBufs guided;          // the guided filter's record frames and its last level's planes
+    DenoiseBufs filter;         // what either filter works in
     size_t record_bytes() const { return (size_t)tiles_x * tiles_y * FILM_TILE_DOUBLES * sizeof(double); }
     size_t n_tiles() const { return (size_t)tiles_x * tiles_y; }
     size_t count_bytes() const { return n_tiles() * sizeof(uint32_t); }
@@ -85,21 +85,12 @@ static RenderDev film_tiles(const rayrs_film* f) {
     std::memset(&rp, 0, sizeof(rp));
     rp.tile_rank = f->prm.tile_rank, rp.tile_ranks = f->prm.tile_ranks;
     rp.tiles_x = f->tiles_x, rp.tiles_y = f->tiles_y;
-    const uint64_t n_tiles = (uint64_t)f->tiles_x * f->tiles_y;
-    rp.n_local_tiles = n_tiles > rp.tile_rank ? (uint32_t)((n_tiles - rp.tile_rank + rp.tile_ranks - 1) / rp.tile_ranks) : 0u;
+    rp.n_local_tiles = rank_tiles(f->n_tiles(), rp.tile_rank, rp.tile_ranks);
     return rp;
 }
 
 // a film's calls run on the scene's device, behind whatever the scene still has in flight
-static int film_enter(rayrs_film* f) {
-    rayrs_scene* s = f->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->pending && s->last_stream) {
-        HIP_TRY(hipStreamSynchronize(s->last_stream));
-        s->pending = false;
-    }
-    return RAYRS_OK;
-}
+static int film_enter(rayrs_film* f) { return scene_settle(f->scene); }
 
 // Makes the list of a pass over some of the share's tiles (film.hip): those an adaptive pass of n samples selects at tau
 // under the cap, or all of them.  One word of the result comes back through the scene's pinned words -- the list's length,
@@ -257,7 +248,7 @@ int rayrs_film_read(rayrs_film* film, uint32_t out_format, void* out_host) {
     if (!film || !out_host || film->samples == 0) return RAYRS_INVALID_ARG;
     if (out_format != RAYRS_OUT_F32 && out_format != RAYRS_OUT_F64) return RAYRS_INVALID_ARG;
     RAYRS_TRY(film_enter(film));
-    const size_t bytes = (size_t)film->camera.x_pixels * film->camera.y_pixels * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4);
+    const size_t bytes = frame_bytes(film->camera.x_pixels, film->camera.y_pixels, out_format);
     HIP_TRY(film->d_out.reserve(bytes));
     const CameraDev cam = make_camera_dev(&film->camera);
     HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), out_format,
@@ -311,30 +302,6 @@ int rayrs_film_features(rayrs_film* film, uint32_t samples, double* normal, doub
     })
 }
 
-int rayrs_film_denoise(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz, double kc,
-                       uint32_t out_format, void* out_host) {
-    RAYRS_GUARDED({
-    if (!film || !out_host || film->samples == 0) return RAYRS_INVALID_ARG;
-    if (out_format != RAYRS_OUT_F32 && out_format != RAYRS_OUT_F64) return RAYRS_INVALID_ARG;
-    if (film->prm.tile_ranks > 1u) return RAYRS_INVALID_ARG;  // the filter needs a pixel's neighbours
-    RAYRS_TRY(denoise_check(levels, kn, ka, kz, kc));
-    RAYRS_TRY(features_check(&film->camera, feature_samples, film->prm.tile_rank, film->prm.tile_ranks, film->prm.fast_traversal));
-    RAYRS_TRY(film_enter(film));
-    RAYRS_TRY(film_features(film, feature_samples));
-    // the frame rayrs_film_read(RAYRS_OUT_F64) returns, left on the device
-    const uint32_t w = film->camera.x_pixels, h = film->camera.y_pixels;
-    HIP_TRY(film->d_out.reserve((size_t)w * h * 3 * sizeof(double)));
-    const CameraDev cam = make_camera_dev(&film->camera);
-    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), RAYRS_OUT_F64,
-                             film->d_out.as<>(), nullptr));
-    void* result = nullptr;
-    RAYRS_TRY(denoise_run(w, h, film->d_out.as<double>(), film->feat.normal.as<double>(), film->feat.albedo.as<double>(),
-                          film->feat.depth.as<double>(), levels, kn, ka, kz, kc, out_format, film->d_ping, film->d_pong, &result));
-    HIP_TRY(hipMemcpy(out_host, result, (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4), hipMemcpyDeviceToHost));
-    return RAYRS_OK;
-    })
-}
-
 // the noise plane of the film as it stands into d_var (include/rayrs_hip.h NOISE PLANE); pixels outside the share read +0
 static int film_noise_plane(rayrs_film* f) {
     const size_t bytes = (size_t)f->camera.x_pixels * f->camera.y_pixels * sizeof(double);
@@ -363,30 +330,40 @@ int rayrs_film_noise(rayrs_film* film, double* variance_host) {
     })
 }
 
-int rayrs_film_denoise_guided(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz, double kv,
-                              uint32_t out_format, void* out_host, double* out_variance) {
-    RAYRS_GUARDED({
+// Both of the film's filters: the refusals, the film's features, the frame rayrs_film_read(RAYRS_OUT_F64) returns left in
+// d_out and, guided, the plane rayrs_film_noise returns in d_var; then the levels, and the result copied out.
+static int film_denoise(rayrs_film* film, bool guided, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz,
+                        double k, uint32_t out_format, void* out_host, double* out_variance) {
     if (!film || !out_host || film->samples == 0) return RAYRS_INVALID_ARG;
     if (out_format != RAYRS_OUT_F32 && out_format != RAYRS_OUT_F64) return RAYRS_INVALID_ARG;
     if (film->prm.tile_ranks > 1u) return RAYRS_INVALID_ARG;  // the filter needs a pixel's neighbours
-    RAYRS_TRY(denoise_check(levels, kn, ka, kz, kv));  // the same rule for kv as for kc
+    RAYRS_TRY(denoise_check(levels, kn, ka, kz, k));  // the same rule for kv as for kc
     RAYRS_TRY(features_check(&film->camera, feature_samples, film->prm.tile_rank, film->prm.tile_ranks, film->prm.fast_traversal));
     RAYRS_TRY(film_enter(film));
     RAYRS_TRY(film_features(film, feature_samples));
-    // the frame rayrs_film_read(RAYRS_OUT_F64) returns and the plane rayrs_film_noise returns, left on the device
     const uint32_t w = film->camera.x_pixels, h = film->camera.y_pixels;
-    HIP_TRY(film->d_out.reserve((size_t)w * h * 3 * sizeof(double)));
+    HIP_TRY(film->d_out.reserve(frame_bytes(w, h, RAYRS_OUT_F64)));
     const CameraDev cam = make_camera_dev(&film->camera);
     HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), RAYRS_OUT_F64,
                              film->d_out.as<>(), nullptr));
-    RAYRS_TRY(film_noise_plane(film));
-    RAYRS_TRY(guided_run(w, h, film->d_out.as<double>(), film->d_var.as<double>(), film->feat.normal.as<double>(),
-                         film->feat.albedo.as<double>(), film->feat.depth.as<double>(), levels, kn, ka, kz, kv, out_format,
-                         out_variance != nullptr, film->guided));
-    HIP_TRY(film->guided.color.download(out_host, (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4)));
-    if (out_variance) HIP_TRY(film->guided.variance.download(out_variance, (size_t)w * h * sizeof(double)));
+    if (guided) RAYRS_TRY(film_noise_plane(film));
+    const DenoiseIn in{w, h, film->d_out.as<double>(), guided ? film->d_var.as<double>() : nullptr, film->feat.normal.as<double>(),
+                       film->feat.albedo.as<double>(), film->feat.depth.as<double>()};
+    const void* result = nullptr;
+    RAYRS_TRY(denoise_run(in, levels, kn, ka, kz, k, out_format, out_variance != nullptr, film->filter, &result));
+    HIP_TRY(hipMemcpy(out_host, result, frame_bytes(w, h, out_format), hipMemcpyDeviceToHost));
+    if (out_variance) HIP_TRY(film->filter.variance.download(out_variance, (size_t)w * h * sizeof(double)));
     return RAYRS_OK;
-    })
+}
+
+int rayrs_film_denoise(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz, double kc,
+                       uint32_t out_format, void* out_host) {
+    RAYRS_GUARDED({ return film_denoise(film, false, feature_samples, levels, kn, ka, kz, kc, out_format, out_host, nullptr); })
+}
+
+int rayrs_film_denoise_guided(rayrs_film* film, uint32_t feature_samples, uint32_t levels, double kn, double ka, double kz, double kv,
+                              uint32_t out_format, void* out_host, double* out_variance) {
+    RAYRS_GUARDED({ return film_denoise(film, true, feature_samples, levels, kn, ka, kz, kv, out_format, out_host, out_variance); })
 }
 
 uint64_t rayrs_film_state_bytes(const rayrs_film* film) {

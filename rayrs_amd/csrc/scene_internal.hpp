@@ -86,6 +86,16 @@ namespace rayrs {
 // thread-local text behind rayrs_last_error()
 void set_last_error(const std::string& text);
 int hip_fail(hipError_t e, const char* what);
+// sets the scene's device (>= 0) and waits for what the scene still has in flight on it (abi.cpp)
+int scene_settle(rayrs_scene* s);
+// the tiles of a frame's n_tiles that rank `rank` of `ranks` owns: rank, rank + ranks, ...
+inline uint32_t rank_tiles(uint64_t n_tiles, uint32_t rank, uint32_t ranks) {
+    return n_tiles > rank ? (uint32_t)((n_tiles - rank + ranks - 1) / ranks) : 0u;
+}
+// the bytes of a w x h frame in an out_format
+inline size_t frame_bytes(uint32_t w, uint32_t h, uint32_t out_format) {
+    return (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4);
+}
 // uploads s->flat to s->device and sizes the traversal kernel's LDS (abi.cpp)
 int scene_upload(rayrs_scene* s);
 // what a render hands its kernels, for the self tests too (abi.cpp)

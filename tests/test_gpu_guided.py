@@ -3,7 +3,7 @@ held bit for bit to the plain-Python reference of tests/_guided.py: rayrs_image_
 variance planes with the awkward values in, every level count up to steps beyond the image, every k switched off and every
 plane absent in turn, the all-infinite plane against the feature-guided filter on the GPU itself; a film's plane and
 guided frame against the reference applied to the oracle's S1, S2 and features, uniform, after an adaptive pass, with one
-chunk, closed, and on a tile share; the command line's extra files."""
+chunk, closed, and on a tile share; both filters in turn on one film's shared buffers; the command line's extra files."""
 import os
 import subprocess
 
@@ -219,6 +219,34 @@ def test_a_tile_share_reads_zero_outside_and_refuses_the_filter():
     assert L.rayrs_film_denoise_guided(h, 16, 3, 1.0, 1.0, 1.0, 1.0, 2, buf.ctypes.data, None) == -1
     assert L.rayrs_film_denoise_guided(h, 16, 3, 1.0, 1.0, 1.0, 1.0, 1, None, None) == -1
     assert L.rayrs_film_denoise_guided(h, 16, 3, 1.0, 1.0, 1.0, 1.0, 1, buf.ctypes.data, None) == 0
+
+
+def test_the_two_filters_share_a_films_buffers_without_a_trace_of_each_other():
+    """A film works both filters in one set of buffers, whose frames the two lay out differently (24-byte colours, 32-byte
+    records): alternating them, with level counts that end in either frame and each output form, every result is, bit for
+    bit, what the same call gives as the first on a fresh film."""
+    cam_args, objs, heur, env = _film.DESCS["sphere"](33, 17)
+    scene, cam = rayrs_amd.Scene(objs, 1e-6, 1e6, heur, env, device=0), rayrs_amd.Camera(*cam_args)
+
+    def new_film():
+        film = rayrs_amd.Film(scene, cam, sample_chunk=C, max_bounces=BOUNCES, seed=SEED)
+        film.render(2 * C)
+        return film
+
+    calls = [("denoised", dict(levels=3)),
+             ("denoised_guided", dict(levels=2, return_variance=True)),
+             ("denoised", dict(levels=1, out_f64=True)),
+             ("denoised_guided", dict(levels=3)),
+             ("denoised", dict(levels=2))]
+    film = new_film()
+    assert np.isfinite(film.noise()).all()                       # two full chunks: the variance does guide
+    for i, (method, kw) in enumerate(calls):
+        got, want = getattr(film, method)(**kw), getattr(new_film(), method)(**kw)
+        if not isinstance(got, tuple):
+            got, want = (got,), (want,)
+        assert len(got) == len(want)
+        for g, w in zip(got, want):
+            assert g.dtype == w.dtype and g.shape == w.shape and F.same_bits(g, w), (i, method, kw)
 
 
 # ------------------------------------------------------------------------------------------------------ the command line
