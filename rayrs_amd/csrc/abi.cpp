@@ -490,7 +490,8 @@ int rayrs_lab_set(rayrs_scene* scene, const rayrs_lab_tuning* lab) {
 uint32_t rayrs_frame_sample_chunk(uint32_t x_pixels, uint32_t y_pixels, uint32_t spp, uint32_t requested) {
     if (spp == 0) return 0;
     uint64_t chunk = requested ? requested : 4u;
-    const uint64_t pixels = (uint64_t)((x_pixels + 7u) / 8u) * ((y_pixels + 7u) / 8u) * 64u;  // whole 8x8 tiles
+    const TileShare ts = tile_share(x_pixels, y_pixels, 0u, 1u);
+    const uint64_t pixels = (uint64_t)ts.tiles_x * ts.tiles_y * 64u;  // whole 8x8 tiles
     while (chunk < spp && pixels * ((spp + chunk - 1) / chunk) > (1ull << 30)) chunk *= 2;
     return chunk >= spp ? 0u : (uint32_t)chunk;  // 0 = one sequential sum per pixel (the reference's order)
 }
@@ -620,7 +621,7 @@ extern "C++" SceneDev rayrs::make_scene_dev(const rayrs_scene* s, bool exact) {
 // is thousands of small-primitive sizes long and makes the bet all the same -- the fast walk stays a bet.
 constexpr double RAYRS_FAR_DIAGONALS = 8.0;
 constexpr double RAYRS_FAR_PRIMITIVES = 4096.0;
-extern "C++" bool rayrs::camera_is_far(const rayrs_scene* s, const rayrs_camera* c) {
+static bool camera_is_far(const rayrs_scene* s, const rayrs_camera* c) {
     const double* b = s->flat.root_box;
     double d2 = 0.0, e2 = 0.0;
     for (int a = 0; a < 3; a++) {
@@ -632,6 +633,10 @@ extern "C++" bool rayrs::camera_is_far(const rayrs_scene* s, const rayrs_camera*
     // (a box or an origin that is not a number compares false: the walk that was asked for, as for any other frame)
     const double small = s->flat.small_extent;
     return d2 > RAYRS_FAR_DIAGONALS * RAYRS_FAR_DIAGONALS * e2 || (small > 0.0 && d2 > RAYRS_FAR_PRIMITIVES * RAYRS_FAR_PRIMITIVES * small * small);
+}
+
+extern "C++" FrameWalk rayrs::frame_walk(const rayrs_scene* s, const rayrs_camera* c, uint32_t fast_traversal) {
+    return FrameWalk{s->local_ok && s->tuning.local_pool != 1u, fast_traversal == 0u || camera_is_far(s, c)};
 }
 
 extern "C++" CameraDev rayrs::make_camera_dev(const rayrs_camera* c) {
@@ -722,18 +727,15 @@ static RenderDev make_render_dev(const rayrs_scene* scene, const rayrs_camera* c
     rp.seed = params->seed;
     rp.chunk = (params->sample_chunk == 0 || params->sample_chunk >= params->spp) ? params->spp : params->sample_chunk;
     rp.nchunks = (rp.spp + rp.chunk - 1) / rp.chunk;
-    rp.tile_rank = params->tile_rank;
-    rp.tile_ranks = params->tile_ranks;
-    rp.tiles_x = (camera->x_pixels + 7) / 8;
-    rp.tiles_y = (camera->y_pixels + 7) / 8;
-    const uint64_t n_tiles = (uint64_t)rp.tiles_x * rp.tiles_y;
-    uint64_t n_local = rank_tiles(n_tiles, rp.tile_rank, rp.tile_ranks);
+    const TileShare ts = tile_share(camera->x_pixels, camera->y_pixels, params->tile_rank, params->tile_ranks);
+    rp.tile_rank = ts.tile_rank, rp.tile_ranks = ts.tile_ranks;
+    rp.tiles_x = ts.tiles_x, rp.tiles_y = ts.tiles_y;
+    rp.n_local_tiles = ts.n_local_tiles;
     if (film && film->list) {  // (at most the share's tiles)
-        n_local = film->n_list < n_local ? film->n_list : n_local;
+        if (film->n_list < rp.n_local_tiles) rp.n_local_tiles = film->n_list;
         rp.tile_list = film->list;
     }
-    rp.n_local_tiles = (uint32_t)n_local;
-    rp.total_items = n_local * rp.nchunks * 64ull;
+    rp.total_items = (uint64_t)rp.n_local_tiles * rp.nchunks * 64ull;
     rp.inv_nchunks = 1.0 / (double)rp.nchunks;
     rp.inv_tiles_x = 1.0 / (double)rp.tiles_x;
     rp.count_work = params->count_work ? 1u : 0u;
@@ -753,7 +755,8 @@ static int plan_frame(const rayrs_scene* scene, const rayrs_camera* camera, cons
     // kernels finish items in no particular order, so the array covers the frame.  The local-pool route renders the frame
     // as a sequence of launches over segments of whole tiles and resolves each segment behind its launch: one segment's
     // worth is all it needs (config 4: 3.2 GB instead of 25.8).
-    p.use_local = scene->local_ok && scene->tuning.local_pool != 1u;
+    const FrameWalk walk = frame_walk(scene, camera, params->fast_traversal);
+    p.use_local = walk.use_local, p.exact = walk.exact;
     p.tile_items = (uint64_t)rp.nchunks * 64u;
     uint64_t seg_want = lab.local_segment_items ? lab.local_segment_items : LOCAL_SEGMENT_ITEMS;
     // (a frame stays within LOCAL_MAX_SEGMENTS launches: larger segments rather than a refused frame)
@@ -769,7 +772,6 @@ static int plan_frame(const rayrs_scene* scene, const rayrs_camera* camera, cons
     if (want_blocks < p.local_blocks) p.local_blocks = (uint32_t)(want_blocks ? want_blocks : 1);
     if (!p.use_local || rp.total_items == 0) p.local_blocks = 0;
 
-    p.exact = params->fast_traversal == 0u || camera_is_far(scene, camera);
     p.sc = make_scene_dev(scene, p.exact);
     p.cam = make_camera_dev(camera);
 
@@ -800,7 +802,7 @@ static int plan_frame(const rayrs_scene* scene, const rayrs_camera* camera, cons
     const bool streaming = !p.use_local && rp.total_items > 0;  // (the local-pool route keeps its paths in LDS)
     p.np = streaming ? (uint32_t)((p.live_total + 1023ull) & ~1023ull) : 0u;  // whole windows
     p.trav_blocks = trav_settings(scene, p.exact, p.np, rp);
-    p.spill_words = streaming ? (size_t)(p.sc.stack_depth - p.sc.stack_lds) * p.trav_blocks * 256u : 0;
+    p.spill_words = streaming ? stack_spill_words(p.sc, (uint64_t)p.trav_blocks * 256u) : 0;
 
     // A path's light lives in a side array and only while it is not +0 (wavefront.h PathSlot).  Where a surface
     // emits, paths do get light, and the hit and miss kernels request the side array's entry together with the

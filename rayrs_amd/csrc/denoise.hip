@@ -16,15 +16,12 @@ namespace rayrs {
 // the tile's own M = N_t / c full chunks, in the header's order; +infinity is selected, never computed.
 __global__ void __launch_bounds__(256) film_noise_kernel(FilmNoiseDev n) {
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (uint64_t)n.n_local_tiles * 64u) return;
     const uint32_t pit = (uint32_t)(idx & 63u);
-    const uint32_t tile = (uint32_t)(idx >> 6) * n.tile_ranks + n.tile_rank;
-    const uint32_t row = (tile / n.tiles_x) * 8u + (pit >> 3);
-    const uint32_t col = (tile % n.tiles_x) * 8u + (pit & 7u);
-    if (row >= n.h || col >= n.w) return;  // padding of an edge tile
-    const double* rec = n.rec + (size_t)tile * FILM_TILE_DOUBLES + pit;
+    const TilePixel px = tile_pixel(n.share, (uint32_t)(idx >> 6), pit);
+    if (!px.in_share || px.row >= n.h || px.col >= n.w) return;  // outside the share, or padding of an edge tile
+    const double* rec = n.rec + (size_t)px.tile * FILM_TILE_DOUBLES + pit;
     const double s1 = rec[FILM_S1 * 64u], s2 = rec[FILM_S2 * 64u];
-    const uint32_t big_m = n.tile_n[tile] / n.c;
+    const uint32_t big_m = n.tile_n[px.tile] / n.c;
     const double m = (double)big_m, c = (double)n.c;
     const double inf = __builtin_huge_val();
     double v = inf;
@@ -32,7 +29,7 @@ __global__ void __launch_bounds__(256) film_noise_kernel(FilmNoiseDev n) {
         const double d = m * s2 - s1 * s1;
         if (__builtin_isfinite(d)) v = d > 0.0 ? d / (((m * m) * (m - 1.0)) * (c * c)) : 0.0;
     }
-    n.variance[(size_t)row * n.w + col] = v;
+    n.variance[(size_t)px.row * n.w + px.col] = v;
 }
 
 // Level 0's records from a colour frame and a variance plane, one lane per pixel.
@@ -183,7 +180,7 @@ __global__ void __launch_bounds__(ATROUS_BX * ATROUS_BY) atrous_kernel(AtrousDev
 __global__ void __launch_bounds__(ATROUS_BX * ATROUS_BY) guided_atrous_kernel(GuidedDev a) { atrous_level<true>(a); }
 
 hipError_t launch_film_noise(const FilmNoiseDev& n, hipStream_t stream) {
-    const uint64_t threads = (uint64_t)n.n_local_tiles * 64u;
+    const uint64_t threads = (uint64_t)n.share.n_local_tiles * 64u;
     if (threads == 0) return hipSuccess;
     hipLaunchKernelGGL(film_noise_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, n);
     return hipGetLastError();

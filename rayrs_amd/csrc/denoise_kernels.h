@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "layout.h"
+
 namespace rayrs {
 
 // One level of the feature-guided filter: out = the level's colour, from `color` and the read-only feature planes (each may
@@ -34,9 +36,8 @@ struct FilmNoiseDev {
     const uint32_t* tile_n;  // N_t per tile of the frame
     double* variance;
     uint32_t w, h;
-    uint32_t tiles_x, n_local_tiles;
-    uint32_t tile_rank, tile_ranks;
-    uint32_t c, pad;
+    TileShare share;
+    uint32_t c;
 };
 
 // One level of the variance-guided filter: reads the records of the level before and the read-only feature planes (each may be null: its

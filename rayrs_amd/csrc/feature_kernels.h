@@ -13,8 +13,7 @@ namespace rayrs {
 // are not touched (the caller clears the planes first).
 struct FeatureDev {
     uint32_t samples;
-    uint32_t tile_rank, tile_ranks;
-    uint32_t tiles_x, n_local_tiles, pad;
+    TileShare share;
     uint64_t seed;
     double inv_samples;  // 1.0 / (double)samples
     double* normal;      // H * W * 3

@@ -23,13 +23,10 @@ __global__ void __launch_bounds__(256) features_kernel(SceneDev sc, CameraDev ca
     // sc.stack_lds entries of the stack in LDS, the rest in the strip `spill` (as in the traversal kernel)
     const LaneStack stack{lds_stack + (size_t)wave * (sc.stack_lds + 1u) * 64u + lane, fd.spill + i, sc.stack_lds,
                           gridDim.x * blockDim.x};
-    const uint32_t lt = (uint32_t)(i >> 6);
-    if (lt >= fd.n_local_tiles) return;  // (wave-uniform)
-    const uint32_t tile = lt * fd.tile_ranks + fd.tile_rank;
-    const uint32_t row = (tile / fd.tiles_x) * 8u + (lane >> 3);
-    const uint32_t col = (tile % fd.tiles_x) * 8u + (lane & 7u);
-    const bool inside = row < cam.H && col < cam.W;
-    const uint32_t r = row < cam.H ? row : cam.H - 1u, c = col < cam.W ? col : cam.W - 1u;
+    const TilePixel px = tile_pixel(fd.share, (uint32_t)(i >> 6), lane);
+    if (!px.in_share) return;  // (wave-uniform)
+    const bool inside = px.row < cam.H && px.col < cam.W;
+    const uint32_t r = px.row < cam.H ? px.row : cam.H - 1u, c = px.col < cam.W ? px.col : cam.W - 1u;
     const uint64_t pixel = (uint64_t)r * cam.W + c;
     V3 n_sum = mk(0.0, 0.0, 0.0), a_sum = mk(0.0, 0.0, 0.0);
     double z_sum = 0.0, cov_sum = 0.0;
@@ -64,7 +61,7 @@ __global__ void __launch_bounds__(256) features_kernel(SceneDev sc, CameraDev ca
         }
     }
     if (!inside) return;
-    const size_t pix = (size_t)row * cam.W + col;
+    const size_t pix = (size_t)px.row * cam.W + px.col;
     const double inv = fd.inv_samples;
     fd.normal[3 * pix] = n_sum.x * inv, fd.normal[3 * pix + 1] = n_sum.y * inv, fd.normal[3 * pix + 2] = n_sum.z * inv;
     fd.albedo[3 * pix] = a_sum.x * inv, fd.albedo[3 * pix + 1] = a_sum.y * inv, fd.albedo[3 * pix + 2] = a_sum.z * inv;
@@ -74,9 +71,9 @@ __global__ void __launch_bounds__(256) features_kernel(SceneDev sc, CameraDev ca
 }
 
 hipError_t launch_features(bool compact, const SceneDev& sc, const CameraDev& cam, const FeatureDev& fd, hipStream_t stream) {
-    if (fd.n_local_tiles == 0u || fd.samples == 0u) return hipSuccess;
+    if (fd.share.n_local_tiles == 0u || fd.samples == 0u) return hipSuccess;
     const uint32_t lds = 4u * 64u * (sc.stack_lds + 1u) * 4u;  // four waves' stacks, + the spare entry
-    const uint32_t blocks = (uint32_t)(features_threads(fd.n_local_tiles) / 256u);
+    const uint32_t blocks = (uint32_t)(features_threads(fd.share.n_local_tiles) / 256u);
     if (compact) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&features_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);

@@ -35,25 +35,21 @@ int features_run(rayrs_scene* scene, const rayrs_camera* camera, uint32_t sample
     HIP_TRY(hipMemsetAsync(b.depth.as<>(), 0, npix * sizeof(double), nullptr));
     HIP_TRY(hipMemsetAsync(b.coverage.as<>(), 0, npix * sizeof(double), nullptr));
     HIP_TRY(hipMemsetAsync(b.prim.as<>(), 0xff, npix * sizeof(uint32_t), nullptr));
-    // the walk a render with these settings takes: the camera rule, and a local-pool scene never makes the fast walk's bets
-    const bool local = scene->local_ok && scene->tuning.local_pool != 1u;
-    const bool exact = fast_traversal == 0u || camera_is_far(scene, camera) || local;
-    const SceneDev sc = make_scene_dev(scene, exact);
+    // the walk a render with these settings takes: a local-pool scene never makes the fast walk's bets
+    const FrameWalk walk = frame_walk(scene, camera, fast_traversal);
+    const SceneDev sc = make_scene_dev(scene, walk.exact || walk.use_local);
     const CameraDev cam = make_camera_dev(camera);
     FeatureDev fd;
     std::memset(&fd, 0, sizeof(fd));
     fd.samples = samples;
-    fd.tile_rank = tile_rank, fd.tile_ranks = tile_ranks;
-    fd.tiles_x = (camera->x_pixels + 7u) / 8u;
-    const uint64_t n_tiles = (uint64_t)fd.tiles_x * ((camera->y_pixels + 7u) / 8u);
-    fd.n_local_tiles = rank_tiles(n_tiles, tile_rank, tile_ranks);
+    fd.share = tile_share(camera->x_pixels, camera->y_pixels, tile_rank, tile_ranks);
     fd.seed = seed;
     fd.inv_samples = 1.0 / (double)samples;
     fd.normal = b.normal.as<double>(), fd.albedo = b.albedo.as<double>();
     fd.depth = b.depth.as<double>(), fd.coverage = b.coverage.as<double>();
     fd.prim = b.prim.as<uint32_t>();
     if (sc.stack_depth > sc.stack_lds)
-        HIP_TRY(b.spill.reserve((size_t)(sc.stack_depth - sc.stack_lds) * features_threads(fd.n_local_tiles) * sizeof(uint32_t)));
+        HIP_TRY(b.spill.reserve(stack_spill_words(sc, features_threads(fd.share.n_local_tiles)) * sizeof(uint32_t)));
     fd.spill = b.spill.as<uint32_t>();
     HIP_TRY(launch_features(scene->flat.compact, sc, cam, fd, nullptr));
     return RAYRS_OK;

@@ -43,9 +43,9 @@ struct FilmSelect {  // what film_compact_kernel leaves for the host: one of the
 // lt0 .. lt0 + n_lt - 1 (rp.partial, which starts at item rp.partial_item0) to the records, in chunk order.
 hipError_t launch_film_accumulate(const CameraDev& cam, const RenderDev& rp, const FilmPassDev& fp, uint32_t lt0, uint32_t n_lt,
                                   hipStream_t stream);
-// counts += the NaN / negative / unconverged / non-finite pixels among the rank's tiles (rp: tile fields only), each
-// tile with its own M_t = tile_n[t] / c; tau2 = tau * tau
-hipError_t launch_film_status(const CameraDev& cam, const RenderDev& rp, const double* rec, const uint32_t* tile_n, uint32_t c,
+// counts += the NaN / negative / unconverged / non-finite pixels among the share's tiles, each tile with its own
+// M_t = tile_n[t] / c; tau2 = tau * tau
+hipError_t launch_film_status(const CameraDev& cam, const TileShare& ts, const double* rec, const uint32_t* tile_n, uint32_t c,
                               double tau2, FilmCounts* counts, hipStream_t stream);
 // out (W * H * 3, f32 or f64, row-major) = running sum * (1 / N_t); pixels of other ranks' tiles (N_t = 0) read as +0
 hipError_t launch_film_read(const CameraDev& cam, uint32_t tiles_x, const double* rec, const uint32_t* tile_n, uint32_t out_format,
@@ -54,7 +54,7 @@ hipError_t launch_film_read(const CameraDev& cam, uint32_t tiles_x, const double
 // N_t + n <= cap and an in-image pixel that is unconverged at tau (all != 0: every tile of the share, whatever it
 // holds); then list = the flagged tiles with their N_t in ascending tile order, and *sel.  flags: n_local_tiles words,
 // list: n_local_tiles entries.
-hipError_t launch_film_select(const CameraDev& cam, const RenderDev& rp, const double* rec, const uint32_t* tile_n, uint32_t c,
+hipError_t launch_film_select(const CameraDev& cam, const TileShare& ts, const double* rec, const uint32_t* tile_n, uint32_t c,
                               uint32_t n, uint32_t cap, double tau2, uint32_t all, uint32_t* flags, TileRef* list, FilmSelect* sel,
                               hipStream_t stream);
 

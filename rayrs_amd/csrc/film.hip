@@ -26,6 +26,15 @@ __device__ __forceinline__ void add_chunk(Rec& r, double cx, double cy, double c
         r.s2 += c * c;
     }
 }
+
+// The converged predicate of include/rayrs_hip.h on a pixel's S1 and S2 and its tile's M full chunks, in the header's
+// operation order: is the pixel unconverged?  A non-finite one is neither that nor converged.
+__device__ __forceinline__ bool pixel_unconverged(double s1, double s2, double m, double tau2, bool& nonfinite) {
+    nonfinite = !(__builtin_isfinite(s1) && __builtin_isfinite(s2));
+    const double s11 = s1 * s1;
+    const bool converged = m >= 2.0 && m * s2 - s11 <= ((tau2 * s11)) * (m - 1.0);
+    return !nonfinite && !converged;
+}
 }  // namespace
 
 // One lane per pixel of the rank's tiles lt0 .. lt0 + n_lt - 1, as resolve_kernel indexes them: a wave holds one tile, so
@@ -35,16 +44,15 @@ __global__ void __launch_bounds__(256) film_accumulate_kernel(CameraDev cam, Ren
     if (idx >= (uint64_t)n_lt * 64u) return;
     const uint32_t pit = (uint32_t)(idx & 63u);
     const uint32_t lt = lt0 + (uint32_t)(idx >> 6);
-    uint32_t tile = lt * rp.tile_ranks + rp.tile_rank, n_before = rp.sample0;
+    TilePixel px = tile_pixel(share_of(rp), lt, pit);
+    uint32_t n_before = rp.sample0;
     bool first = fp.first != 0u;
     if (rp.tile_list) {  // the pass's tile lt, and what it holds: an empty tile's first chunk sum is assigned
         const TileRef t = rp.tile_list[lt];
-        tile = t.tile, n_before = t.samples, first = t.samples == 0u;
+        px = pixel_of_tile(share_of(rp), t.tile, pit, px.in_share), n_before = t.samples, first = t.samples == 0u;
     }
-    const uint32_t row = (tile / rp.tiles_x) * 8u + (pit >> 3);
-    const uint32_t col = (tile % rp.tiles_x) * 8u + (pit & 7u);
-    if (row >= cam.H || col >= cam.W) return;  // padding of an edge tile: its record stays zero
-    double* rec = fp.rec + (size_t)tile * FILM_TILE_DOUBLES + pit;
+    if (!px.in_share || px.row >= cam.H || px.col >= cam.W) return;  // padding of an edge tile: its record stays zero
+    double* rec = fp.rec + (size_t)px.tile * FILM_TILE_DOUBLES + pit;
     const double* src = rp.partial + ((((size_t)lt * rp.nchunks) * 64u + pit) - rp.partial_item0) * 3;
     const uint32_t n = rp.nchunks, full = fp.full_chunks;
     Rec r;
@@ -72,35 +80,26 @@ __global__ void __launch_bounds__(256) film_accumulate_kernel(CameraDev cam, Ren
     for (; k < n; k++, src += ITEM_STRIDE) add_chunk(r, src[0], src[1], src[2], k < full);
     rec[FILM_SX * 64u] = r.x, rec[FILM_SY * 64u] = r.y, rec[FILM_SZ * 64u] = r.z;
     rec[FILM_S1 * 64u] = r.s1, rec[FILM_S2 * 64u] = r.s2;
-    if (pit == 0u) fp.tile_n[tile] = n_before + rp.spp;  // (pixel 0 of a tile of the frame is in the image)
+    if (pit == 0u) fp.tile_n[px.tile] = n_before + rp.spp;  // (pixel 0 of a tile of the frame is in the image)
 }
 
 // One pass over the records of the rank's tiles.  Per lane the tests of main.rs:81-87 on the running sum and the
 // converged predicate of include/rayrs_hip.h (no square root, no division: the count is exactly reproducible); per wave a
 // ballot and a population count, and one atomic add per counter that has anything to add.
-__global__ void __launch_bounds__(256) film_status_kernel(CameraDev cam, RenderDev rp, const double* recs, const uint32_t* tile_n,
+__global__ void __launch_bounds__(256) film_status_kernel(CameraDev cam, TileShare ts, const double* recs, const uint32_t* tile_n,
                                                           uint32_t c, double tau2, FilmCounts* counts) {
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t pit = (uint32_t)(idx & 63u);
-    const uint32_t lt = (uint32_t)(idx >> 6);
-    bool valid = idx < (uint64_t)rp.n_local_tiles * 64u;
-    const uint32_t tile = valid ? lt * rp.tile_ranks + rp.tile_rank : 0u;
-    const uint32_t row = (tile / rp.tiles_x) * 8u + (pit >> 3);
-    const uint32_t col = (tile % rp.tiles_x) * 8u + (pit & 7u);
-    const uint32_t n_t = valid ? tile_n[tile] : 0u;
+    const TilePixel px = tile_pixel(ts, (uint32_t)(idx >> 6), pit);
+    const uint32_t n_t = px.in_share ? tile_n[px.tile] : 0u;
     const double m = (double)(n_t / c);  // the tile's own full chunks
-    valid = valid && row < cam.H && col < cam.W;
     bool nan = false, neg = false, unconverged = false, nonfinite = false;
-    if (valid) {
-        const double* rec = recs + (size_t)tile * FILM_TILE_DOUBLES + pit;
+    if (px.in_share && px.row < cam.H && px.col < cam.W) {
+        const double* rec = recs + (size_t)px.tile * FILM_TILE_DOUBLES + pit;
         const double x = rec[FILM_SX * 64u], y = rec[FILM_SY * 64u], z = rec[FILM_SZ * 64u];
-        const double s1 = rec[FILM_S1 * 64u], s2 = rec[FILM_S2 * 64u];
         nan = x != x || y != y || z != z;        // main.rs:81
         neg = x < 0.0 || y < 0.0 || z < 0.0;    // main.rs:85
-        nonfinite = !(__builtin_isfinite(s1) && __builtin_isfinite(s2));
-        const double s11 = s1 * s1;
-        const bool converged = m >= 2.0 && m * s2 - s11 <= ((tau2 * s11)) * (m - 1.0);
-        unconverged = !nonfinite && !converged;
+        unconverged = pixel_unconverged(rec[FILM_S1 * 64u], rec[FILM_S2 * 64u], m, tau2, nonfinite);
     }
     const unsigned long long b_nan = __ballot(nan), b_neg = __ballot(neg), b_unc = __ballot(unconverged), b_nf = __ballot(nonfinite);
     if ((threadIdx.x & 63u) == 0u) {
@@ -136,29 +135,22 @@ __global__ void __launch_bounds__(256) film_read_kernel(CameraDev cam, uint32_t 
 // The tiles an adaptive pass samples.  One wave per tile of the share, reading the records as film_status_kernel does and
 // the same predicate with the tile's own M_t: one ballot says whether any in-image pixel is unconverged (a non-finite
 // pixel is not, and padding never is).  The flag also needs room for n more samples below the cap.
-__global__ void __launch_bounds__(256) film_select_kernel(CameraDev cam, RenderDev rp, const double* recs, const uint32_t* tile_n,
+__global__ void __launch_bounds__(256) film_select_kernel(CameraDev cam, TileShare ts, const double* recs, const uint32_t* tile_n,
                                                           uint32_t c, uint32_t n, uint32_t cap, double tau2, uint32_t all,
                                                           uint32_t* flags) {
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t pit = (uint32_t)(idx & 63u);
     const uint32_t lt = (uint32_t)(idx >> 6);
-    const bool in_share = idx < (uint64_t)rp.n_local_tiles * 64u;  // wave-uniform
-    const uint32_t tile = in_share ? lt * rp.tile_ranks + rp.tile_rank : 0u;
-    const uint32_t row = (tile / rp.tiles_x) * 8u + (pit >> 3);
-    const uint32_t col = (tile % rp.tiles_x) * 8u + (pit & 7u);
-    const uint32_t n_t = in_share ? tile_n[tile] : 0u;
+    const TilePixel px = tile_pixel(ts, lt, pit);  // (in_share is wave-uniform)
+    const uint32_t n_t = px.in_share ? tile_n[px.tile] : 0u;
     const double m = (double)(n_t / c);
-    bool unconverged = false;
-    if (in_share && !all && row < cam.H && col < cam.W) {
-        const double* rec = recs + (size_t)tile * FILM_TILE_DOUBLES + pit;
-        const double s1 = rec[FILM_S1 * 64u], s2 = rec[FILM_S2 * 64u];
-        const bool nonfinite = !(__builtin_isfinite(s1) && __builtin_isfinite(s2));
-        const double s11 = s1 * s1;
-        const bool converged = m >= 2.0 && m * s2 - s11 <= ((tau2 * s11)) * (m - 1.0);
-        unconverged = !nonfinite && !converged;
+    bool unconverged = false, nonfinite;
+    if (px.in_share && !all && px.row < cam.H && px.col < cam.W) {
+        const double* rec = recs + (size_t)px.tile * FILM_TILE_DOUBLES + pit;
+        unconverged = pixel_unconverged(rec[FILM_S1 * 64u], rec[FILM_S2 * 64u], m, tau2, nonfinite);
     }
     const unsigned long long b_unc = __ballot(unconverged);
-    if (in_share && pit == 0u) flags[lt] = (all || (b_unc != 0ull && (uint64_t)n_t + n <= cap)) ? 1u : 0u;
+    if (px.in_share && pit == 0u) flags[lt] = (all || (b_unc != 0ull && (uint64_t)n_t + n <= cap)) ? 1u : 0u;
 }
 
 // flags -> the list of (tile, N_t) in ascending tile order, by a scan: where a tile lands in the list, and with it the
@@ -166,19 +158,18 @@ __global__ void __launch_bounds__(256) film_select_kernel(CameraDev cam, RenderD
 // workgroup walks the share 1024 tiles at a time: a ballot and a population count per wave, the sixteen wave totals
 // through LDS, the running base in a register.  (65536 tiles, a 2048 x 2048 frame, are 64 steps.)
 constexpr uint32_t COMPACT_THREADS = 1024;
-__global__ void __launch_bounds__(COMPACT_THREADS) film_compact_kernel(RenderDev rp, const uint32_t* flags, const uint32_t* tile_n,
+__global__ void __launch_bounds__(COMPACT_THREADS) film_compact_kernel(TileShare ts, const uint32_t* flags, const uint32_t* tile_n,
                                                                        TileRef* list, FilmSelect* sel) {
     __shared__ uint32_t s_wave[COMPACT_THREADS / 64u];
     __shared__ uint32_t s_max;
     const uint32_t tid = threadIdx.x, wave = tid >> 6;
     if (tid == 0u) s_max = 0u;
     uint32_t base = 0u, most = 0u;
-    for (uint32_t start = 0u; start < rp.n_local_tiles; start += COMPACT_THREADS) {
+    for (uint32_t start = 0u; start < ts.n_local_tiles; start += COMPACT_THREADS) {
         const uint32_t lt = start + tid;
-        const bool valid = lt < rp.n_local_tiles;
-        const uint32_t tile = valid ? lt * rp.tile_ranks + rp.tile_rank : 0u;
-        const uint32_t n_t = valid ? tile_n[tile] : 0u;
-        const bool flagged = valid && flags[lt] != 0u;
+        const TilePixel px = tile_pixel(ts, lt, 0u);  // (the tile alone)
+        const uint32_t n_t = px.in_share ? tile_n[px.tile] : 0u;
+        const bool flagged = px.in_share && flags[lt] != 0u;
         most = n_t > most ? n_t : most;
         const unsigned long long b = __ballot(flagged);
         const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
@@ -192,7 +183,7 @@ __global__ void __launch_bounds__(COMPACT_THREADS) film_compact_kernel(RenderDev
         }
         if (flagged) {  // (base + before + below < the flagged tiles so far <= n_local_tiles: inside the list)
             TileRef t;
-            t.tile = tile, t.samples = n_t;
+            t.tile = px.tile, t.samples = n_t;
             list[base + before + below] = t;
         }
         base += total;
@@ -211,12 +202,11 @@ hipError_t launch_film_accumulate(const CameraDev& cam, const RenderDev& rp, con
     return hipGetLastError();
 }
 
-hipError_t launch_film_status(const CameraDev& cam, const RenderDev& rp, const double* rec, const uint32_t* tile_n, uint32_t c,
+hipError_t launch_film_status(const CameraDev& cam, const TileShare& ts, const double* rec, const uint32_t* tile_n, uint32_t c,
                               double tau2, FilmCounts* counts, hipStream_t stream) {
-    const uint64_t n = (uint64_t)rp.n_local_tiles * 64u;
+    const uint64_t n = (uint64_t)ts.n_local_tiles * 64u;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(film_status_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, cam, rp, rec, tile_n, c, tau2,
-                       counts);
+    hipLaunchKernelGGL(film_status_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, cam, ts, rec, tile_n, c, tau2, counts);
     return hipGetLastError();
 }
 
@@ -229,17 +219,17 @@ hipError_t launch_film_read(const CameraDev& cam, uint32_t tiles_x, const double
     return hipGetLastError();
 }
 
-hipError_t launch_film_select(const CameraDev& cam, const RenderDev& rp, const double* rec, const uint32_t* tile_n, uint32_t c,
+hipError_t launch_film_select(const CameraDev& cam, const TileShare& ts, const double* rec, const uint32_t* tile_n, uint32_t c,
                               uint32_t n, uint32_t cap, double tau2, uint32_t all, uint32_t* flags, TileRef* list, FilmSelect* sel,
                               hipStream_t stream) {
-    const uint64_t threads = (uint64_t)rp.n_local_tiles * 64u;
+    const uint64_t threads = (uint64_t)ts.n_local_tiles * 64u;
     if (threads) {
-        hipLaunchKernelGGL(film_select_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, cam, rp, rec, tile_n, c, n,
+        hipLaunchKernelGGL(film_select_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, cam, ts, rec, tile_n, c, n,
                            cap, tau2, all, flags);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(film_compact_kernel, dim3(1), dim3(COMPACT_THREADS), 0, stream, rp, flags, tile_n, list, sel);
+    hipLaunchKernelGGL(film_compact_kernel, dim3(1), dim3(COMPACT_THREADS), 0, stream, ts, flags, tile_n, list, sel);
     return hipGetLastError();
 }
 

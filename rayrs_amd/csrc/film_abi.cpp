@@ -40,7 +40,7 @@ struct rayrs_film {
     rayrs_scene* scene = nullptr;  // not owned
     rayrs_camera camera = {};
     rayrs_film_params prm = {};    // as given, defaults filled in
-    uint32_t tiles_x = 0, tiles_y = 0;
+    TileShare share = {};          // the film's tiles of the frame's (layout.h)
     // samples: N of a uniform film; once the tiles differ, the largest N_t as last read from the device (film_max_samples)
     uint64_t samples = 0, rays = 0, paths = 0;
     bool uniform = true;  // every tile of the share holds `samples` samples (no adaptive pass has left any out yet)
@@ -61,8 +61,8 @@ struct rayrs_film {
     uint32_t feat_samples = 0;  // 0 = none yet
     DevBuf d_var;               // the noise plane (rayrs_film_noise, rayrs_film_denoise_guided), grown on demand
     DenoiseBufs filter;         // what either filter works in
-    size_t record_bytes() const { return (size_t)tiles_x * tiles_y * FILM_TILE_DOUBLES * sizeof(double); }
-    size_t n_tiles() const { return (size_t)tiles_x * tiles_y; }
+    size_t record_bytes() const { return n_tiles() * FILM_TILE_DOUBLES * sizeof(double); }
+    size_t n_tiles() const { return (size_t)share.tiles_x * share.tiles_y; }
     size_t count_bytes() const { return n_tiles() * sizeof(uint32_t); }
     uint64_t full_chunks() const { return samples / prm.sample_chunk; }
     StateHeader header() const {
@@ -79,16 +79,6 @@ struct rayrs_film {
     }
 };
 
-// the tile fields of a RenderDev, which is all the status kernel reads of it
-static RenderDev film_tiles(const rayrs_film* f) {
-    RenderDev rp;
-    std::memset(&rp, 0, sizeof(rp));
-    rp.tile_rank = f->prm.tile_rank, rp.tile_ranks = f->prm.tile_ranks;
-    rp.tiles_x = f->tiles_x, rp.tiles_y = f->tiles_y;
-    rp.n_local_tiles = rank_tiles(f->n_tiles(), rp.tile_rank, rp.tile_ranks);
-    return rp;
-}
-
 // a film's calls run on the scene's device, behind whatever the scene still has in flight
 static int film_enter(rayrs_film* f) { return scene_settle(f->scene); }
 
@@ -96,12 +86,11 @@ static int film_enter(rayrs_film* f) { return scene_settle(f->scene); }
 // under the cap, or all of them.  One word of the result comes back through the scene's pinned words -- the list's length,
 // which the pass is planned from, or (all) the largest N_t, which bounds the pass -- and that copy is the only wait.
 static int film_select(rayrs_film* f, uint32_t n, uint32_t cap, double tau, bool all, uint32_t* word) {
-    const RenderDev rp = film_tiles(f);
-    HIP_TRY(f->d_flags.reserve((size_t)rp.n_local_tiles * sizeof(uint32_t)));
-    HIP_TRY(f->d_list.reserve((size_t)rp.n_local_tiles * sizeof(TileRef)));
+    HIP_TRY(f->d_flags.reserve((size_t)f->share.n_local_tiles * sizeof(uint32_t)));
+    HIP_TRY(f->d_list.reserve((size_t)f->share.n_local_tiles * sizeof(TileRef)));
     const CameraDev cam = make_camera_dev(&f->camera);
     FilmSelect* sel = f->d_select.as<FilmSelect>();
-    HIP_TRY(launch_film_select(cam, rp, f->d_rec.as<double>(), f->d_tile_n.as<uint32_t>(), f->prm.sample_chunk, n, cap, tau * tau,
+    HIP_TRY(launch_film_select(cam, f->share, f->d_rec.as<double>(), f->d_tile_n.as<uint32_t>(), f->prm.sample_chunk, n, cap, tau * tau,
                                all ? 1u : 0u, f->d_flags.as<uint32_t>(), f->d_list.as<TileRef>(), sel, nullptr));
     uint32_t* h_word = f->scene->pool.h_live.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(h_word, all ? &sel->max_samples : &sel->n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
@@ -165,8 +154,7 @@ int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayr
     f->scene = scene;
     f->camera = *camera;
     f->prm = prm;
-    f->tiles_x = (camera->x_pixels + 7u) / 8u;
-    f->tiles_y = (camera->y_pixels + 7u) / 8u;
+    f->share = tile_share(camera->x_pixels, camera->y_pixels, prm.tile_rank, prm.tile_ranks);
     HIP_TRY(hipSetDevice(scene->device));
     HIP_TRY(f->d_rec.reserve(f->record_bytes()));
     HIP_TRY(hipMemset(f->d_rec.as<>(), 0, f->record_bytes()));
@@ -199,7 +187,7 @@ int rayrs_film_render(rayrs_film* film, uint32_t n, rayrs_render_stats* pass_sta
         RAYRS_TRY(film_select(film, n, 0u, 0.0, true, &most));
         film->samples = most;
         if (most > SLOT_SAMPLE_MASK || n > SLOT_SAMPLE_MASK - most) return RAYRS_UNSUPPORTED;
-        n_list = film_tiles(film).n_local_tiles;
+        n_list = film->share.n_local_tiles;
     }
     rayrs_render_stats st;
     RAYRS_TRY(film_pass(film, n, n_list, &st));
@@ -223,7 +211,7 @@ int rayrs_film_render_adaptive(rayrs_film* film, uint32_t n, double tau, uint32_
     std::memset(&st, 0, sizeof(st));
     if (active != 0u) {
         RAYRS_TRY(film_pass(film, n, active, &st));
-        if (film->uniform && active == film_tiles(film).n_local_tiles) film->samples += n;  // every tile went on
+        if (film->uniform && active == film->share.n_local_tiles) film->samples += n;  // every tile went on
         else film->uniform = false;
     }
     if (active_tiles) *active_tiles = active;
@@ -251,7 +239,7 @@ int rayrs_film_read(rayrs_film* film, uint32_t out_format, void* out_host) {
     const size_t bytes = frame_bytes(film->camera.x_pixels, film->camera.y_pixels, out_format);
     HIP_TRY(film->d_out.reserve(bytes));
     const CameraDev cam = make_camera_dev(&film->camera);
-    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), out_format,
+    HIP_TRY(launch_film_read(cam, film->share.tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), out_format,
                              film->d_out.as<>(), nullptr));
     HIP_TRY(film->d_out.download(out_host, bytes));
     return RAYRS_OK;
@@ -263,9 +251,8 @@ int rayrs_film_status_get(rayrs_film* film, double tau, rayrs_film_status* out) 
     if (!film || !out || !(tau >= 0.0) || !std::isfinite(tau)) return RAYRS_INVALID_ARG;
     RAYRS_TRY(film_enter(film));
     const CameraDev cam = make_camera_dev(&film->camera);
-    const RenderDev rp = film_tiles(film);
     HIP_TRY(hipMemsetAsync(film->d_counts.as<>(), 0, sizeof(FilmCounts), nullptr));
-    HIP_TRY(launch_film_status(cam, rp, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), film->prm.sample_chunk, tau * tau,
+    HIP_TRY(launch_film_status(cam, film->share, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), film->prm.sample_chunk, tau * tau,
                                film->d_counts.as<FilmCounts>(), nullptr));
     FilmCounts c;
     HIP_TRY(film->d_counts.download(&c, sizeof(c)));
@@ -307,15 +294,12 @@ static int film_noise_plane(rayrs_film* f) {
     const size_t bytes = (size_t)f->camera.x_pixels * f->camera.y_pixels * sizeof(double);
     HIP_TRY(f->d_var.reserve(bytes));
     HIP_TRY(hipMemsetAsync(f->d_var.as<>(), 0, bytes, nullptr));
-    const RenderDev rp = film_tiles(f);
     FilmNoiseDev n;
     std::memset(&n, 0, sizeof(n));
     n.rec = f->d_rec.as<double>(), n.tile_n = f->d_tile_n.as<uint32_t>();
     n.variance = f->d_var.as<double>();
     n.w = f->camera.x_pixels, n.h = f->camera.y_pixels;
-    n.tiles_x = f->tiles_x, n.n_local_tiles = rp.n_local_tiles;
-    n.tile_rank = rp.tile_rank, n.tile_ranks = rp.tile_ranks;
-    n.c = f->prm.sample_chunk;
+    n.share = f->share, n.c = f->prm.sample_chunk;
     HIP_TRY(launch_film_noise(n, nullptr));
     return RAYRS_OK;
 }
@@ -344,7 +328,7 @@ static int film_denoise(rayrs_film* film, bool guided, uint32_t feature_samples,
     const uint32_t w = film->camera.x_pixels, h = film->camera.y_pixels;
     HIP_TRY(film->d_out.reserve(frame_bytes(w, h, RAYRS_OUT_F64)));
     const CameraDev cam = make_camera_dev(&film->camera);
-    HIP_TRY(launch_film_read(cam, film->tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), RAYRS_OUT_F64,
+    HIP_TRY(launch_film_read(cam, film->share.tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), RAYRS_OUT_F64,
                              film->d_out.as<>(), nullptr));
     if (guided) RAYRS_TRY(film_noise_plane(film));
     const DenoiseIn in{w, h, film->d_out.as<double>(), guided ? film->d_var.as<double>() : nullptr, film->feat.normal.as<double>(),

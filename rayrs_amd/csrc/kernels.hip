@@ -15,10 +15,8 @@ __global__ void __launch_bounds__(256) resolve_kernel(CameraDev cam, RenderDev r
     if (idx >= n) return;
     const uint32_t pit = (uint32_t)(idx & 63u);
     const uint32_t lt = lt0 + (uint32_t)(idx >> 6);
-    const uint32_t tile = lt * rp.tile_ranks + rp.tile_rank;
-    const uint32_t row = (tile / rp.tiles_x) * 8u + (pit >> 3);
-    const uint32_t col = (tile % rp.tiles_x) * 8u + (pit & 7u);
-    if (row >= cam.H || col >= cam.W) return;
+    const TilePixel px = tile_pixel(share_of(rp), lt, pit);
+    if (!px.in_share || px.row >= cam.H || px.col >= cam.W) return;
     double x = 0.0, y = 0.0, z = 0.0;
     for (uint32_t k = 0; k < rp.nchunks; k++) {
         const double* src = rp.partial + ((((size_t)lt * rp.nchunks + k) * 64u + pit) - rp.partial_item0) * 3;
@@ -32,7 +30,7 @@ __global__ void __launch_bounds__(256) resolve_kernel(CameraDev cam, RenderDev r
     if (x < 0.0 || y < 0.0 || z < 0.0) atomicAdd(&rp.counters->neg_pixels, 1ull);        // main.rs:85
     const double inv = 1.0 / (double)rp.spp;
     x *= inv, y *= inv, z *= inv;
-    const size_t pix = (size_t)row * cam.W + col;
+    const size_t pix = (size_t)px.row * cam.W + px.col;
     if (rp.out_format == RAYRS_OUT_F64) {
         double* dst = reinterpret_cast<double*>(rp.out) + pix * 3;
         dst[0] = x, dst[1] = y, dst[2] = z;

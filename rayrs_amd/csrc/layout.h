@@ -173,6 +173,12 @@ struct alignas(8) TileRef {
 };
 static_assert(sizeof(TileRef) == 8, "TileRef");
 
+// A rank's share of a frame's tiles_x * tiles_y 8x8 tiles (row-major): rank tile_rank of tile_ranks owns the tiles tile_rank,
+// tile_rank + tile_ranks, ..., n_local_tiles of them: its local tiles lt = 0, 1, ... (tile_share and tile_pixel below)
+struct TileShare {
+    uint32_t tile_rank, tile_ranks, tiles_x, tiles_y, n_local_tiles;
+};
+
 struct RenderDev {
     uint32_t spp, max_bounces;
     uint64_t seed;
@@ -199,6 +205,7 @@ struct RenderDev {
     // tile_list[lt].tile and its window begins at tile_list[lt].samples (item_geometry below)
     const TileRef* tile_list;
 };
+static_assert(sizeof(RenderDev) == 144 && __builtin_offsetof(RenderDev, tile_rank) == 24 && __builtin_offsetof(RenderDev, tile_list) == 136, "RenderDev");
 
 // n / d and n % d for a launch-constant d with 1/d at hand: the quotient of the f64 product is
 // within one of the true one (n < 2^32, relative error 2^-52), and the remainder says which.
@@ -233,6 +240,31 @@ RR_LAYOUT_FN void item_geometry(const RenderDev& rp, uint32_t item, uint32_t& ro
     const uint32_t w_end = s0 + rp.spp;  // the window's end (at most 2^30 - 1: checked at launch)
     s_begin = s0 + chunk * rp.chunk;
     s_end = s_begin + rp.chunk < w_end ? s_begin + rp.chunk : w_end;
+}
+
+// the tiles of a frame's n_tiles that rank `rank` of `ranks` owns: rank, rank + ranks, ...
+RR_LAYOUT_FN uint32_t rank_tiles(uint64_t n_tiles, uint32_t rank, uint32_t ranks) {
+    return n_tiles > rank ? (uint32_t)((n_tiles - rank + ranks - 1) / ranks) : 0u;
+}
+// rank `rank` of `ranks` (>= 1) of an x_pixels x y_pixels frame: whole tiles, the last of a row or a column padded
+RR_LAYOUT_FN TileShare tile_share(uint32_t x_pixels, uint32_t y_pixels, uint32_t rank, uint32_t ranks) {
+    const uint32_t tx = (x_pixels + 7u) / 8u, ty = (y_pixels + 7u) / 8u;
+    return TileShare{rank, ranks, tx, ty, rank_tiles((uint64_t)tx * ty, rank, ranks)};
+}
+RR_LAYOUT_FN TileShare share_of(const RenderDev& rp) { return TileShare{rp.tile_rank, rp.tile_ranks, rp.tiles_x, rp.tiles_y, rp.n_local_tiles}; }
+
+// The pixel of a per-pixel kernel's thread, lane `pit` (0..63) of the share's local tile lt.  An lt outside the share gets tile 0,
+// always a legal index to read.  row, col may be an edge tile's padding: the caller compares them with the image (such lanes vote).
+struct TilePixel {
+    uint32_t tile, row, col;
+    bool in_share;
+};
+RR_LAYOUT_FN TilePixel pixel_of_tile(const TileShare& ts, uint32_t tile, uint32_t pit, bool in_share) {
+    return TilePixel{tile, (tile / ts.tiles_x) * 8u + (pit >> 3), (tile % ts.tiles_x) * 8u + (pit & 7u), in_share};
+}
+RR_LAYOUT_FN TilePixel tile_pixel(const TileShare& ts, uint32_t lt, uint32_t pit) {
+    const bool in_share = lt < ts.n_local_tiles;
+    return pixel_of_tile(ts, in_share ? lt * ts.tile_ranks + ts.tile_rank : 0u, pit, in_share);
 }
 
 }  // namespace rayrs

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/rayrs_hip.h"
+#include "layout.h"
 
 namespace {
 
@@ -381,7 +382,7 @@ int main(int argc, char** argv) {
         if (adaptive) {
             std::vector<uint32_t> per_tile((size_t)rayrs_film_tile_samples(film, nullptr, 0));
             rayrs_film_tile_samples(film, per_tile.data(), per_tile.size());
-            const uint32_t tiles_x = (cam.x_pixels + 7u) / 8u;
+            const uint32_t tiles_x = rayrs::tile_share(cam.x_pixels, cam.y_pixels, 0u, 1u).tiles_x;
             uint64_t lo = ~0ull, hi = 0, sum = 0;
             for (uint32_t r = 0; r < cam.y_pixels; r++)
                 for (uint32_t c = 0; c < cam.x_pixels; c++) {

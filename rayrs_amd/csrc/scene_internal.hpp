@@ -88,10 +88,6 @@ void set_last_error(const std::string& text);
 int hip_fail(hipError_t e, const char* what);
 // sets the scene's device (>= 0) and waits for what the scene still has in flight on it (abi.cpp)
 int scene_settle(rayrs_scene* s);
-// the tiles of a frame's n_tiles that rank `rank` of `ranks` owns: rank, rank + ranks, ...
-inline uint32_t rank_tiles(uint64_t n_tiles, uint32_t rank, uint32_t ranks) {
-    return n_tiles > rank ? (uint32_t)((n_tiles - rank + ranks - 1) / ranks) : 0u;
-}
 // the bytes of a w x h frame in an out_format
 inline size_t frame_bytes(uint32_t w, uint32_t h, uint32_t out_format) {
     return (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4);
@@ -101,8 +97,14 @@ int scene_upload(rayrs_scene* s);
 // what a render hands its kernels, for the self tests too (abi.cpp)
 SceneDev make_scene_dev(const rayrs_scene* s, bool exact);
 CameraDev make_camera_dev(const rayrs_camera* c);
-// the camera rule of rayrs_render_params.fast_traversal: such a frame takes the default walk whatever it asked for (abi.cpp)
-bool camera_is_far(const rayrs_scene* s, const rayrs_camera* c);
+// The route and the walk of a frame with these settings (abi.cpp).  exact: the default walk, asked for or by the camera rule of
+// rayrs_render_params.fast_traversal; the local-pool route's walk is exact whatever it says.
+struct FrameWalk {
+    bool use_local, exact;
+};
+FrameWalk frame_walk(const rayrs_scene* s, const rayrs_camera* c, uint32_t fast_traversal);
+// words of the traversal stacks' overflow strip for a launch of `threads` threads: the entries beyond the LDS part
+inline size_t stack_spill_words(const SceneDev& sc, uint64_t threads) { return (size_t)(sc.stack_depth - sc.stack_lds) * threads; }
 uint32_t trav_settings(const rayrs_scene* s, bool exact, uint32_t np, RenderDev& rp);
 constexpr size_t POOL_SLOT_BYTES = sizeof(PathSlot) + 4 * sizeof(double) + 1u;  // a slot record, its light entry, its state byte
 WfDev pool_wf(const DevBuf& block, uint32_t np, const DevBuf& ctl, uint32_t trav_blocks, const DevBuf& spill);

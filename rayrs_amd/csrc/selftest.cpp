@@ -57,7 +57,7 @@ int rayrs_test_intersect(rayrs_scene* scene, const double* o, const double* d, u
     const SceneDev sc = make_scene_dev(scene, exact != 0);
     DevBuf dspill;  // stack entries beyond the LDS part, one strip per thread of the launch
     const uint64_t threads = (n + 255) / 256 * 256;
-    if (sc.stack_depth > sc.stack_lds) HIP_TRY(alloc(dspill, (size_t)(sc.stack_depth - sc.stack_lds) * threads * 4));
+    if (sc.stack_depth > sc.stack_lds) HIP_TRY(alloc(dspill, stack_spill_words(sc, threads) * 4));
     if (n)
         HIP_TRY(launch_test_intersect(scene->flat.compact, sc, dorg.as<const double>(), ddir.as<const double>(), n,
                                       dt.as<double>(), dprim.as<long long>(), dspill.as<uint32_t>(), nullptr));
@@ -87,7 +87,7 @@ int rayrs_test_trace(rayrs_scene* scene, const double* o, const double* d, uint6
     DevBuf dblock, dctl, dspill, dcount, dans, dorg, ddir;
     HIP_TRY(alloc(dblock, (size_t)np * POOL_SLOT_BYTES));
     HIP_TRY(alloc(dctl, sizeof(WfCtl)));
-    HIP_TRY(alloc(dspill, (size_t)(sc.stack_depth - sc.stack_lds) * trav_blocks * 256u * 4u));
+    HIP_TRY(alloc(dspill, stack_spill_words(sc, (uint64_t)trav_blocks * 256u) * 4u));
     HIP_TRY(alloc(dcount, sizeof(Counters)));
     HIP_TRY(alloc(dans, sizeof(unsigned long long)));
     HIP_TRY(alloc(dorg, (size_t)np * 24));
@@ -171,7 +171,7 @@ int rayrs_test_path_trace(rayrs_scene* scene, const rayrs_camera* camera, uint64
     const SceneDev sc = make_scene_dev(scene, exact != 0);
     const CameraDev cam = make_camera_dev(camera);
     const uint64_t threads = (n + 255) / 256 * 256;
-    if (sc.stack_depth > sc.stack_lds) HIP_TRY(alloc(dspill, (size_t)(sc.stack_depth - sc.stack_lds) * threads * 4));
+    if (sc.stack_depth > sc.stack_lds) HIP_TRY(alloc(dspill, stack_spill_words(sc, threads) * 4));
     if (n)
         HIP_TRY(launch_test_path_trace(scene->flat.compact, sc, cam, seed, max_bounces, dpix.as<const uint32_t>(),
                                        dsam.as<const uint32_t>(), n, cap, dn.as<uint32_t>(), dprim.as<uint32_t>(), dt.as<double>(),

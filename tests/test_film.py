@@ -233,6 +233,72 @@ def test_item_geometry_with_a_window_start(tmp_path):
     assert (out[2], out[3]) == ((1 << 30) - 8, (1 << 30) - 4)
 
 
+SHARE_SHIM = r"""
+#include "layout.h"
+// out: (tile, row, col, in_share) of every lane of the local tiles 0 .. n_local_tiles + 1; share: the five fields
+extern "C" void share_pixels(unsigned x_pixels, unsigned y_pixels, unsigned rank, unsigned ranks, unsigned* share, unsigned* out) {
+    const rayrs::TileShare ts = rayrs::tile_share(x_pixels, y_pixels, rank, ranks);
+    share[0] = ts.tile_rank, share[1] = ts.tile_ranks, share[2] = ts.tiles_x, share[3] = ts.tiles_y, share[4] = ts.n_local_tiles;
+    rayrs::RenderDev rp = {};   // the kernels that take a RenderDev map through share_of
+    rp.tile_rank = ts.tile_rank, rp.tile_ranks = ts.tile_ranks, rp.tiles_x = ts.tiles_x, rp.tiles_y = ts.tiles_y;
+    rp.n_local_tiles = ts.n_local_tiles;
+    for (unsigned lt = 0; lt <= ts.n_local_tiles + 1; lt++)
+        for (unsigned pit = 0; pit < 64; pit++) {
+            const rayrs::TilePixel p = rayrs::tile_pixel(lt & 1 ? rayrs::share_of(rp) : ts, lt, pit);
+            *out++ = p.tile, *out++ = p.row, *out++ = p.col, *out++ = p.in_share ? 1u : 0u;
+        }
+}
+"""
+
+
+def test_tile_share_and_tile_pixel_are_the_three_line_mapping(tmp_path):
+    """layout.h tile_share, share_of and tile_pixel compiled for the host, exhaustively for frames up to 40 x 24 and up to
+    seven ranks: the share's fields, every lane of every local tile and of the two local tiles past the share against the
+    three-line restatement; the ranks' shares partition the frame's tiles, and their in-image pixels the image."""
+    cxx = shutil.which("g++") or shutil.which("c++") or "/opt/rocm/bin/hipcc"
+    src = tmp_path / "share_shim.cpp"
+    src.write_text(SHARE_SHIM)
+    lib = tmp_path / "libshare_shim.so"
+    cmd = [cxx] + (["-x", "c++"] if cxx.endswith("hipcc") else []) + ["-std=c++17", "-O1", "-shared", "-fPIC", "-ffp-contract=off",
+           "-I", os.path.join(ROOT, "rayrs_amd", "csrc"), "-o", str(lib), str(src)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    fn = C.CDLL(str(lib)).share_pixels
+    fn.argtypes = [C.c_uint32] * 4 + [C.POINTER(C.c_uint32)] * 2
+    fn.restype = None
+    share = (C.c_uint32 * 5)()
+    buf = np.zeros((15 + 2) * 64 * 4, dtype=np.uint32)   # 40 x 24 is 5 x 3 tiles
+    out = buf.ctypes.data_as(C.POINTER(C.c_uint32))
+    pit_of = np.tile(np.arange(64), 17)
+    lt_of = np.repeat(np.arange(17), 64)
+    for x in range(1, 41):
+        for y in range(1, 25):
+            tiles_x, tiles_y = (x + 7) // 8, (y + 7) // 8
+            n_tiles = tiles_x * tiles_y
+            for ranks in range(1, 8):
+                owned, cover = [], np.zeros((y, x), dtype=np.int64)
+                for rank in range(ranks):
+                    fn(x, y, rank, ranks, share, out)
+                    n_local = len(range(rank, n_tiles, ranks))
+                    assert list(share) == [rank, ranks, tiles_x, tiles_y, n_local], (x, y, rank, ranks)
+                    if rank >= n_tiles:
+                        assert share[4] == 0   # more ranks than tiles: the surplus ranks own nothing
+                    k = (n_local + 2) * 64
+                    got = buf[:4 * k].reshape(k, 4).astype(np.int64)
+                    lt, pit = lt_of[:k], pit_of[:k]
+                    inside = lt < n_local
+                    tile = np.where(inside, lt * ranks + rank, 0)   # the three-line restatement
+                    row = (tile // tiles_x) * 8 + (pit >> 3)
+                    col = (tile % tiles_x) * 8 + (pit & 7)
+                    assert np.array_equal(got, np.stack([tile, row, col, inside.astype(np.int64)], axis=1)), (x, y, rank, ranks)
+                    assert (got[~inside][:, 0] == 0).all() and (~inside).sum() == 128   # past the share: tile 0, not in it
+                    owned += list(got[inside][::64, 0])
+                    seen = inside & (row < y) & (col < x)
+                    np.add.at(cover, (row[seen], col[seen]), 1)
+                assert sorted(owned) == list(range(n_tiles)), (x, y, ranks)
+                assert (cover == 1).all(), (x, y, ranks)
+
+
 @pytest.mark.parametrize("name", ["sphere", "mesh"])
 def test_the_oracle_side_reconstruction_is_sound(name):
     """The frame rebuilt from per-sample traces equals orc_render's bit for bit (so S1, S2 and the converged counts the

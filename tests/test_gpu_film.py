@@ -11,7 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+import _features as F
 import _film
+import _film_adaptive as A
+import _guided as G
 import _nonfinite as N
 import _oracle
 import rayrs_amd
@@ -283,6 +286,74 @@ def test_tile_shares_add_up_to_the_frame(variant):
         unconverged += st["unconverged"]
     assert_same_frame(total, ref, "the three shares summed")
     assert rays == ost["rays"] and unconverged == _film.noise_counts(s1, s2, m, 0.2)[0]
+
+
+EDGE_W, EDGE_H, EDGE_TAU = 20, 12, 0.5   # 3 x 2 tiles, the right column and the bottom row padded
+
+
+@pytest.mark.parametrize("ranks", [4, 7], ids=["shares-2-2-1-1", "an-empty-share"])
+@pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
+def test_shares_of_a_small_padded_frame(variant, ranks):
+    """The smallest frame on which the per-pixel kernels' tile mapping can go wrong: edge padding on both sides, shares of
+    unequal size and, with seven ranks for six tiles, a rank that owns nothing.  Per share the frame, the noise counts, the
+    noise plane, the features and one adaptive pass are the oracle's; the shares put together are the oracle's frame."""
+    from test_gpu_features import assert_same_planes
+    from test_gpu_film_adaptive import adaptive_pass
+    w, h = EDGE_W, EDGE_H
+    s = Setup(*variant, w=w, h=h)
+    ref, ost = s.ref(16)
+    rgb, it = A.named_traces(s.name, 24, w, h)   # 16 samples, and the 8 an adaptive pass adds
+    frame, s1, s2, m = _film.expectation(rgb, C, 16)
+    assert_same_frame(frame, ref, "the frame from the traces")
+    for tau in _film.TAUS:   # not satisfied by counting nothing or everything
+        assert 0 < _film.noise_counts(s1, s2, m, tau)[0] < w * h == 240, tau
+    ps = F.named_samples(s.name, 5, w, h)
+    whole = F.features_from(ps, 5)
+    tile_index = np.arange(6).reshape(2, 3)
+    total, rays = np.zeros_like(ref), 0
+    unconverged = dict.fromkeys(_film.TAUS, 0)
+    planes = {k: np.zeros_like(whole[k]) for k in ("normal", "albedo", "depth", "coverage")}
+    planes["object"] = np.full_like(whole["object"], F.MISS)
+    for r in range(ranks):
+        what = f"{variant} rank {r} of {ranks}"
+        mask = tiles.tile_mask(w, h, r, ranks)
+        share = tile_index % ranks == r
+        film = s.film(tile_rank=r, tile_ranks=ranks)
+        assert film.pixels() == int(mask.sum()) and (film.pixels() == 0) == (r >= 6)
+        rays += film.render(8)["rays"] + film.render(8)["rays"]
+        img = film.image(out_f64=True)
+        assert (img[~mask] == 0).all() and not np.signbit(img[~mask]).any(), what
+        assert np.array_equal(img[mask].view(np.uint64), ref[mask].view(np.uint64)), what
+        total += img
+        for tau in _film.TAUS:
+            st = film.status(tau)
+            print(f"{what} tau={tau}: unconverged {st['unconverged']} nonfinite {st['nonfinite']}")
+            assert (st["unconverged"], st["nonfinite"]) == _film.noise_counts(s1, s2, m, tau, mask), (what, tau)
+            assert (st["nan_pixels"], st["neg_pixels"]) == (0, 0) == (ost["nan_pixels"], ost["neg_pixels"])
+            unconverged[tau] += st["unconverged"]
+        noise = film.noise()   # the header's variance from the oracle's S1 and S2; +0 outside the share
+        assert F.same_bits(noise, G.noise_plane(s1, s2, np.where(share, 16, 0), C, share)), what
+        assert (noise[~mask] == 0).all() and not np.signbit(noise[~mask]).any(), what
+        feats = film.features(samples=5)
+        assert_same_planes(feats, rayrs_amd.render_features(s.scene, s.cam, samples=5, seed=SEED, tile_rank=r, tile_ranks=ranks), what)
+        assert_same_planes(feats, F.features_from(ps, 5, r, ranks), (what, "oracle"))
+        for k in planes:
+            planes[k][mask] = feats[k][mask]
+        # one adaptive pass: the tiles of the share the oracle-side predicate flags, in ascending order (the replay's N_t,
+        # frame, counts, rays and paths after it)
+        rep = A.Replay(rgb, it, C, rank=r, ranks=ranks)
+        rep.uniform_pass(8), rep.uniform_pass(8)
+        p, _ = adaptive_pass(film, rep, 8, EDGE_TAU, 0, what)
+        assert np.array_equal(film.tile_samples(), np.where(p["active"], 24, np.where(share, 16, 0))), what
+        if r >= 6:   # the empty share: every call above returned, and everything it returned is empty
+            assert not mask.any() and not img.any() and not noise.any() and p["active_tiles"] == 0
+            assert all(not feats[k].any() for k in ("normal", "albedo", "depth", "coverage")) and (feats["object"] == F.MISS).all()
+            assert (st["unconverged"], st["nonfinite"], st["rays"], st["paths"]) == (0, 0, 0, 0)
+        film.close()
+    assert_same_frame(total, ref, f"the {ranks} shares summed")
+    assert rays == ost["rays"]
+    assert unconverged == {tau: _film.noise_counts(s1, s2, m, tau)[0] for tau in _film.TAUS}
+    assert_same_planes(planes, whole, f"the {ranks} shares' features put together")
 
 
 def test_the_fast_walk_serves_a_film():
