@@ -242,20 +242,20 @@ static void scene_configure_local(rayrs_scene* s) {
     const WalkTree& t = f.gate;  // (the groups behind their gating boxes: this route makes neither of the default walk's bets)
     if (t.n() > 1 || f.n_prims() == 0 || f.n_prims() > LP_MAX_PRIMS || s->surfaces.size() > LP_MAX_PRIMS) return;
     auto add_gate = [&](const double* box, uint32_t ref) {
-        if ((ref >> 30) != REF_RANGE) return false;
+        if (ref_kind(ref) != REF_RANGE) return false;
         const uint32_t g = ls.n_gates++;
         for (int i = 0; i < 6; i++) ls.box[g][i] = box[i];
-        ls.first[g] = (ref & 0x3fffffffu) >> 2;
-        ls.count[g] = (ref & 3u) + 1u;
+        ls.first[g] = ref_first(ref);
+        ls.count[g] = ref_count(ref);
         return true;
     };
     if (t.n() == 0) {  // the root group behind the root Node's box (trav_init)
         if (!add_gate(f.root_box, t.root_ref)) return;
     } else {
-        if ((t.root_ref >> 30) != REF_INTERIOR) return;
+        if (ref_kind(t.root_ref) != REF_INTERIOR) return;
         for (uint32_t k = 0; k < 4; k++) {
             const uint32_t ref = t.ref[k];
-            if ((ref >> 30) == REF_NONE) continue;
+            if (ref_kind(ref) == REF_NONE) continue;
             if (!add_gate(&t.box[(size_t)k * 6], ref)) return;  // an interior slot: not a one-record tree
         }
     }

@@ -355,8 +355,7 @@ RR_DEV void trav_pop(const LaneStack& stack, Trav& tv) {
     }
 }
 
-// One wide record (layout.h): up to four boxes tested, the hit slots entered nearest first
-// (ties by slot), the others pushed farthest first.
+// The slab test on a slot of a wide record (layout.h), compact and f64 layout.
 RR_DEV bool slab_f32(uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, uint32_t z0, uint32_t z1, bool nx, bool ny,
                      bool nz, V3 o, V3 inv, double tmin, double tmax, double& entry) {
     return slab(f32bits_to_f64(nx ? x1 : x0), f32bits_to_f64(nx ? x0 : x1), f32bits_to_f64(ny ? y1 : y0),
@@ -385,17 +384,24 @@ struct HotNodes {
     RR_DEV static constexpr uint32_t stride() { return COMPACT ? 9u : 17u; }  // granules
 };
 
-template <bool COMPACT, bool COUNT, bool EXACT = false>
-RR_DEV void trav_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack, const HotNodes& hot, Trav& tv,
-                               WorkCount& wc) {
+// What a ray finds at one wide record: for each of the four slots, whether the ray enters its box (h), the slab's entry
+// parameter (e) and the slot's reference (r).
+struct RecordTest {
+    bool h0, h1, h2, h3;
+    double e0, e1, e2, e3;
+    uint32_t r0, r1, r2, r3;
+};
+
+// The record test of both walks: the record tv.cur, fetched from its LDS copy or from HBM, and its four boxes tested.
+// Unused slots need no special case: they carry the inverted box (scene_host.cpp), for which the slab test says "missed".
+template <bool COMPACT, bool COUNT>
+RR_DEV RecordTest trav_record_test(const SceneDev& sc, V3 o, const HotNodes& hot, const Trav& tv, WorkCount& wc) {
     const double tmin = sc.t0, tmax = sc.t1;
     const V3 inv = tv.inv;
     const bool nx = inv.x < 0.0, ny = inv.y < 0.0, nz = inv.z < 0.0;
-    const uint32_t rec = tv.cur & 0x3fffffffu;
+    const uint32_t rec = ref_record(tv.cur);
     if (COUNT) wc.interior++;
-    double e0, e1, e2, e3;
-    bool h0, h1, h2, h3;
-    uint32_t r0, r1, r2, r3;
+    RecordTest s;
     if (COMPACT) {
         uint4 a, b, c, d, f, g, r;
         if (rec < hot.count) {
@@ -405,12 +411,12 @@ RR_DEV void trav_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack,
             const uint4* src = reinterpret_cast<const uint4*>(sc.nodes) + (size_t)rec * 8;
             a = src[0], b = src[1], c = src[2], d = src[3], f = src[4], g = src[5], r = src[6];
         }
-        r0 = r.x, r1 = r.y, r2 = r.z, r3 = r.w;
+        s.r0 = r.x, s.r1 = r.y, s.r2 = r.z, s.r3 = r.w;
         // slot k = dwords 6k .. 6k+5 (xmin xmax ymin ymax zmin zmax)
-        h0 = slab_f32(a.x, a.y, a.z, a.w, b.x, b.y, nx, ny, nz, o, inv, tmin, tmax, e0);
-        h1 = slab_f32(b.z, b.w, c.x, c.y, c.z, c.w, nx, ny, nz, o, inv, tmin, tmax, e1);
-        h2 = slab_f32(d.x, d.y, d.z, d.w, f.x, f.y, nx, ny, nz, o, inv, tmin, tmax, e2);
-        h3 = slab_f32(f.z, f.w, g.x, g.y, g.z, g.w, nx, ny, nz, o, inv, tmin, tmax, e3);
+        s.h0 = slab_f32(a.x, a.y, a.z, a.w, b.x, b.y, nx, ny, nz, o, inv, tmin, tmax, s.e0);
+        s.h1 = slab_f32(b.z, b.w, c.x, c.y, c.z, c.w, nx, ny, nz, o, inv, tmin, tmax, s.e1);
+        s.h2 = slab_f32(d.x, d.y, d.z, d.w, f.x, f.y, nx, ny, nz, o, inv, tmin, tmax, s.e2);
+        s.h3 = slab_f32(f.z, f.w, g.x, g.y, g.z, g.w, nx, ny, nz, o, inv, tmin, tmax, s.e3);
     } else {
         // slot by slot (a whole 208-byte record in registers would not fit five waves per SIMD);
         // the scenes that need this layout are the sphere rows, whose few records all sit in LDS
@@ -420,25 +426,33 @@ RR_DEV void trav_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack,
         uint4 x, y, z, r;
         if (in_lds) x = lsrc[0], y = lsrc[1], z = lsrc[2], r = lsrc[12];
         else x = gsrc[0], y = gsrc[1], z = gsrc[2], r = gsrc[12];
-        r0 = r.x, r1 = r.y, r2 = r.z, r3 = r.w;
-        h0 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e0);
+        s.r0 = r.x, s.r1 = r.y, s.r2 = r.z, s.r3 = r.w;
+        s.h0 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, s.e0);
         if (in_lds) x = lsrc[3], y = lsrc[4], z = lsrc[5];
         else x = gsrc[3], y = gsrc[4], z = gsrc[5];
-        h1 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e1);
+        s.h1 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, s.e1);
         if (in_lds) x = lsrc[6], y = lsrc[7], z = lsrc[8];
         else x = gsrc[6], y = gsrc[7], z = gsrc[8];
-        h2 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e2);
+        s.h2 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, s.e2);
         if (in_lds) x = lsrc[9], y = lsrc[10], z = lsrc[11];
         else x = gsrc[9], y = gsrc[10], z = gsrc[11];
-        h3 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e3);
+        s.h3 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, s.e3);
     }
     // keep the references' load with the boxes' (the compiler would otherwise sink it below the
     // "any slot hit" branch, a second memory round trip per step)
-    asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
-    // Unused slots need no special case here: they carry the inverted box (scene_host.cpp), for
-    // which the slab test above says "missed".  Boxes entered beyond the closest hit so far are
-    // skipped -- beyond it by TRAV_CULL_MARGIN (unless EXACT): a primitive's computed t and the entry parameter of the
-    // box around it are rounded independently (and t badly so on grazing rays), so a hit computed in
+    asm volatile("" : "+v"(s.r0), "+v"(s.r1), "+v"(s.r2), "+v"(s.r3));
+    return s;
+}
+
+// One wide record: the slots the ray enters are visited nearest first (ties by slot), the others pushed farthest first.
+template <bool COMPACT, bool COUNT, bool EXACT = false>
+RR_DEV void trav_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack, const HotNodes& hot, Trav& tv,
+                               WorkCount& wc) {
+    const RecordTest s = trav_record_test<COMPACT, COUNT>(sc, o, hot, tv, wc);
+    const double e0 = s.e0, e1 = s.e1, e2 = s.e2, e3 = s.e3;
+    const uint32_t r0 = s.r0, r1 = s.r1, r2 = s.r2, r3 = s.r3;
+    // Boxes entered beyond the closest hit so far are skipped -- beyond it by TRAV_CULL_MARGIN (unless EXACT): a
+    // primitive's computed t and the entry parameter of the box around it are rounded independently (and t badly so on grazing rays), so a hit computed in
     // front of its own box must not be lost to a farther one (every primitive that is tested is judged
     // by the reference's rule, so a wider margin only costs visits, never the answer).
     // Which slots are entered, and the six comparisons of their entry parameters below, are taken as wave masks (a
@@ -448,12 +462,12 @@ RR_DEV void trav_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack,
     // (a compile-time choice: the margin as a kernel argument is one more scalar pair alive across the walk, which the
     // traversal kernel answers by re-loading arguments from memory inside its loop -- +27 % kernel time, measured)
     const double cull = EXACT ? (double)__builtin_inf() : tv.best_t * TRAV_CULL_MARGIN;
-    const unsigned long long m0 = __builtin_amdgcn_ballot_w64(h0) & __builtin_amdgcn_ballot_w64(!(e0 > cull));
-    const unsigned long long m1 = __builtin_amdgcn_ballot_w64(h1) & __builtin_amdgcn_ballot_w64(!(e1 > cull));
-    const unsigned long long m2 = __builtin_amdgcn_ballot_w64(h2) & __builtin_amdgcn_ballot_w64(!(e2 > cull));
-    const unsigned long long m3 = __builtin_amdgcn_ballot_w64(h3) & __builtin_amdgcn_ballot_w64(!(e3 > cull));
+    const unsigned long long m0 = __builtin_amdgcn_ballot_w64(s.h0) & __builtin_amdgcn_ballot_w64(!(e0 > cull));
+    const unsigned long long m1 = __builtin_amdgcn_ballot_w64(s.h1) & __builtin_amdgcn_ballot_w64(!(e1 > cull));
+    const unsigned long long m2 = __builtin_amdgcn_ballot_w64(s.h2) & __builtin_amdgcn_ballot_w64(!(e2 > cull));
+    const unsigned long long m3 = __builtin_amdgcn_ballot_w64(s.h3) & __builtin_amdgcn_ballot_w64(!(e3 > cull));
 #define RR_LANE_BIT(mask) __builtin_amdgcn_inverse_ballot_w64(mask)
-    h0 = RR_LANE_BIT(m0), h1 = RR_LANE_BIT(m1), h2 = RR_LANE_BIT(m2), h3 = RR_LANE_BIT(m3);
+    const bool h0 = RR_LANE_BIT(m0), h1 = RR_LANE_BIT(m1), h2 = RR_LANE_BIT(m2), h3 = RR_LANE_BIT(m3);
     const int n = (int)h0 + (int)h1 + (int)h2 + (int)h3;
     if (n == 0) {
         trav_pop(stack, tv);
@@ -496,12 +510,26 @@ RR_DEV void trav_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack,
     }
 }
 
-// One leaf reference: its 1..4 primitives in DFS order, then pop.
+// The accept rule of the closest hit, for every walk: a hit counts inside the scene's t range, and it replaces the
+// closest so far if it is nearer, or as near and earlier in depth-first order.  (Everything by reference: the callers'
+// values stay where they are, and the kernels that run only the hot group's test compile to the code they had.
+// local_pool.hip lp_isect keeps its own copy, which also tracks the tag: using this one there changes its kernels.)
+RR_DEV void take_hit(const double& t, const uint32_t& p, const double& tmin, const double& tmax, double& best_t,
+                     uint32_t& best_prim) {
+    if (t > tmin && t < tmax) {                                // bvh.rs:406
+        if (t < best_t || (t == best_t && p < best_prim)) {    // bvh.rs:62
+            best_t = t;
+            best_prim = p;
+        }
+    }
+}
+
+// The group test of both walks: the 1..4 primitives of one leaf group, in DFS order.
 template <bool COMPACT, bool COUNT>
-RR_DEV void trav_leaf_step(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack, Trav& tv, WorkCount& wc) {
+RR_DEV void trav_group_test(const SceneDev& sc, V3 o, V3 d, uint32_t ref, Trav& tv, WorkCount& wc) {
     const double tmin = sc.t0, tmax = sc.t1;
-    const uint32_t first = (tv.cur & 0x3fffffffu) >> 2;
-    const uint32_t count = (tv.cur & 3u) + 1u;
+    const uint32_t first = ref_first(ref);
+    const uint32_t count = ref_count(ref);
     if (COUNT) wc.leaf_prims = count;
     for (uint32_t k = 0; k < count; k++) {
         const uint32_t p = first + k;
@@ -513,17 +541,18 @@ RR_DEV void trav_leaf_step(const SceneDev& sc, V3 o, V3 d, const LaneStack& stac
             else wc.plane++;
         }
         double t;
-        if (prim_intersect<COMPACT>(r, o, d, t) && t > tmin && t < tmax) {  // bvh.rs:406
-            if (t < tv.best_t || (t == tv.best_t && p < tv.best_prim)) {    // bvh.rs:62
-                tv.best_t = t;
-                tv.best_prim = p;
-            }
-        }
+        if (prim_intersect<COMPACT>(r, o, d, t)) take_hit(t, p, tmin, tmax, tv.best_t, tv.best_prim);
     }
+}
+
+// One leaf reference: its group, then pop.
+template <bool COMPACT, bool COUNT>
+RR_DEV void trav_leaf_step(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack, Trav& tv, WorkCount& wc) {
+    trav_group_test<COMPACT, COUNT>(sc, o, d, tv.cur, tv, wc);
     trav_pop(stack, tv);
 }
 
-RR_DEV bool trav_at_interior(const Trav& tv) { return (tv.cur >> 30) == REF_INTERIOR; }
+RR_DEV bool trav_at_interior(const Trav& tv) { return ref_kind(tv.cur) == REF_INTERIOR; }
 
 // ---- the default walk with a lane's leaf groups SET ASIDE (wavefront.hip wf_trav_kernel<.., EXACT>) ----
 // The default walk culls nothing: which groups a ray's primitives are tested of is decided by the gating boxes alone, and
@@ -538,7 +567,6 @@ RR_DEV bool trav_at_interior(const Trav& tv) { return (tv.cur >> 30) == REF_INTE
 constexpr uint32_t LEAFQ = TRAV_LEAFQ;                // queue entries per lane (layout.h)
 constexpr uint32_t LEAFQ_ONE = 1u << 16;              // one queued group, in Trav::sp
 constexpr uint32_t LEAFQ_ROOM = (LEAFQ - 3u) << 16;   // sp below this: four more groups fit
-constexpr uint32_t REF_LEAF_BASE = REF_RANGE << 30;   // an entered slot's reference at or above this is a leaf group
 RR_DEV bool defer_has_leaf(const Trav& tv) { return (uint32_t)tv.sp >= LEAFQ_ONE; }
 RR_DEV bool defer_has_room(const Trav& tv) { return (uint32_t)tv.sp < LEAFQ_ROOM; }
 RR_DEV bool defer_finished(const Trav& tv) { return tv.cur == TRAV_DONE && (uint32_t)tv.sp < LEAFQ_ONE; }
@@ -562,51 +590,11 @@ RR_DEV void defer_take_ref(const LaneStack& stack, Trav& tv, uint32_t ref) {
 template <bool COMPACT, bool COUNT>
 RR_DEV void trav_interior_step_defer(const SceneDev& sc, V3 o, const LaneStack& stack, const HotNodes& hot, Trav& tv,
                                      WorkCount& wc) {
-    const double tmin = sc.t0, tmax = sc.t1;
-    const V3 inv = tv.inv;
-    const bool nx = inv.x < 0.0, ny = inv.y < 0.0, nz = inv.z < 0.0;
-    const uint32_t rec = tv.cur & 0x3fffffffu;
-    if (COUNT) wc.interior++;
-    double e0, e1, e2, e3;
-    bool h0, h1, h2, h3;
-    uint32_t r0, r1, r2, r3;
-    if (COMPACT) {
-        uint4 a, b, c, d, f, g, r;
-        if (rec < hot.count) {
-            const uint4* src = hot.lds + rec * HotNodes::stride<true>();
-            a = src[0], b = src[1], c = src[2], d = src[3], f = src[4], g = src[5], r = src[6];
-        } else {
-            const uint4* src = reinterpret_cast<const uint4*>(sc.nodes) + (size_t)rec * 8;
-            a = src[0], b = src[1], c = src[2], d = src[3], f = src[4], g = src[5], r = src[6];
-        }
-        r0 = r.x, r1 = r.y, r2 = r.z, r3 = r.w;
-        h0 = slab_f32(a.x, a.y, a.z, a.w, b.x, b.y, nx, ny, nz, o, inv, tmin, tmax, e0);
-        h1 = slab_f32(b.z, b.w, c.x, c.y, c.z, c.w, nx, ny, nz, o, inv, tmin, tmax, e1);
-        h2 = slab_f32(d.x, d.y, d.z, d.w, f.x, f.y, nx, ny, nz, o, inv, tmin, tmax, e2);
-        h3 = slab_f32(f.z, f.w, g.x, g.y, g.z, g.w, nx, ny, nz, o, inv, tmin, tmax, e3);
-    } else {
-        const bool in_lds = rec < hot.count;
-        const uint4* lsrc = hot.lds + (in_lds ? rec : 0u) * HotNodes::stride<false>();
-        const uint4* gsrc = reinterpret_cast<const uint4*>(sc.nodes) + (size_t)rec * 16;
-        uint4 x, y, z, r;
-        if (in_lds) x = lsrc[0], y = lsrc[1], z = lsrc[2], r = lsrc[12];
-        else x = gsrc[0], y = gsrc[1], z = gsrc[2], r = gsrc[12];
-        r0 = r.x, r1 = r.y, r2 = r.z, r3 = r.w;
-        h0 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e0);
-        if (in_lds) x = lsrc[3], y = lsrc[4], z = lsrc[5];
-        else x = gsrc[3], y = gsrc[4], z = gsrc[5];
-        h1 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e1);
-        if (in_lds) x = lsrc[6], y = lsrc[7], z = lsrc[8];
-        else x = gsrc[6], y = gsrc[7], z = gsrc[8];
-        h2 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e2);
-        if (in_lds) x = lsrc[9], y = lsrc[10], z = lsrc[11];
-        else x = gsrc[9], y = gsrc[10], z = gsrc[11];
-        h3 = slab_f64(x, y, z, nx, ny, nz, o, inv, tmin, tmax, e3);
-    }
-    asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));  // (the references' load stays with the boxes': see trav_interior_step)
+    const RecordTest s = trav_record_test<COMPACT, COUNT>(sc, o, hot, tv, wc);
+    const uint32_t r0 = s.r0, r1 = s.r1, r2 = s.r2, r3 = s.r3;
     // Entered slots, as wave masks (unused slots carry the inverted box: never entered), split by what the slot refers to.
-    const unsigned long long m0 = __builtin_amdgcn_ballot_w64(h0), m1 = __builtin_amdgcn_ballot_w64(h1);
-    const unsigned long long m2 = __builtin_amdgcn_ballot_w64(h2), m3 = __builtin_amdgcn_ballot_w64(h3);
+    const unsigned long long m0 = __builtin_amdgcn_ballot_w64(s.h0), m1 = __builtin_amdgcn_ballot_w64(s.h1);
+    const unsigned long long m2 = __builtin_amdgcn_ballot_w64(s.h2), m3 = __builtin_amdgcn_ballot_w64(s.h3);
     const unsigned long long q0 = __builtin_amdgcn_ballot_w64(r0 >= REF_LEAF_BASE), q1 = __builtin_amdgcn_ballot_w64(r1 >= REF_LEAF_BASE);
     const unsigned long long q2 = __builtin_amdgcn_ballot_w64(r2 >= REF_LEAF_BASE), q3 = __builtin_amdgcn_ballot_w64(r3 >= REF_LEAF_BASE);
 #define RR_LANE_BIT(mask) __builtin_amdgcn_inverse_ballot_w64(mask)
@@ -654,32 +642,11 @@ RR_DEV void trav_interior_step_defer(const SceneDev& sc, V3 o, const LaneStack& 
     }
 }
 
-// One queued leaf group of the lane: its 1..4 primitives in DFS order.
+// One queued leaf group of the lane.
 template <bool COMPACT, bool COUNT>
 RR_DEV void trav_leaf_step_defer(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack, Trav& tv, WorkCount& wc) {
-    const double tmin = sc.t0, tmax = sc.t1;
     tv.sp -= (int)LEAFQ_ONE;
-    const uint32_t ref = defer_queue(stack)[((uint32_t)tv.sp >> 16) * 64u];
-    const uint32_t first = (ref & 0x3fffffffu) >> 2;
-    const uint32_t count = (ref & 3u) + 1u;
-    if (COUNT) wc.leaf_prims = count;
-    for (uint32_t k = 0; k < count; k++) {
-        const uint32_t p = first + k;
-        const PrimRec<COMPACT> r = load_prim<COMPACT>(sc.prims, p);
-        if (COUNT) {
-            const uint32_t kind = r.tag() & 3u;
-            if (kind == PRIM_TRIANGLE) wc.tri++;
-            else if (kind == PRIM_SPHERE) wc.sphere++;
-            else wc.plane++;
-        }
-        double t;
-        if (prim_intersect<COMPACT>(r, o, d, t) && t > tmin && t < tmax) {  // bvh.rs:406
-            if (t < tv.best_t || (t == tv.best_t && p < tv.best_prim)) {    // bvh.rs:62
-                tv.best_t = t;
-                tv.best_prim = p;
-            }
-        }
-    }
+    trav_group_test<COMPACT, COUNT>(sc, o, d, defer_queue(stack)[((uint32_t)tv.sp >> 16) * 64u], tv, wc);
 }
 
 // ------------------------------------------------------- the hot group (layout.h HotGroupDev)
@@ -796,17 +763,12 @@ RR_DEV void hot_group_step(const SceneDev& sc, V3 o, V3 d, bool owe, Trav& tv, W
                                   h->prim[k].v[4], o, d, t);
         }
         const uint32_t p = first + k;
-        if (entered && hit && t > tmin && t < tmax) {                     // bvh.rs:406
-            if (t < tv.best_t || (t == tv.best_t && p < tv.best_prim)) {  // bvh.rs:62
-                tv.best_t = t;
-                tv.best_prim = p;
-            }
-        }
+        if (entered && hit) take_hit(t, p, tmin, tmax, tv.best_t, tv.best_prim);
     }
 }
 
 // The first record of the tree without the hot group (HotGroupDev::root_box, the f64 values its record holds): does the ray
-// enter which of its four slots?  The same test, on the same values, that trav_interior_step makes of that record.
+// enter which of its four slots?  The same test, on the same values, that trav_record_test makes of that record.
 RR_DEV uint32_t hot_root_record_entered(const SceneDev& sc, V3 o, V3 inv) {  // bit c: the ray enters slot c
     const HotPtr h = hot_ptr(sc);
     const double tmin = sc.t0, tmax = sc.t1;

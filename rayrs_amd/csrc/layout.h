@@ -20,6 +20,13 @@
 
 namespace rayrs {
 
+// functions of this header that the host and the kernels share
+#if defined(__HIPCC__)
+#define RR_LAYOUT_FN __host__ __device__ static inline
+#else
+#define RR_LAYOUT_FN static inline
+#endif
+
 // child reference: kind << 30 | payload
 constexpr uint32_t REF_INTERIOR = 0u;  // payload = interior record index
 constexpr uint32_t REF_RANGE = 1u;     // payload = first_prim << 2 | (count - 1): 1..4 primitives behind the slot's box
@@ -27,6 +34,18 @@ constexpr uint32_t REF_SINGLE = 2u;    // two-child export only: payload = prim 
                                        // bvh.rs:297, :302); the gate tree holds it as a one-primitive REF_RANGE behind
                                        // the box of the Node it hangs under
 constexpr uint32_t REF_NONE = 3u;
+// The bits of a reference are spelled out here and nowhere else: the builder makes references and the walks take them
+// apart with these.
+RR_LAYOUT_FN constexpr uint32_t ref_kind(uint32_t ref) { return ref >> 30; }
+RR_LAYOUT_FN constexpr uint32_t ref_record(uint32_t ref) { return ref & 0x3fffffffu; }         // REF_INTERIOR: the record's index
+RR_LAYOUT_FN constexpr uint32_t ref_first(uint32_t ref) { return (ref & 0x3fffffffu) >> 2; }   // a group's first primitive (DFS index)
+RR_LAYOUT_FN constexpr uint32_t ref_count(uint32_t ref) { return (ref & 3u) + 1u; }            // ... and how many it has: 1..4
+RR_LAYOUT_FN constexpr uint32_t record_ref(uint32_t rec) { return (REF_INTERIOR << 30) | rec; }
+RR_LAYOUT_FN constexpr uint32_t group_ref(uint32_t first, uint32_t count, uint32_t kind = REF_RANGE) {
+    return (kind << 30) | (first << 2) | (count - 1u);
+}
+constexpr uint32_t REF_UNUSED = REF_NONE << 30;    // what an unused slot carries
+constexpr uint32_t REF_LEAF_BASE = REF_RANGE << 30;  // a reference a ray can enter (never REF_NONE: the inverted box) at or above this is a leaf group
 
 // primitive tag: kind | axis << 2 | surface << 8
 constexpr uint32_t PRIM_SPHERE = 0u;
@@ -210,11 +229,6 @@ static_assert(sizeof(RenderDev) == 144 && __builtin_offsetof(RenderDev, tile_ran
 // n / d and n % d for a launch-constant d with 1/d at hand: the quotient of the f64 product is
 // within one of the true one (n < 2^32, relative error 2^-52), and the remainder says which.
 // A dozen instructions against the ~35 of a 32-bit integer division.
-#if defined(__HIPCC__)
-#define RR_LAYOUT_FN __host__ __device__ static inline
-#else
-#define RR_LAYOUT_FN static inline
-#endif
 RR_LAYOUT_FN uint32_t udiv_by(uint32_t n, uint32_t d, double inv_d, uint32_t& rem) {
     uint32_t q = (uint32_t)((double)n * inv_d);
     int32_t r = (int32_t)(n - q * d);

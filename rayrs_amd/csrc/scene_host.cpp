@@ -183,7 +183,7 @@ struct Builder {
     uint32_t emit_single(uint32_t obj) {
         const uint32_t p = next_prim++;
         flat.prim_object[p] = obj;
-        return (REF_SINGLE << 30) | (p << 2);
+        return group_ref(p, 1u, REF_SINGLE);
     }
 
     // Node over order[lo, hi), hi - lo >= 1 handled by the caller for singles.
@@ -195,7 +195,7 @@ struct Builder {
         if (len <= 4) {  // bvh.rs:306-316 / :378-387
             const uint32_t first = next_prim;
             for (size_t i = lo; i < hi; i++) flat.prim_object[next_prim++] = order[i];
-            return (REF_RANGE << 30) | (first << 2) | (uint32_t)(len - 1);
+            return group_ref(first, (uint32_t)len);
         }
         const double ex = box.xmax - box.xmin, ey = box.ymax - box.ymin, ez = box.zmax - box.zmin;
         int axis;
@@ -274,7 +274,7 @@ struct Builder {
             double* bx = &flat.child_box[((size_t)rec * 2 + ch) * 6];
             bx[0] = cb.xmin, bx[1] = cb.xmax, bx[2] = cb.ymin, bx[3] = cb.ymax, bx[4] = cb.zmin, bx[5] = cb.zmax;
         }
-        return (REF_INTERIOR << 30) | rec;
+        return record_ref(rec);
     }
 };
 
@@ -285,7 +285,7 @@ double record_area(const WalkTree& f, uint32_t rec) {
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     bool any = false;
     for (int i = 0; i < 4; i++) {
-        const uint32_t kind = f.ref[(size_t)rec * 4 + i] >> 30;
+        const uint32_t kind = ref_kind(f.ref[(size_t)rec * 4 + i]);
         if (kind != REF_INTERIOR && kind != REF_RANGE) continue;
         const double* b = &f.box[((size_t)rec * 4 + i) * 6];
         for (int a = 0; a < 3; a++) {
@@ -327,14 +327,14 @@ void front_largest(WalkTree& f) {
         const uint32_t old = order[i];
         for (int c = 0; c < 4; c++) {
             uint32_t r = f.ref[(size_t)old * 4 + c];
-            if ((r >> 30) == REF_INTERIOR) r = (REF_INTERIOR << 30) | new_of[r & 0x3fffffffu];
+            if (ref_kind(r) == REF_INTERIOR) r = record_ref(new_of[ref_record(r)]);
             ref[(size_t)i * 4 + c] = r;
         }
         for (int c = 0; c < 24; c++) box[(size_t)i * 24 + c] = f.box[(size_t)old * 24 + c];
     }
     f.box.swap(box);
     f.ref.swap(ref);
-    f.root_ref = (REF_INTERIOR << 30) | new_of[f.root_ref & 0x3fffffffu];
+    f.root_ref = record_ref(new_of[ref_record(f.root_ref)]);
 }
 
 // ------------------------------------------------------------ the walk trees
@@ -360,7 +360,7 @@ void front_largest(WalkTree& f) {
 
 struct WalkGroup {
     double box[6];
-    uint32_t ref;  // REF_RANGE: first primitive << 2 | count - 1
+    uint32_t ref;  // REF_RANGE (layout.h group_ref)
 };
 
 // The groups of the two-child tree in depth-first order.  `gate` is the box of record n itself.
@@ -368,16 +368,16 @@ void collect_groups(const FlatScene& f, uint32_t n, const double* gate, std::vec
     for (int c = 0; c < 2; c++) {
         const uint32_t r = f.child_ref[(size_t)n * 2 + c];
         const double* box = &f.child_box[((size_t)n * 2 + c) * 6];
-        const uint32_t kind = r >> 30;
+        const uint32_t kind = ref_kind(r);
         if (kind == REF_INTERIOR) {
-            collect_groups(f, r & 0x3fffffffu, box, out);
+            collect_groups(f, ref_record(r), box, out);
         } else {
             WalkGroup g;
             // a direct leaf has no box of its own in the reference (bvh.rs:297, :302): what gates it
             // is the box of the Node it hangs under
             const double* gb = kind == REF_SINGLE ? gate : box;
             for (int k = 0; k < 6; k++) g.box[k] = gb[k];
-            g.ref = (REF_RANGE << 30) | (r & 0x3fffffffu);
+            g.ref = group_ref(ref_first(r), ref_count(r));  // (a direct leaf: a group of one)
             out.push_back(g);
         }
     }
@@ -574,7 +574,7 @@ struct WideCollapse {
 uint32_t emit_wide(WalkTree& f, const WideCollapse& wc, int32_t n, uint32_t* stack_need) {
     const std::vector<WalkNode>& nodes = wc.nodes;
     const uint32_t rec = f.n();
-    f.ref.resize(f.ref.size() + 4, REF_NONE << 30);
+    f.ref.resize(f.ref.size() + 4, REF_UNUSED);
     f.box.resize(f.box.size() + 24, 0.0);
     int32_t slots[4] = {-1, -1, -1, -1};
     int ns = 0;
@@ -594,7 +594,7 @@ uint32_t emit_wide(WalkTree& f, const WideCollapse& wc, int32_t n, uint32_t* sta
         for (int q = 0; q < 6; q++) f.box[((size_t)rec * 4 + i) * 6 + q] = c.box[q];
     }
     *stack_need = (uint32_t)(ns - 1) + below;
-    return (REF_INTERIOR << 30) | rec;
+    return record_ref(rec);
 }
 
 // The fast walk's tree's leaf slots: every primitive alone behind a box of its own -- its bounding box (the one
@@ -632,11 +632,11 @@ void tight_box(const Aabb& b, const double* gate, double* out) {
 void split_groups(const std::vector<WalkGroup>& groups, const std::vector<Aabb>& prim_box, std::vector<WalkGroup>& out) {
     out.reserve(groups.size() * 3);
     for (const WalkGroup& g : groups) {
-        const uint32_t first = (g.ref & 0x3fffffffu) >> 2, count = (g.ref & 3u) + 1u;
+        const uint32_t first = ref_first(g.ref), count = ref_count(g.ref);
         for (uint32_t i = 0; i < count; i++) {
             WalkGroup r;
             tight_box(prim_box[first + i], g.box, r.box);
-            r.ref = (REF_RANGE << 30) | ((first + i) << 2);
+            r.ref = group_ref(first + i, 1u);
             out.push_back(r);
         }
     }
@@ -682,8 +682,8 @@ void pick_hot_group(FlatScene& f, const std::vector<WalkGroup>& groups) {
     build_tree_over(rest, f.gate_hot);
     const WalkGroup& g = groups[best];
     for (int k = 0; k < 6; k++) f.hot.box[k] = g.box[k];
-    f.hot.first = (g.ref & 0x3fffffffu) >> 2;
-    f.hot.count = (g.ref & 3u) + 1u;
+    f.hot.first = ref_first(g.ref);
+    f.hot.count = ref_count(g.ref);
     f.has_hot = true;  // (the primitives' values are filled in by build_flat_scene, which has the objects)
 }
 
@@ -691,12 +691,12 @@ void pick_hot_group(FlatScene& f, const std::vector<WalkGroup>& groups) {
 void build_walk_trees(FlatScene& f, const std::vector<Aabb>& prim_box) {
     f.walk = WalkTree();
     f.gate = WalkTree();
-    if ((f.root_ref >> 30) != REF_INTERIOR) {  // one bottom Node: its box is root_box, tested by trav_init
+    if (ref_kind(f.root_ref) != REF_INTERIOR) {  // one bottom Node: its box is root_box, tested by trav_init
         f.walk.root_ref = f.gate.root_ref = f.root_ref;
         return;
     }
     std::vector<WalkGroup> groups;
-    collect_groups(f, f.root_ref & 0x3fffffffu, f.root_box, groups);
+    collect_groups(f, ref_record(f.root_ref), f.root_box, groups);
     build_tree_over(groups, f.gate);
     pick_hot_group(f, groups);
     std::vector<WalkGroup> singles;
@@ -706,7 +706,7 @@ void build_walk_trees(FlatScene& f, const std::vector<Aabb>& prim_box) {
 
 inline bool boxes_f32_exact(const WalkTree& t) {
     for (size_t r = 0; r < t.ref.size(); r++) {
-        if ((t.ref[r] >> 30) == REF_NONE) continue;  // box never read
+        if (ref_kind(t.ref[r]) == REF_NONE) continue;  // box never read
         for (int k = 0; k < 6; k++)
             if (!f32_exact(t.box[r * 6 + k])) return false;
     }
@@ -726,7 +726,7 @@ void fill_nodes(WalkTree& t) {
             const uint32_t ref = t.ref[(size_t)r * 4 + ch];
             nodes[r].ref[ch] = ref;
             for (int k = 0; k < 6; k++)
-                nodes[r].box[ch][k] = (ref >> 30) == REF_NONE ? ((k & 1) ? (F)-inf : (F)inf) : (F)t.box[((size_t)r * 4 + ch) * 6 + k];
+                nodes[r].box[ch][k] = ref_kind(ref) == REF_NONE ? ((k & 1) ? (F)-inf : (F)inf) : (F)t.box[((size_t)r * 4 + ch) * 6 + k];
         }
 }
 
@@ -758,7 +758,7 @@ int build_flat_scene(const ObjectList& objs, double z_near, double z_far, int he
         root = b.boxes[0];
         f.prim_object[0] = 0;
         b.next_prim = 1;
-        f.root_ref = (REF_RANGE << 30) | 0u;
+        f.root_ref = group_ref(0u, 1u);
     } else {
         f.root_ref = b.build(0, n, 0, &root);
     }
@@ -851,13 +851,13 @@ int build_flat_scene(const ObjectList& objs, double z_near, double z_far, int he
         }
         // the root record of the tree without the group, as the kernels' records hold it (fill_nodes)
         const WalkTree& t = f.gate_hot;
-        const uint32_t r = t.root_ref & 0x3fffffffu;
+        const uint32_t r = ref_record(t.root_ref);
         const double inf = std::numeric_limits<double>::infinity();
         for (int ch = 0; ch < 4; ch++) {
             const uint32_t ref = t.ref[(size_t)r * 4 + ch];
             f.hot.root_ref[ch] = ref;
             for (int k = 0; k < 6; k++)
-                f.hot.root_box[ch][k] = (ref >> 30) == REF_NONE ? ((k & 1) ? -inf : inf) : t.box[((size_t)r * 4 + ch) * 6 + k];
+                f.hot.root_box[ch][k] = ref_kind(ref) == REF_NONE ? ((k & 1) ? -inf : inf) : t.box[((size_t)r * 4 + ch) * 6 + k];
         }
     }
 

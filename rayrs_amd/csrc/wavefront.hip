@@ -94,7 +94,7 @@ RR_DEV uint32_t compact_window_ready(const WfDev& wf, uint32_t win, uint16_t* li
 
 // A PRE-TESTED ray's READY state (finish_rays) carries, instead of the octant, WHICH slots of the walk tree's first record it
 // enters (bits 3..6; at least one): the traversal kernel starts the walk below those slots -- the record has been tested, by the
-// kernel that made the ray, with the arithmetic and the values trav_interior_step would test it with -- and builds its
+// kernel that made the ray, with the arithmetic and the values trav_record_test would test it with -- and builds its
 // list slot by slot of the FIRST slot entered: the rays a wave takes together start in the same quarter of the scene.
 // A list entry carries the mask above the slot's offset in its window (9 bits).
 RR_DEV uint8_t ready_state_pre(uint32_t mask) { return (uint8_t)(WF_READY | (mask << 3)); }
@@ -1175,21 +1175,28 @@ hipError_t wf_launch_gen(bool compact, const SceneDev& sc, const CameraDev& cam,
     return hipGetLastError();
 }
 
-// The traversal kernel's instances: <COMPACT, COUNT> x the fast walk <false, false>, the default walk <true, false> and
-// the default walk on pre-tested rays <true, true> (a scene with a hot group).
+// The traversal kernel's instances, named here and nowhere else: <COMPACT, COUNT> x the fast walk <false, false>, the
+// default walk <true, false> and the default walk on pre-tested rays <true, true> (a scene with a hot group).
+// f(kernel) for the instance that serves a launch.
+template <class F>
+static auto with_trav_instance(F f, bool compact, bool count, bool exact, bool pre) {
+    return with_bools([&](auto C, auto N, auto X, auto P) { return f(wf_trav_kernel<C(), N(), X(), X() && P()>); },
+                      compact, count, exact, pre);
+}
+
 hipError_t wf_launch_trav(bool compact, bool count, const SceneDev& sc, const RenderDev& rp, const WfDev& wf,
                           uint32_t blocks, hipStream_t stream) {
     const uint32_t lds = wf_trav_lds_bytes(compact, sc.stack_lds, sc.leafq, sc.hot_records);
-    with_bools([&](auto C, auto N, auto X, auto P) {
-        hipLaunchKernelGGL((wf_trav_kernel<C(), N(), X(), X() && P()>), dim3(blocks), dim3(256), lds, stream, sc, rp, wf);
+    with_trav_instance([&](auto* kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, stream, sc, rp, wf);
     }, compact, count, sc.exact != 0u, sc.hot != nullptr);
     return hipGetLastError();
 }
 
 hipError_t wf_trav_occupancy(bool compact, uint32_t lds, int* blocks_per_cu) {
-    return with_bools([&](auto C) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, wf_trav_kernel<C(), false, false, false>, 256, lds);
-    }, compact);
+    return with_trav_instance([&](auto* kernel) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kernel, 256, lds);
+    }, compact, false, false, false);
 }
 
 hipError_t wf_trav_raise_lds(bool compact, uint32_t lds) {
@@ -1201,17 +1208,10 @@ hipError_t wf_trav_raise_lds(bool compact, uint32_t lds) {
     std::lock_guard<std::mutex> lock(mutex);
     uint32_t& set = raised[{device, compact}];
     if (lds <= set) return hipSuccess;
-    e = with_bools([&](auto C) {
-        const void* const instances[] = {
-            reinterpret_cast<const void*>(&wf_trav_kernel<C(), false, false, false>), reinterpret_cast<const void*>(&wf_trav_kernel<C(), true, false, false>),
-            reinterpret_cast<const void*>(&wf_trav_kernel<C(), false, true, false>), reinterpret_cast<const void*>(&wf_trav_kernel<C(), true, true, false>),
-            reinterpret_cast<const void*>(&wf_trav_kernel<C(), false, true, true>), reinterpret_cast<const void*>(&wf_trav_kernel<C(), true, true, true>)};
-        for (const void* k : instances) {
-            const hipError_t ek = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (ek != hipSuccess) return ek;
-        }
-        return hipSuccess;
-    }, compact);
+    for (int i = 0; i < 8 && e == hipSuccess; i++)  // (count, exact, pre): every instance of this layout, some of them twice
+        e = with_trav_instance([&](auto* kernel) {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        }, compact, (i & 1) != 0, (i & 2) != 0, (i & 4) != 0);
     if (e == hipSuccess) set = lds;
     return e;
 }

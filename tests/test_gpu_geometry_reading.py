@@ -7,7 +7,8 @@ tests/test_second_reading_of_geometry_rs.py under three builders.  Two routes:
     rays leave them (finish_rays' pre-test of the hot group and the first record, on a scene with one) and through the
     traversal kernel's rounds, with its LDS record cache, window lists and leaf queue (wavefront.hip).
 
-On the hot-group scenes the trace runs again with the whole gate tree (rayrs_lab hot_group), with each leaf-queue setting of
+On a compact and an f64 scene both walks run with the record test (device_path.h trav_record_test) reading every record from HBM
+and reading the first from LDS.  On the hot-group scenes the trace runs again with the whole gate tree (rayrs_lab hot_group), with each leaf-queue setting of
 test_gpu_hot_group.test_leaf_groups_set_aside_in_any_order_change_nothing, and through a pool of 1024 slots."""
 import functools
 
@@ -50,9 +51,9 @@ def intersect(scene, o, d):
     return t, obj
 
 
-def trace(scene, o, d):
+def trace(scene, o, d, exact=1):
     t, obj, answered = np.zeros(len(o)), np.zeros(len(o), dtype=np.int64), np.zeros(1, dtype=np.uint64)
-    _ffi.check(scene._L.rayrs_test_trace(scene._h, o.ctypes.data, d.ctypes.data, len(o), 1, t.ctypes.data,
+    _ffi.check(scene._L.rayrs_test_trace(scene._h, o.ctypes.data, d.ctypes.data, len(o), exact, t.ctypes.data,
                                          obj.ctypes.data, answered.ctypes.data), "rayrs_test_trace")
     return t, obj, int(answered[0])
 
@@ -128,3 +129,20 @@ def test_the_render_route_answers_as_the_reading_however_it_is_set(scene, how):
         assert answered == 0      # no hot group: no pre-test
     else:
         assert answered > 0
+
+
+@pytest.mark.parametrize("hot_records", [0xffffffff, 1], ids=["every_record_from_hbm", "first_record_from_lds"])
+@pytest.mark.parametrize("scene", ["mesh1280_light", "soup"])
+def test_the_record_test_answers_alike_from_either_source(scene, hot_records):
+    """Both walks' interior steps share one record test, which fetches a record from its LDS copy or from HBM, in the compact
+    (mesh1280_light: with a hot group) and in the f64 layout (soup).  rayrs_lab hot_records says how many records are
+    copied to LDS: none, or the first only, so that one walk reads from both.  The default walk (exact = 1) is held to the
+    reading; the fast walk (exact = 0) promises nothing against the reading and is held to itself under default settings."""
+    rays, spans = scene_rays(scene)
+    sc, info = device_scene(scene, "sah1000")
+    # some records of either walk's tree are left in HBM when the first is in LDS
+    assert info["n_wide"] > 1 and (info["hot_n_wide"] if info["hot_count"] else info["gate_n_wide"]) > 1
+    fast = trace(sc, rays.o, rays.d, exact=0)[:2]
+    sc.lab_set(hot_records=hot_records)
+    assert_same(trace(sc, rays.o, rays.d)[:2], reading(scene, "sah1000"), f"rayrs_test_trace hot_records={hot_records:#x}")
+    assert_same(trace(sc, rays.o, rays.d, exact=0)[:2], fast, f"rayrs_test_trace exact=0 hot_records={hot_records:#x}")

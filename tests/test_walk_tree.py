@@ -5,9 +5,14 @@ culled; the default walk's gate tree with nothing culled)
 and is compared with its restatement of the reference's recursion (traversal 0, bvh.rs:391-415),
 bit for bit, on the cases where a different topology could show: degenerate rays, unhittable flat
 boxes, direct leaves, coincident and abutting primitives (equal-t ties, bvh.rs:62)."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
+import _geometry_reading as G
 import _oracle
 import rayrs_amd
 from rayrs_amd import procedural, scenes
@@ -298,3 +303,48 @@ def test_the_hot_group_is_the_floors_group_on_the_mesh_scenes_and_absent_on_the_
         for k in ("rays", "tri_tests", "sphere_tests", "plane_tests"):
             assert sg[k] == sh[k], k
         assert sh["interior_visits"] <= sg["interior_visits"]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
+def test_the_reference_helpers_of_layout_h_decode_every_exported_reference(tmp_path):
+    """layout.h's ref_kind / ref_record / ref_first / ref_count -- what the builder and every walk take a reference apart
+    with -- on every reference of the three trees a compact scene with a hot group and an f64 scene export, against the
+    decoding spelled out here; every group lies within the scene's primitives.  The helpers are host and device inlines
+    with no entry point of their own: tests/ref_layout_probe.cpp applies them, built with the address and undefined-behaviour
+    sanitizers (linked statically: the program runs whatever else is preloaded)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = tmp_path / "ref_layout_probe"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-static-libasan", "-static-libubsan", "-o", str(exe), os.path.join(here, "ref_layout_probe.cpp")],
+                   check=True, capture_output=True)
+    hdri = procedural.make_hdri(8, 4)
+    for name, compact in (("mesh1280_light", 1), ("soup", 0)):
+        prod = rayrs_amd.Scene(G.SCENES[name](), G.T0, G.T1, G.HEURISTICS["sah1000"], hdri, device=-1)
+        info = prod.info()
+        assert info["compact"] == compact
+        trees = [prod.export_wide()[1], prod.export_gate_tree()[1]]
+        roots = [info["root_ref"], info["gate_root_ref"]]
+        if info["hot_count"]:
+            trees.append(prod.export_hot_tree()[1])
+            roots.append(info["hot_root_ref"])
+        assert (info["hot_count"] >= 1) == (name == "mesh1280_light")
+        refs = np.concatenate([t.reshape(-1) for t in trees] + [np.array(roots, dtype=np.uint32)]).astype(np.uint32)
+        assert len(refs) > 100
+        path = tmp_path / (name + ".refs")
+        refs.tofile(path)
+        out = subprocess.run([str(exe), str(path)], check=True, capture_output=True, text=True)
+        got = np.array(out.stdout.split(), dtype=np.int64).reshape(-1, 4)
+        r = refs.astype(np.int64)
+        assert len(got) == len(r)
+        assert np.array_equal(got[:, 0], r >> 30)
+        assert np.array_equal(got[:, 1], r & 0x3fffffff)
+        assert np.array_equal(got[:, 2], (r & 0x3fffffff) >> 2)
+        assert np.array_equal(got[:, 3], (r & 3) + 1)
+        assert set(np.unique(got[:, 0])) == {0, 1, 3}   # interior slots, leaf groups, unused slots
+        groups = got[got[:, 0] == 1]
+        assert (groups[:, 2] + groups[:, 3] <= info["n_prims"]).all()
+        at = 0
+        for t in trees:   # an interior slot's record is one of its own tree's
+            mine = got[at:at + t.size]
+            assert (mine[mine[:, 0] == 0][:, 1] < len(t)).all()
+            at += t.size
