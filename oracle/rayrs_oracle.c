@@ -2150,6 +2150,55 @@ uint32_t orc_path_trace(const orc_scene* s, const orc_camera* c, uint32_t row, u
     return tr.n;
 }
 
+/* ---- orc_path_trace(cap = 0) for every pixel of the camera and every sample index below n ---- */
+
+typedef struct {
+    const orc_scene* s;
+    const orc_camera* c;
+    uint32_t n, max_bounces;
+    uint64_t seed;
+    int traversal, nthreads, index;
+    double* rgb;
+    uint32_t* iterations;
+} trace_batch_job;
+
+static void* path_trace_batch_worker(void* arg) {
+    trace_batch_job* j = (trace_batch_job*)arg;
+    const uint64_t pixels = (uint64_t)j->c->x_pixels * j->c->y_pixels;
+    for (uint64_t p = (uint64_t)j->index; p < pixels; p += (uint64_t)j->nthreads) {
+        uint32_t row = (uint32_t)(p / j->c->x_pixels), col = (uint32_t)(p % j->c->x_pixels);
+        for (uint32_t sample = 0; sample < j->n; sample++) {
+            uint64_t at = p * j->n + sample;
+            j->iterations[at] = orc_path_trace(j->s, j->c, row, col, sample, j->seed, j->max_bounces, j->traversal, 0, NULL,
+                                               NULL, NULL, NULL, j->rgb + 3 * at);
+        }
+    }
+    return NULL;
+}
+
+/* rgb[(row * x_pixels + col) * n + sample][3] and iterations[(row * x_pixels + col) * n + sample] on nthreads threads. */
+int orc_path_trace_batch(const orc_scene* s, const orc_camera* c, uint32_t n, uint64_t seed, uint32_t max_bounces,
+                         int traversal, int nthreads, double* rgb, uint32_t* iterations) {
+    if (!s || !s->built || !c || !rgb || !iterations) return -2;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    trace_batch_job jobs[256];
+    pthread_t th[256];
+    int started[256];
+    for (int k = 0; k < nthreads; k++) {
+        trace_batch_job j = {s, c, n, max_bounces, seed, traversal, nthreads, k, rgb, iterations};
+        jobs[k] = j;
+    }
+    /* a worker that could not be started is run here: every share of the pixels is traced */
+    for (int k = 1; k < nthreads; k++) started[k] = pthread_create(&th[k], NULL, path_trace_batch_worker, &jobs[k]) == 0;
+    path_trace_batch_worker(&jobs[0]);
+    for (int k = 1; k < nthreads; k++) {
+        if (started[k]) pthread_join(th[k], NULL);
+        else path_trace_batch_worker(&jobs[k]);
+    }
+    return 0;
+}
+
 uint32_t orc_radiance(const orc_scene* s, const double o[3], const double d[3], uint32_t max_bounces, uint64_t key,
                       uint32_t* draw, int traversal, double rgb[3]) {
     rng_t rng = {key, *draw};

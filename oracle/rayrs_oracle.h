@@ -175,6 +175,11 @@ void orc_primary_ray(const orc_camera* c, uint32_t i, uint32_t j, uint64_t key, 
 uint32_t orc_path_trace(const orc_scene* s, const orc_camera* c, uint32_t row, uint32_t col, uint32_t sample, uint64_t seed,
                         uint32_t max_bounces, int traversal, uint32_t cap, int64_t* obj, double* t, double* thr,
                         uint32_t* draw, double rgb[3]);
+/* orc_path_trace(cap = 0) for every pixel of the camera and every sample index below n, on nthreads threads: radiance()'s
+ * value into rgb[((row * x_pixels + col) * n + sample) * 3 ..] and the number of loop iterations into
+ * iterations[(row * x_pixels + col) * n + sample]. */
+int orc_path_trace_batch(const orc_scene* s, const orc_camera* c, uint32_t n, uint64_t seed, uint32_t max_bounces,
+                         int traversal, int nthreads, double* rgb, uint32_t* iterations);
 /* radiance() for one path; returns number of BVH queries. */
 uint32_t orc_radiance(const orc_scene* s, const double o[3], const double d[3], uint32_t max_bounces, uint64_t key,
                       uint32_t* draw, int traversal, double rgb[3]);

@@ -1,6 +1,7 @@
 """What the progressive film's tests (test_film.py, test_gpu_film.py) expect, computed from the CPU oracle alone: the
 frame from OracleScene.render(spp=N, sample_chunk=c), and the chunk sums, S1, S2 and the converged count of
-include/rayrs_hip.h (NOISE) from OracleScene.path_traces(...)["rgb"] -- one radiance per pixel and sample index --
+include/rayrs_hip.h (NOISE) from OracleScene.path_trace_batch -- one radiance per pixel and sample index, what
+path_traces(...)["rgb"] holds --
 summed in numpy f64 in the stated order.  Nothing here calls the library under test."""
 import functools
 
@@ -38,11 +39,7 @@ def oracle_of(desc):
 
 def traces(osc, ocam, n, seed=SEED, bounces=BOUNCES):
     """rgb[row, col, s] = the radiance of sample s of the pixel, s < n, as orc_render computes it."""
-    h, w = ocam.y_pixels(), ocam.x_pixels()
-    pixels = [(r, c) for r in range(h) for c in range(w) for _ in range(n)]
-    samples = [s for _ in range(h * w) for s in range(n)]
-    tr = osc.path_traces(ocam, pixels, samples, seed, bounces, cap=4)
-    return np.ascontiguousarray(tr["rgb"]).reshape(h, w, n, 3)
+    return osc.path_trace_batch(ocam, n, seed, bounces)[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -73,14 +70,19 @@ def expectation(rgb, c, n):
     return frame, s1, s2, m
 
 
-def noise_counts(s1, s2, m, tau, mask=None):
-    """(unconverged, nonfinite) among the pixels of mask (default: all), by the header's predicate in its order."""
-    if mask is None:
-        mask = np.ones(s1.shape, dtype=bool)
+def noise_masks(s1, s2, m, tau):
+    """(unconverged, nonfinite) per pixel, by the header's predicate in its order."""
     mf = float(m)
     with np.errstate(all="ignore"):
         s11 = s1 * s1
         converged = (mf * s2 - s11 <= ((tau * tau) * s11) * (mf - 1.0)) & (m >= 2)
     nonfinite = ~(np.isfinite(s1) & np.isfinite(s2))
-    unconverged = ~nonfinite & ~converged
+    return ~nonfinite & ~converged, nonfinite
+
+
+def noise_counts(s1, s2, m, tau, mask=None):
+    """(unconverged, nonfinite) among the pixels of mask (default: all)."""
+    if mask is None:
+        mask = np.ones(s1.shape, dtype=bool)
+    unconverged, nonfinite = noise_masks(s1, s2, m, tau)
     return int((unconverged & mask).sum()), int((nonfinite & mask).sum())

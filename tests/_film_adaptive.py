@@ -16,11 +16,8 @@ CURSOR_MAX = (1 << 30) - 1
 
 def traces(osc, ocam, n, seed=SEED, bounces=BOUNCES, traversal=0):
     """(rgb[row, col, s, 3], iterations[row, col, s]) of the samples s < n of every pixel, as orc_render runs them."""
-    h, w = ocam.y_pixels(), ocam.x_pixels()
-    pixels = [(r, c) for r in range(h) for c in range(w) for _ in range(n)]
-    samples = [s for _ in range(h * w) for s in range(n)]
-    tr = osc.path_traces(ocam, pixels, samples, seed, bounces, cap=4, traversal=traversal)
-    return np.ascontiguousarray(tr["rgb"]).reshape(h, w, n, 3), tr["n"].astype(np.uint64).reshape(h, w, n)
+    rgb, it = osc.path_trace_batch(ocam, n, seed, bounces, traversal=traversal)
+    return rgb, it.astype(np.uint64)
 
 
 @functools.lru_cache(maxsize=None)
@@ -31,7 +28,14 @@ def named_traces(name, n=CAP, w=W, h=H):
 
 class Replay:
     """A film as the header defines it, held as the per-tile sample counts N_t alone: everything else follows from the
-    traces.  tile_rank / tile_ranks: the share, tiles t of the frame (row-major) with t % ranks == rank."""
+    traces.  tile_rank / tile_ranks: the share, tiles t of the frame (row-major) with t % ranks == rank.
+
+    Vectorised, so that frames of thousands of tiles replay in seconds: whatever is asked per tile is computed for the
+    whole image once per distinct N_t (at) and then taken, or reduced, over the pixels whose tile holds that N_t.  This
+    relies on two things.  A pixel's sums, frame value and predicate depend on its own samples and its tile's N_t alone,
+    so the image evaluated at N is, on a tile with N_t = N, that tile evaluated alone -- bit for bit, the same numpy
+    operations on the same operands.  And what is reduced over pixels or tiles are counts -- integers, whose sum has no
+    order."""
 
     def __init__(self, rgb, iterations, c=C, rank=0, ranks=1):
         self.rgb, self.it, self.c = rgb, iterations, c
@@ -42,6 +46,7 @@ class Replay:
         self.share = (index % ranks) == rank
         self.closed = False
         self._at = {}
+        self._tile_counts = {}   # tau -> (unconverged[ty, tx], nonfinite[ty, tx]) for self.nt as it stands
 
     def at(self, n):
         """(frame, S1, S2, M) of the whole image after n samples per pixel; n = 0 is the empty film."""
@@ -51,79 +56,105 @@ class Replay:
             self._at[n] = _film.expectation(self.rgb, self.c, n) if n else (np.zeros((self.h, self.w, 3)), zero, zero, 0)
         return self._at[n]
 
+    def per_pixel(self, per_tile):
+        """A per-tile array spread over the tiles' pixels in the image (clipped at its edge: padding is no pixel)."""
+        return np.repeat(np.repeat(per_tile, 8, axis=0), 8, axis=1)[:self.h, :self.w]
+
+    def per_tile(self, per_pixel):
+        """The per-tile sums of a per-pixel array of counts."""
+        padded = np.zeros((self.ty * 8, self.tx * 8), dtype=np.int64)
+        padded[:self.h, :self.w] = per_pixel
+        return padded.reshape(self.ty, 8, self.tx, 8).sum(axis=(1, 3))
+
     def tile_pixels(self, ty, tx):
         mask = np.zeros((self.h, self.w), dtype=bool)
         mask[ty * 8:ty * 8 + 8, tx * 8:tx * 8 + 8] = True   # (clipped at the image's edge: padding is no pixel)
         return mask
 
     def tiles(self):
-        return [(ty, tx) for ty in range(self.ty) for tx in range(self.tx) if self.share[ty, tx]]
+        return [(int(ty), int(tx)) for ty, tx in np.argwhere(self.share)]   # (row-major: ascending tile order)
+
+    def levels(self):
+        """(N, the share's pixels whose tile holds N samples) for every distinct N_t in the share."""
+        nt_px, share_px = self.per_pixel(self.nt), self.per_pixel(self.share)
+        return [(int(n), share_px & (nt_px == n)) for n in np.unique(self.nt[self.share])]
+
+    def all_tile_counts(self, tau):
+        """(unconverged[ty, tx], nonfinite[ty, tx]) among each tile's pixels, with the tile's own M; 0 outside the share."""
+        if tau not in self._tile_counts:
+            unc, nonf = np.zeros((self.h, self.w), dtype=bool), np.zeros((self.h, self.w), dtype=bool)
+            for n, px in self.levels():
+                _, s1, s2, m = self.at(n)
+                u, f = _film.noise_masks(s1, s2, m, tau)
+                unc[px], nonf[px] = u[px], f[px]
+            self._tile_counts[tau] = self.per_tile(unc), self.per_tile(nonf)
+        return self._tile_counts[tau]
 
     def tile_counts(self, ty, tx, tau):
         """(unconverged, nonfinite) among the tile's pixels, with the tile's own M."""
-        _, s1, s2, m = self.at(self.nt[ty, tx])
-        return _film.noise_counts(s1, s2, m, tau, self.tile_pixels(ty, tx))
+        unc, nonf = self.all_tile_counts(tau)
+        return int(unc[ty, tx]), int(nonf[ty, tx])
 
     def counts(self, tau):
-        per_tile = [self.tile_counts(ty, tx, tau) for ty, tx in self.tiles()]
-        return sum(u for u, _ in per_tile), sum(f for _, f in per_tile)
+        unc, nonf = self.all_tile_counts(tau)
+        return int(unc.sum()), int(nonf.sum())
 
     def frame(self):
         out = np.zeros((self.h, self.w, 3))
-        for ty, tx in self.tiles():
-            m = self.tile_pixels(ty, tx)
-            out[m] = self.at(self.nt[ty, tx])[0][m]
+        for n, px in self.levels():
+            out[px] = self.at(n)[0][px]
         return out
 
     def sums(self):
         """S1 and S2 per pixel, each tile at its own count."""
         s1, s2 = np.zeros((self.h, self.w)), np.zeros((self.h, self.w))
-        for ty, tx in self.tiles():
-            m = self.tile_pixels(ty, tx)
-            s1[m], s2[m] = self.at(self.nt[ty, tx])[1][m], self.at(self.nt[ty, tx])[2][m]
+        for n, px in self.levels():
+            s1[px], s2[px] = self.at(n)[1][px], self.at(n)[2][px]
         return s1, s2
+
+    def select_mask(self, n, tau, cap=0):
+        cap = min(cap, CURSOR_MAX) if cap else CURSOR_MAX
+        return self.share & (self.nt.astype(np.int64) + n <= cap) & (self.all_tile_counts(tau)[0] > 0)
 
     def select(self, n, tau, cap=0):
         """The tiles a pass of n samples takes: room below the cap, and a pixel in the image that is unconverged at tau."""
-        cap = min(cap, CURSOR_MAX) if cap else CURSOR_MAX
-        return [(ty, tx) for ty, tx in self.tiles()
-                if int(self.nt[ty, tx]) + n <= cap and self.tile_counts(ty, tx, tau)[0] > 0]
+        return [(int(ty), int(tx)) for ty, tx in np.argwhere(self.select_mask(n, tau, cap))]
 
-    def _add(self, tiles, n):
+    def _add(self, active, n):
+        """n more samples for the tiles of the mask `active`: (rays, paths) of them."""
         rays = paths = 0
-        for ty, tx in tiles:
-            n0 = int(self.nt[ty, tx])
-            window = self.it[ty * 8:ty * 8 + 8, tx * 8:tx * 8 + 8, n0:n0 + n]
-            assert window.shape[2] == n, "the traces are shorter than the film"
-            rays += int(window.sum())
-            paths += int(window.size)
-            self.nt[ty, tx] = n0 + n
+        nt_px, active_px = self.per_pixel(self.nt), self.per_pixel(active)
+        for n0 in np.unique(self.nt[active]):
+            n0 = int(n0)
+            assert n0 + n <= self.it.shape[2], "the traces are shorter than the film"
+            px = active_px & (nt_px == n0)
+            rays += int(self.it[px][:, n0:n0 + n].sum())
+            paths += int(px.sum()) * n
+        self.nt[active] += np.uint32(n)
+        self._tile_counts = {}
         return rays, paths
 
     def snapshot(self, active, rays, paths, tau):
         s1, s2 = self.sums()
         unc, nonf = self.counts(tau)
-        mask = np.zeros((self.ty, self.tx), dtype=bool)
-        for ty, tx in active:
-            mask[ty, tx] = True
-        return dict(active=mask, active_tiles=len(active), nt=self.nt.copy(), frame=self.frame(), s1=s1, s2=s2,
+        return dict(active=active.copy(), active_tiles=int(active.sum()), nt=self.nt.copy(), frame=self.frame(), s1=s1, s2=s2,
                     unconverged=unc, nonfinite=nonf, rays=rays, paths=paths)
 
     def adaptive_pass(self, n, tau, cap=0):
         assert n > 0 and n % self.c == 0 and not self.closed
-        active = self.select(n, tau, cap)
+        active = self.select_mask(n, tau, cap)
         rays, paths = self._add(active, n)
         return self.snapshot(active, rays, paths, tau)
 
     def uniform_pass(self, n, tau=TAU):
         assert n > 0 and not self.closed
-        active = self.tiles()
+        active = self.share
         rays, paths = self._add(active, n)
         self.closed = n % self.c != 0
         return self.snapshot(active, rays, paths, tau)
 
     def pixel_samples(self):
-        return sum(int(self.nt[ty, tx]) * int(self.tile_pixels(ty, tx).sum()) for ty, tx in self.tiles())
+        return int(self.per_pixel(self.nt)[self.per_pixel(self.share)].sum(dtype=np.int64))
 
 
 def replay_until(rep, tau=TAU, step=PASS, cap=CAP):

@@ -107,6 +107,7 @@ def lib():
     L.orc_path_trace.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp,
                                  C.POINTER(C.c_double)]
     L.orc_path_trace.restype = C.c_uint32
+    L.orc_path_trace_batch.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp, vp]
     L.orc_set_cull_margin.argtypes = [C.c_double]
     L.orc_set_cull_margin.restype = None
     L.orc_set_math_mode.argtypes = [C.c_int]
@@ -356,6 +357,17 @@ class OracleScene:
             out["n"][i] = n
             out["obj"][i], out["t"][i], out["thr"][i], out["draw"][i], out["rgb"][i] = obj, t, thr, dr, rgb[:]
         return out
+
+    def path_trace_batch(self, cam, n, seed, max_bounces=50, traversal=0, nthreads=None):
+        """path_traces' `rgb` and `n` for the samples s < n of every pixel of the camera, in one call on all cores:
+        (rgb[row, col, s, 3] f64, iterations[row, col, s] u32)."""
+        h, w = cam.y_pixels(), cam.x_pixels()
+        rgb = np.zeros((h, w, n, 3))
+        it = np.zeros((h, w, n), dtype=np.uint32)
+        rc = self._L.orc_path_trace_batch(self._h, C.byref(cam.desc), int(n), int(seed), int(max_bounces), int(traversal),
+                                          int(nthreads or os.cpu_count() or 1), rgb.ctypes.data, it.ctypes.data)
+        assert rc == 0
+        return rgb, it
 
     def radiance(self, o, d, max_bounces, key, draw=0, traversal=0):
         rgb = (C.c_double * 3)()
