@@ -801,6 +801,20 @@ RR_DEV bool bvh_intersect(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack
     return tv.best_prim != 0xffffffffu;
 }
 
+// ---- one-lane queries (kernels.hip's self-test kernels, features.hip): every lane of a 256-thread workgroup its own ray.
+// The lane's stack: sc.stack_lds entries and the spare in the workgroup's dynamic LDS (launch_dispatch.h
+// lane_stacks_lds_bytes), the rest in the strip `spill`, one word per thread of the grid per entry (as in the traversal kernel).
+RR_DEV LaneStack lane_stack(uint32_t* lds, uint32_t* spill, const SceneDev& sc) {
+    return LaneStack{lds + (size_t)(threadIdx.x >> 6) * (sc.stack_lds + 1u) * 64u + (threadIdx.x & 63u),
+                     spill + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x), sc.stack_lds, gridDim.x * blockDim.x};
+}
+template <bool COMPACT>  // the query, by the walk the scene names (sc.exact: the default walk)
+RR_DEV bool lane_query(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack, double& t_hit, uint32_t& prim_hit) {
+    WorkCount wc{0, 0, 0, 0, 0};
+    return sc.exact ? bvh_intersect<COMPACT, false, true>(sc, o, d, stack, t_hit, prim_hit, wc)
+                    : bvh_intersect<COMPACT, false, false>(sc, o, d, stack, t_hit, prim_hit, wc);
+}
+
 // ---------------------------------------------------------------- materials
 
 struct CtLayer {  // struct CookTorrance, material.rs:194-200
@@ -1185,6 +1199,71 @@ RR_DEV void primary_ray(const CameraDev& cam, uint32_t i, uint32_t j, Rng& rng, 
     const V3 ex = mk(cam.e_x[0], cam.e_x[1], cam.e_x[2]);
     const V3 ey = mk(cam.e_y[0], cam.e_y[1], cam.e_y[2]);
     d = v_add(v_add(mk(cam.z[0], cam.z[1], cam.z[2]), v_scale(ex, x)), v_scale(ey, y));
+}
+
+// ----------------------------------------------------------------- radiance
+// radiance() (lib.rs:521-560) and a sample's start (main.rs:67-79), once, for the kernels that run them: wavefront.hip
+// (next_sample, wf_hit_kernel, wf_miss_kernel), local_pool.hip (lp_gen, lp_isect, lp_shade, lp_background), kernels.hip
+// (test_path_trace_kernel) and features.hip.  The order of the f64 operations is what the routes' bit-for-bit agreement rests on.
+
+// A sample's start (main.rs:68-76): its RNG key, from the image pixel and the sample's number, and its primary ray.
+RR_DEV uint64_t sample_key(uint64_t seed, const CameraDev& cam, uint32_t row, uint32_t col, uint32_t sample) {
+    return rr_path_key(seed, (uint64_t)row * cam.W + col, (uint64_t)sample);
+}
+RR_DEV void sample_ray(const CameraDev& cam, uint32_t row, uint32_t col, Rng& rng, V3& o, V3& d) {
+    primary_ray(cam, cam.H - row, cam.W - col, rng, o, d);  // image origin is upper left, camera origin lower right (main.rs:74-75)
+}
+
+// A closest hit, in two halves (the local pool makes the position in one phase and the rest in another): the position
+// (lib.rs:528), and what Material::evaluate is handed there (lib.rs:528-529) with the hit surface's row.
+RR_DEV V3 hit_position(V3 o, V3 d, double t) { return v_add(o, v_scale(d, t)); }
+struct HitPoint {
+    V3 normal, view;
+    uint32_t sid;  // row of SceneDev::surfaces
+};
+template <bool COMPACT>
+RR_DEV HitPoint hit_point(const PrimRec<COMPACT>& rec, V3 position, V3 d) {
+    return HitPoint{prim_normal<COMPACT>(rec, position), v_unit(v_scale(d, -1.0)), rec.tag() >> 8};
+}
+
+// One turn of the loop on a surface that scatters (lib.rs:530-547): the surface's emission (SurfaceDev::emit), throughput,
+// roulette on the draw `u` (taken by the caller where the reference takes it, lib.rs:539), the loop's bound (lib.rs:525:
+// this is turn `bounce`, 1-based) and DivAssign (vecmath.rs:708-714).  True: the path goes on; false: radiance() returns light.
+constexpr uint32_t NO_BOUNCE_BOUND = 0xffffffffu;  // for a caller whose own loop is lib.rs:525's
+RR_DEV bool bounce_step(V3 color, const double* emit, double u, uint32_t bounce, uint32_t max_bounces, V3& thr, V3& light) {
+    light = v_add(light, v_mul(thr, mk(emit[0], emit[1], emit[2])));
+    thr = v_mul(thr, color);
+    const double p = rr_max(rr_max(thr.x, thr.y), thr.z);
+    if (u > p) return false;
+    if (bounce >= max_bounces) return false;
+    thr = mk(thr.x / p, thr.y / p, thr.z / p);
+    return true;
+}
+
+// A path that leaves the scene (lib.rs:555).
+RR_DEV V3 escape(const SceneDev& sc, V3 d, V3 thr, V3 light) { return v_add(light, v_mul(thr, background(sc, d))); }
+
+// A path's light is exactly +0 until it meets an emitter (or its throughput stops being finite): such paths keep no light
+// (wavefront.h SLOT_LIGHT_BIT).  Bitwise: -0 and NaN are not +0.
+RR_DEV bool light_is_plus_zero(V3 light) {
+    return (rr_f64_bits(light.x) | rr_f64_bits(light.y) | rr_f64_bits(light.z)) == 0ull;
+}
+
+// Sum over the 64 lanes (every lane must call it); the result is valid in lane 0 (and all lanes).
+RR_DEV unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// One atomic per wave for a per-lane counter.
+RR_DEV void wave_atomic_add(unsigned long long* dst, unsigned long long v) {
+    const unsigned long long s = wave_sum(v);
+    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(dst, s);
 }
 
 }  // namespace rayrs

@@ -4,6 +4,7 @@
 
 #include "device_path.h"
 #include "kernels.h"
+#include "launch_dispatch.h"
 
 namespace rayrs {
 
@@ -60,8 +61,6 @@ hipError_t launch_accumulate(void* dst, const void* src, size_t n, bool f64, hip
 
 // ------------------------------------------------------------ launch glue
 
-static inline uint32_t lds_bytes_for(uint32_t stack_depth) { return 4u * 64u * (stack_depth + 1u) * 4u; }  // + the spare entry
-
 hipError_t launch_resolve(const CameraDev& cam, const RenderDev& rp, uint32_t lt0, uint32_t n_lt, hipStream_t stream) {
     const uint64_t n = (uint64_t)n_lt * 64u;
     if (n == 0) return hipSuccess;
@@ -111,44 +110,32 @@ template <bool COMPACT>
 __global__ void __launch_bounds__(256) test_intersect_kernel(SceneDev sc, const double* o, const double* d, uint64_t n,
                                                              double* t_out, long long* prim_out, uint32_t* spill) {
     extern __shared__ uint32_t lds_stack[];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = threadIdx.x >> 6;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // sc.stack_lds entries of the stack in LDS, the rest in the strip `spill` (as in the traversal kernel)
-    const LaneStack stack{lds_stack + (size_t)wave * (sc.stack_lds + 1u) * 64u + lane, spill + i, sc.stack_lds,
-                          gridDim.x * blockDim.x};
+    const LaneStack stack = lane_stack(lds_stack, spill, sc);
     if (i >= n) return;
     double t = 0.0;
     uint32_t prim = 0;
-    WorkCount wc{0, 0, 0, 0, 0};
     const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
-    const bool hit = sc.exact ? bvh_intersect<COMPACT, false, true>(sc, ro, rd, stack, t, prim, wc)
-                              : bvh_intersect<COMPACT, false, false>(sc, ro, rd, stack, t, prim, wc);
+    const bool hit = lane_query<COMPACT>(sc, ro, rd, stack, t, prim);
     t_out[i] = hit ? t : 0.0;
     prim_out[i] = hit ? (long long)prim : -1ll;
 }
 
 hipError_t launch_test_intersect(bool compact, const SceneDev& sc, const double* o, const double* d, uint64_t n,
                                  double* t_out, long long* prim_out, uint32_t* spill, hipStream_t stream) {
-    const uint32_t lds = lds_bytes_for(sc.stack_lds);
+    const uint32_t lds = lane_stacks_lds_bytes(sc.stack_lds);
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    if (compact) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&test_intersect_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(test_intersect_kernel<true>, dim3(blocks), dim3(256), lds, stream, sc, o, d, n, t_out,
-                           prim_out, spill);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&test_intersect_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(test_intersect_kernel<false>, dim3(blocks), dim3(256), lds, stream, sc, o, d, n, t_out,
-                           prim_out, spill);
-    }
-    return hipGetLastError();
+    return with_bools([&](auto C) {
+        const hipError_t e = raise_dynamic_lds(test_intersect_kernel<C()>, lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(test_intersect_kernel<C()>, dim3(blocks), dim3(256), lds, stream, sc, o, d, n, t_out, prim_out, spill);
+        return hipGetLastError();
+    }, compact);
 }
 
-// One sample exactly as the path kernels run it -- the path key, the primary ray (wavefront.hip next_sample), then the
-// loop of lib.rs:521-560 with the device functions of device_path.h -- in ONE lane from the first ray to the last, with
-// its trace: per loop iteration the primitive the query found (0xffffffff: none), its t, and the throughput and the
+// One sample as the path kernels run it -- device_path.h's radiance section, the functions they call: the sample's start,
+// then per turn of the loop of lib.rs:521-560 the hit point and the bounce, or the escape -- in ONE lane from the first ray
+// to the last, with its trace: per loop iteration the primitive the query found (0xffffffff: none), its t, and the throughput and the
 // RNG's draw index on leaving the iteration (rayrs_selftest.h rayrs_test_path_trace; the CPU checker keeps the same).
 template <bool COMPACT>
 __global__ void __launch_bounds__(256) test_path_trace_kernel(SceneDev sc, CameraDev cam, uint64_t seed, uint32_t max_bounces,
@@ -157,16 +144,13 @@ __global__ void __launch_bounds__(256) test_path_trace_kernel(SceneDev sc, Camer
                                                               double* thr_out, uint32_t* draw_out, double* rgb_out,
                                                               uint32_t* spill) {
     extern __shared__ uint32_t lds_stack[];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = threadIdx.x >> 6;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const LaneStack stack{lds_stack + (size_t)wave * (sc.stack_lds + 1u) * 64u + lane, spill + i, sc.stack_lds,
-                          gridDim.x * blockDim.x};
+    const LaneStack stack = lane_stack(lds_stack, spill, sc);
     if (i >= n) return;
     const uint32_t row = pix[i] >> 16, col = pix[i] & 0xffffu;
-    Rng rng{rr_path_key(seed, (uint64_t)row * cam.W + col, (uint64_t)sample[i]), 0};
+    Rng rng{sample_key(seed, cam, row, col, sample[i]), 0};
     V3 o, d;
-    primary_ray(cam, cam.H - row, cam.W - col, rng, o, d);  // image origin is upper left, camera origin lower right (main.rs:74-75)
+    sample_ray(cam, row, col, rng, o, d);
     V3 thr = mk(1.0, 1.0, 1.0), light = mk(0.0, 0.0, 0.0), result = mk(0.0, 0.0, 0.0);
     uint32_t b = 0;
     bool returned = false;
@@ -177,40 +161,26 @@ __global__ void __launch_bounds__(256) test_path_trace_kernel(SceneDev sc, Camer
             thr_out[3 * at] = thr.x, thr_out[3 * at + 1] = thr.y, thr_out[3 * at + 2] = thr.z;
         }
     };
+    // (this `for` is lib.rs:525's and the bounce is told of no bound: the trace keeps the last turn's throughput divided, as
+    // the reference leaves it, where a kernel that ends a path at the bound skips the division nobody reads)
     for (; b < max_bounces && !returned; b++) {
         double t = 0.0;
         uint32_t prim = 0xffffffffu;
-        WorkCount wc{0, 0, 0, 0, 0};
-        const bool hit = sc.exact ? bvh_intersect<COMPACT, false, true>(sc, o, d, stack, t, prim, wc)
-                                  : bvh_intersect<COMPACT, false, false>(sc, o, d, stack, t, prim, wc);
-        if (!hit) {
+        if (!lane_query<COMPACT>(sc, o, d, stack, t, prim)) {
             put(0xffffffffu, 0.0);
-            result = v_add(light, v_mul(thr, background(sc, d)));  // lib.rs:555
+            result = escape(sc, d, thr, light);
             returned = true;
             continue;
         }
         const PrimRec<COMPACT> rec = load_prim<COMPACT>(sc.prims, prim);
-        const V3 position = v_add(o, v_scale(d, t));
-        const V3 normal = prim_normal<COMPACT>(rec, position);
-        const V3 view = v_unit(v_scale(d, -1.0));
-        const SurfaceDev* surf = sc.surfaces + (rec.tag() >> 8);
-        const Scatter ev = material_evaluate(surf, normal, view, rng);
-        if (!ev.scatter) {  // lib.rs:550
-            put(prim, t);
-            result = light, returned = true;
-            continue;
-        }
-        light = v_add(light, v_mul(thr, mk(surf->emit[0], surf->emit[1], surf->emit[2])));
-        thr = v_mul(thr, ev.color);
-        const double p = rr_max(rr_max(thr.x, thr.y), thr.z);
-        if (rng.next() > p) {
-            put(prim, t);
-            result = light, returned = true;
-            continue;
-        }
-        thr = mk(thr.x / p, thr.y / p, thr.z / p);  // DivAssign, vecmath.rs:708-714
-        o = position, d = ev.dir;
+        const V3 position = hit_position(o, d, t);
+        const HitPoint hp = hit_point<COMPACT>(rec, position, d);
+        const SurfaceDev* surf = sc.surfaces + hp.sid;
+        const Scatter ev = material_evaluate(surf, hp.normal, hp.view, rng);
+        const bool goes_on = ev.scatter && bounce_step(ev.color, surf->emit, rng.next(), b + 1u, NO_BOUNCE_BOUND, thr, light);
         put(prim, t);
+        if (goes_on) o = position, d = ev.dir;
+        else result = light, returned = true;  // lib.rs:550, or the roulette
     }
     if (!returned) result = light;  // lib.rs:559
     n_out[i] = b;
@@ -221,20 +191,15 @@ hipError_t launch_test_path_trace(bool compact, const SceneDev& sc, const Camera
                                   const uint32_t* pix, const uint32_t* sample, uint64_t n, uint32_t cap, uint32_t* n_out,
                                   uint32_t* prim_out, double* t_out, double* thr_out, uint32_t* draw_out, double* rgb_out,
                                   uint32_t* spill, hipStream_t stream) {
-    const uint32_t lds = lds_bytes_for(sc.stack_lds);
+    const uint32_t lds = lane_stacks_lds_bytes(sc.stack_lds);
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    if (compact) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&test_path_trace_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(test_path_trace_kernel<true>, dim3(blocks), dim3(256), lds, stream, sc, cam, seed, max_bounces, pix,
+    return with_bools([&](auto C) {
+        const hipError_t e = raise_dynamic_lds(test_path_trace_kernel<C()>, lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(test_path_trace_kernel<C()>, dim3(blocks), dim3(256), lds, stream, sc, cam, seed, max_bounces, pix,
                            sample, n, cap, n_out, prim_out, t_out, thr_out, draw_out, rgb_out, spill);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&test_path_trace_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(test_path_trace_kernel<false>, dim3(blocks), dim3(256), lds, stream, sc, cam, seed, max_bounces, pix,
-                           sample, n, cap, n_out, prim_out, t_out, thr_out, draw_out, rgb_out, spill);
-    }
-    return hipGetLastError();
+        return hipGetLastError();
+    }, compact);
 }
 
 __global__ void test_material_kernel(const SurfaceDev* surf, const double* normal, const double* view,

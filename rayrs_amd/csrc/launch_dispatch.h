@@ -1,5 +1,10 @@
-// launch_dispatch.h -- run-time bools into template arguments, for the launch glue of wavefront.hip and local_pool.hip.
+// launch_dispatch.h -- what the launch glue of the .hip files shares: run-time bools into template arguments, a kernel's
+// dynamic-LDS limit, and the LDS of a launch whose lanes each walk the tree with a stack of their own.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <mutex>
 #include <type_traits>
 
 namespace rayrs {
@@ -13,5 +18,28 @@ auto with_bools(F f, bool b, Rest... rest) {
     return b ? with_bools([&](auto... cs) { return f(std::true_type{}, cs...); }, rest...)
              : with_bools([&](auto... cs) { return f(std::false_type{}, cs...); }, rest...);
 }
+
+// A kernel's dynamic-LDS limit belongs to the kernel on a device, not to a scene or a launch, and every thread of the
+// process that launches the kernel shares it: it is only ever raised, so that at every launch it is at least what the
+// launch asks for -- set to each launch's own size, one thread could lower it between another's set and its launch.
+template <class... Args>
+hipError_t raise_dynamic_lds(void (*kernel_fn)(Args...), uint32_t lds) {
+    static std::mutex mutex;  // (mutex and map are per kernel signature, which is enough: a kernel has one)
+    static std::map<std::pair<int, const void*>, uint32_t> raised;  // (device, kernel): what its limit there was last set to
+    const void* kernel = reinterpret_cast<const void*>(kernel_fn);
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(mutex);
+    uint32_t& set = raised[{device, kernel}];
+    if (lds <= set) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) set = lds;
+    return e;
+}
+
+// Dynamic LDS of a 256-thread workgroup of one-lane queries (device_path.h lane_stack): four waves' stacks of
+// stack_lds entries and the spare one.
+inline uint32_t lane_stacks_lds_bytes(uint32_t stack_lds) { return 4u * 64u * (stack_lds + 1u) * 4u; }
 
 }  // namespace rayrs

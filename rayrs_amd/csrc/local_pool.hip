@@ -22,8 +22,9 @@
 //   * an item (pixel, sample chunk) belongs to one path slot, which runs its samples one after the other,
 //     so they are summed in order (main.rs:67-69); items come from a device-wide counter, a few dozen at
 //     a time per wave.
-// The arithmetic is device_path.h's, the same functions the streaming kernels call: frames are identical
-// bit for bit on either route (tests/test_gpu_local_pool.py renders both and the oracle).
+// The arithmetic is device_path.h's, the same functions the streaming kernels call -- the materials, the background, and
+// the loop around them (its "radiance" section: sample start, hit point, bounce, escape): frames are identical bit for
+// bit on either route (tests/test_gpu_local_pool.py renders both, the oracle and the self test's lane-by-lane samples).
 #include <hip/hip_runtime.h>
 
 #include "device_path.h"
@@ -113,8 +114,8 @@ RR_DEV uint32_t lp_gen(const Pool& pl, bool valid, uint32_t p, const SceneDev& s
                        V3& ray_inv) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = pl.u(U_SCUR, p);
-    bool has_item = valid && (w >> 31) != 0u;
-    uint32_t s_cur = w & SLOT_SAMPLE_MASK, item = pl.u(U_ITEM, p);
+    bool has_item = valid && slot_has_item(w);
+    uint32_t s_cur = slot_cursor(w), item = pl.u(U_ITEM, p);
     uint32_t row, col, s_end, s_first;
     item_geometry(rp, item, row, col, s_first, s_end);  // (of no meaning without an item)
     if (has_item && s_cur >= s_end) {  // the item's sum goes to the resolve kernel
@@ -165,12 +166,9 @@ RR_DEV uint32_t lp_gen(const Pool& pl, bool valid, uint32_t p, const SceneDev& s
     uint32_t ns = LP_DEAD;
     if (valid && dead) pl.u(U_SCUR, p) = 0u;
     if (valid && !dead) {
-        Rng rng;
-        rng.key = rr_path_key(rp.seed, (uint64_t)row * cam.W + col, (uint64_t)s_cur);
-        rng.draw = 0;
+        Rng rng{sample_key(rp.seed, cam, row, col, s_cur), 0};
         V3 o, d;
-        // image origin is upper left, camera origin lower right (main.rs:74-75)
-        primary_ray(cam, cam.H - row, cam.W - col, rng, o, d);
+        sample_ray(cam, row, col, rng, o, d);
         n.paths++;
         s_cur++;
         const V3 inv = mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
@@ -241,7 +239,7 @@ RR_DEV uint32_t lp_isect(const Pool& pl, bool valid, uint32_t p, V3 gen_o, V3 ge
     }
     uint32_t ns = LP_BG;
     if (best_prim != 0xffffffffu) {  // (never for a lane without a path: `in` is false there)
-        pl.set_v3(F_OX, p, v_add(o, v_scale(d, best_t)));  // position, lib.rs:528
+        pl.set_v3(F_OX, p, hit_position(o, d, best_t));
         pl.u(U_PRIM, p) = best_prim;
         ns = LP_SHADE0 + (uint32_t)s_surf[best_tag >> 8].kind;
     }
@@ -254,11 +252,11 @@ RR_DEV uint32_t lp_background(const Pool& pl, bool valid, uint32_t p, const Scen
     const V3 d = pl.v3(F_DX, p), thr = pl.v3(F_TX, p);
     const uint32_t bd = pl.u(U_BD, p), w = pl.u(U_SCUR, p);
     V3 light = mk(0.0, 0.0, 0.0);
-    if (valid && ((w >> 30) & 1u)) {
+    if (valid && slot_has_light(w)) {
         const double* l = lp_light(lp, p);
         light = mk(l[0], l[1], l[2]);
     }
-    const V3 result = v_add(light, v_mul(thr, background(sc, d)));
+    const V3 result = escape(sc, d, thr, light);
     if (valid) {
         pl.f(F_AX, p) += result.x, pl.f(F_AY, p) += result.y, pl.f(F_AZ, p) += result.z;
         n.escaped++;
@@ -283,13 +281,13 @@ RR_DEV uint32_t lp_shade(const Pool& pl, bool valid, uint32_t p, int kind, const
     Scatter ev;
     uint32_t draw;
     {
+        // (device_path.h hit_point, written out: calling it here measured +0.3 % on config 2 twice, docs/EXPERIMENT_LOG.md A.9)
         const V3 normal = prim_normal<COMPACT>(rec, pl.v3(F_OX, p));   // F_OX holds the hit position (lp_isect)
         const V3 view = v_unit(v_scale(pl.v3(F_DX, p), -1.0));
         // the RNG key of the sample in flight: the item's pixel and the sample before the cursor
         uint32_t row, col, s_first, s_end;
         item_geometry(rp, pl.u(U_ITEM, p), row, col, s_first, s_end);
-        Rng rng{rr_path_key(rp.seed, (uint64_t)row * cam.W + col, (uint64_t)((pl.u(U_SCUR, p) & SLOT_SAMPLE_MASK) - 1u)),
-                pl.u(U_BD, p) >> 16};
+        Rng rng{sample_key(rp.seed, cam, row, col, slot_cursor(pl.u(U_SCUR, p)) - 1u), pl.u(U_BD, p) >> 16};
         ev = material_evaluate_kind(kind, surf, normal, view, rng);
         draw = rng.draw;
         if (ev.scatter) {  // the roulette's draw (lib.rs:539), taken here so that the key need not outlive the block
@@ -299,20 +297,17 @@ RR_DEV uint32_t lp_shade(const Pool& pl, bool valid, uint32_t p, int kind, const
             const uint32_t bounce = bd & LP_BOUNCE_MASK;
             V3 thr = pl.v3(F_TX, p);
             V3 light = mk(0.0, 0.0, 0.0);
-            if (valid && ((w >> 30) & 1u)) {
+            if (valid && slot_has_light(w)) {
                 const double* l = lp_light(lp, p);
                 light = mk(l[0], l[1], l[2]);
             }
-            light = v_add(light, v_mul(thr, mk(surf->emit[0], surf->emit[1], surf->emit[2])));
-            thr = v_mul(thr, ev.color);
-            const double pr = rr_max(rr_max(thr.x, thr.y), thr.z);
+            const bool goes_on = bounce_step(ev.color, surf->emit, u, bounce, rp.max_bounces, thr, light);
             if (!valid) return LP_DEAD;
-            if (!(u > pr) && bounce < rp.max_bounces) {            // roulette lib.rs:539; loop bound lib.rs:525, :559
-                thr = mk(thr.x / pr, thr.y / pr, thr.z / pr);     // DivAssign, vecmath.rs:708-714
+            if (goes_on) {
                 pl.set_v3(F_DX, p, ev.dir);                        // (F_OX keeps the position: the new ray's origin)
                 pl.set_v3(F_TX, p, thr);
                 pl.u(U_BD, p) = (bounce + 1u) | (draw << 16);
-                const bool keep_light = !((rr_f64_bits(light.x) | rr_f64_bits(light.y) | rr_f64_bits(light.z)) == 0ull);
+                const bool keep_light = !light_is_plus_zero(light);
                 if (keep_light) {
                     double* l = lp_light(lp, p);
                     l[0] = light.x, l[1] = light.y, l[2] = light.z;
@@ -320,7 +315,7 @@ RR_DEV uint32_t lp_shade(const Pool& pl, bool valid, uint32_t p, int kind, const
                 pl.u(U_SCUR, p) = (w & ~SLOT_LIGHT_BIT) | (keep_light ? SLOT_LIGHT_BIT : 0u);
                 return LP_ISECT;
             }
-            // radiance() returns `light` (lib.rs:559, or the roulette's return); main.rs:69 adds it to the pixel
+            // radiance() returns `light` (the roulette's return, or lib.rs:559); main.rs:69 adds it to the pixel
             pl.f(F_AX, p) += light.x, pl.f(F_AY, p) += light.y, pl.f(F_AZ, p) += light.z;
             return LP_GEN;
         }
@@ -328,7 +323,7 @@ RR_DEV uint32_t lp_shade(const Pool& pl, bool valid, uint32_t p, int kind, const
     // NoScatter: radiance() returns `light` without the surface's emission (lib.rs:550)
     if (!valid) return LP_DEAD;
     const uint32_t w = pl.u(U_SCUR, p);
-    if ((w >> 30) & 1u) {
+    if (slot_has_light(w)) {
         const double* l = lp_light(lp, p);
         pl.f(F_AX, p) += l[0], pl.f(F_AY, p) += l[1], pl.f(F_AZ, p) += l[2];
     }
@@ -341,20 +336,6 @@ RR_DEV unsigned long long lp_clock() {
     unsigned long long t;
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
     return t;
-}
-
-RR_DEV unsigned long long lp_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-RR_DEV void lp_wave_add(unsigned long long* dst, unsigned long long v) {
-    const unsigned long long s = lp_wave_sum(v);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(dst, s);
 }
 
 }  // namespace
@@ -476,37 +457,33 @@ __global__ void __launch_bounds__(256, LP_WPS) lp_path_kernel(SceneDev sc, Local
     }
 
     Counters* c = rp.counters;
-    lp_wave_add(&c->rays, n.rays);
-    lp_wave_add(&c->paths, n.paths);
-    lp_wave_add(&c->escaped_paths, n.escaped);
-    lp_wave_add(&c->direct_rays, n.direct);
+    wave_atomic_add(&c->rays, n.rays);
+    wave_atomic_add(&c->paths, n.paths);
+    wave_atomic_add(&c->escaped_paths, n.escaped);
+    wave_atomic_add(&c->direct_rays, n.direct);
     if (COUNT) {
-        lp_wave_add(&c->interior_visits, n.interior);
-        lp_wave_add(&c->tri_tests, n.tri);
-        lp_wave_add(&c->sphere_tests, n.sphere);
-        lp_wave_add(&c->plane_tests, n.plane);
+        wave_atomic_add(&c->interior_visits, n.interior);
+        wave_atomic_add(&c->tri_tests, n.tri);
+        wave_atomic_add(&c->sphere_tests, n.sphere);
+        wave_atomic_add(&c->plane_tests, n.plane);
         if (lane == 0) {
             atomicAdd(&c->step_wave, u_wave * 64ull);
             atomicAdd(&c->interior_ticks, tk_isect), atomicAdd(&c->leaf_ticks, tk_shade);
             atomicAdd(&c->refill_ticks, tk_other);
             atomicAdd(&c->inner_wave, n_isect), atomicAdd(&c->leaf_wave, n_shade);  // phase executions (diagnostics)
         }
-        lp_wave_add(&c->step_lane, u_lane);
+        wave_atomic_add(&c->step_lane, u_lane);
     }
 }
 
 uint32_t lp_lds_bytes(uint32_t n_prims, uint32_t n_surfaces) { return lp_block_bytes(n_prims, n_surfaces); }
 
 hipError_t lp_configure() {
-    const int most = (int)lp_block_bytes(LP_MAX_PRIMS, LP_MAX_PRIMS);
-    const void* const instances[] = {
-        reinterpret_cast<const void*>(&lp_path_kernel<true, false>), reinterpret_cast<const void*>(&lp_path_kernel<true, true>),
-        reinterpret_cast<const void*>(&lp_path_kernel<false, false>), reinterpret_cast<const void*>(&lp_path_kernel<false, true>)};
-    for (const void* k : instances) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    const uint32_t most = lp_block_bytes(LP_MAX_PRIMS, LP_MAX_PRIMS);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 4 && e == hipSuccess; i++)
+        e = with_bools([&](auto C, auto N) { return raise_dynamic_lds(lp_path_kernel<C(), N()>, most); }, (i & 1) != 0, (i & 2) != 0);
+    return e;
 }
 
 // workgroups of the kernel a CU holds with this scene's LDS footprint (at most LP_WPS, its launch bound)

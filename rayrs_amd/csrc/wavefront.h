@@ -49,6 +49,10 @@ static_assert(sizeof(PathSlot) == 128, "PathSlot");
 constexpr uint32_t SLOT_ITEM_BIT = 1u << 31;    // the slot has an item
 constexpr uint32_t SLOT_LIGHT_BIT = 1u << 30;   // the path's light is in WfDev::light (else it is +0)
 constexpr uint32_t SLOT_SAMPLE_MASK = (1u << 30) - 1u;  // samples per pixel a slot can count
+// the cursor word (TailSlot::s_cur; local_pool.hip U_SCUR) taken apart
+RR_LAYOUT_FN constexpr uint32_t slot_cursor(uint32_t word) { return word & SLOT_SAMPLE_MASK; }
+RR_LAYOUT_FN constexpr bool slot_has_item(uint32_t word) { return (word >> 31) != 0u; }
+RR_LAYOUT_FN constexpr bool slot_has_light(uint32_t word) { return ((word >> 30) & 1u) != 0u; }
 
 // slot states
 constexpr uint8_t WF_IDLE = 0;   // no path in flight: gen_kernel's input

@@ -25,9 +25,6 @@
 // hand-off is needed.
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <mutex>
-
 #include "device_path.h"
 #include "kernels.h"
 #include "lab_ticks.h"
@@ -178,23 +175,6 @@ RR_DEV bool feed_next(BatchFeed& f, const WfDev& wf, uint32_t& slot, bool& valid
     return true;
 }
 
-// Sum over the 64 lanes (every lane must call it); the result is valid in lane 0 (and all lanes).
-RR_DEV unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
-// One atomic per wave for a per-lane counter.
-RR_DEV void wave_atomic_add(unsigned long long* dst, unsigned long long v) {
-    const unsigned long long s = wave_sum(v);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(dst, s);
-}
-
 // ---- kernel arguments, re-read where they are used ----
 // The gen, hit and miss kernels take (SceneDev, CameraDev, RenderDev, WfDev) by value: 496 bytes of scalars, loop invariants
 // all.  Left to itself the compiler loads them at the kernel's entry, runs out of scalar registers in the hit kernel's loop,
@@ -254,9 +234,9 @@ struct ItemRegs {
     // had just issued -- a full memory latency at the top of every batch, the look-ahead undone (hit kernel: s_waitcnt
     // vmcnt(4) behind its eight slot requests; found in the ISA, round 6).
     uint32_t word;
-    RR_DEV uint32_t cursor() const { return word & SLOT_SAMPLE_MASK; }
-    RR_DEV bool has_item() const { return (word >> 31) != 0u; }
-    RR_DEV bool has_light() const { return ((word >> 30) & 1u) != 0u; }  // the path's light is in the side array (else it is +0)
+    RR_DEV uint32_t cursor() const { return slot_cursor(word); }
+    RR_DEV bool has_item() const { return slot_has_item(word); }
+    RR_DEV bool has_light() const { return slot_has_light(word); }  // the path's light is in the side array (else it is +0)
 };
 
 RR_DEV ItemRegs load_item(const WfDev& wf, uint32_t slot) {
@@ -269,8 +249,8 @@ RR_DEV ItemRegs load_item(const WfDev& wf, uint32_t slot) {
 }
 
 // The RNG key of the sample a slot has in flight: the item's pixel and the sample before its cursor.
-RR_DEV uint64_t sample_key(const RenderDev& rp, const CameraDev& cam, const ItemRegs& ir) {
-    return rr_path_key(rp.seed, (uint64_t)(ir.pix >> 16) * cam.W + (ir.pix & 0xffffu), (uint64_t)(ir.cursor() - 1u));
+RR_DEV uint64_t item_sample_key(const RenderDev& rp, const CameraDev& cam, const ItemRegs& ir) {
+    return sample_key(rp.seed, cam, ir.pix >> 16, ir.pix & 0xffffu, ir.cursor() - 1u);
 }
 
 // A wave's private range of reserved item ids [next, end).  Items are taken from the
@@ -477,11 +457,8 @@ RR_DEV NewRays next_sample(bool want, uint32_t slot, const ItemRegs& ir, bool ac
             // start the slot's next sample (main.rs:68-76)
             const CameraDev& cam = karg<CameraDev, KA_CAM>();
             const SceneDev& sc = karg<SceneDev, KA_SC>();
-            Rng rng;
-            rng.key = rr_path_key(rp.seed, (uint64_t)row * cam.W + col, (uint64_t)s_cur);
-            rng.draw = 0;
-            // image origin is upper left, camera origin lower right (main.rs:74-75)
-            primary_ray(cam, cam.H - row, cam.W - col, rng, o, d);
+            Rng rng{sample_key(rp.seed, cam, row, col, s_cur), 0};
+            sample_ray(cam, row, col, rng, o, d);
             sn.paths++;
             s_cur++;
             // (DEFER with the pre-test: 1 / d and the root box wait for the end, where the bounced rays need them too)
@@ -491,7 +468,7 @@ RR_DEV NewRays next_sample(bool want, uint32_t slot, const ItemRegs& ir, bool ac
             }
             if (!enters && !DEFER) {
                 // radiance() with the first query a Miss: light 0 + throughput 1 * background (lib.rs:522-523, :555)
-                const V3 result = v_add(mk(0.0, 0.0, 0.0), v_mul(mk(1.0, 1.0, 1.0), background(sc, d)));
+                const V3 result = escape(sc, d, mk(1.0, 1.0, 1.0), mk(0.0, 0.0, 0.0));
                 acc0 += result.x;
                 acc1 += result.y;
                 acc2 += result.z;
@@ -863,9 +840,6 @@ RR_DEV V3 load_light(const WfDev& wf, uint32_t slot) {
     const double* l = light_slot(wf, slot);
     return mk(l[0], l[1], l[2]);
 }
-RR_DEV bool light_is_plus_zero(V3 light) {  // bitwise: -0 and NaN are not
-    return (rr_f64_bits(light.x) | rr_f64_bits(light.y) | rr_f64_bits(light.z)) == 0ull;
-}
 
 template <bool EAGER>
 RR_DEV void load_hit_in(const WfDev& wf, HitIn& h) {  // idle lanes read slot 0: harmless
@@ -881,7 +855,8 @@ RR_DEV void load_hit_in(const WfDev& wf, HitIn& h) {  // idle lanes read slot 0:
     h.ir = load_item(wf, h.slot);
 }
 
-// Built for two workgroups per CU: 256 registers, batch b + 1 requested while batch b is computed (below).
+// Built for three workgroups per CU (the launch bound; tests/test_kernel_resources.py holds it to 168 registers), batch
+// b + 1 requested while batch b is computed (below).  The loop it runs a turn of is device_path.h's radiance section.
 template <bool COMPACT, bool EAGER>
 __global__ void __launch_bounds__(256, 3) wf_hit_kernel(SceneDev sc, CameraDev cam, RenderDev rp, WfDev wf) {
     __shared__ uint32_t lists[4][FEED_LIST];
@@ -938,32 +913,20 @@ __global__ void __launch_bounds__(256, 3) wf_hit_kernel(SceneDev sc, CameraDev c
                 thr = bounce > 1u ? cur.thr : mk(1.0, 1.0, 1.0);
                 light = mk(0.0, 0.0, 0.0);
                 if (bounce > 1u && ir.has_light()) light = EAGER ? cur.light : load_light(wf, slot);
-                Rng rng{sample_key(rp, karg<CameraDev, KA_CAM>(), ir), cur.bd >> 16};
+                Rng rng{item_sample_key(rp, karg<CameraDev, KA_CAM>(), ir), cur.bd >> 16};
                 // lib.rs:528-551
                 const PrimRec<COMPACT>& rec = rec_cur;
-                position = v_add(o, v_scale(d, t));
-                const V3 normal = prim_normal<COMPACT>(rec, position);
-                const V3 view = v_unit(v_scale(d, -1.0));
-                const uint32_t sid = rec.tag() >> 8;
-                hit_sid = sid < 7u ? sid : 7u;
-                const SurfaceDev* surf = sid < n_surf_lds ? &s_surf[sid] : sc.surfaces + sid;
-                const Scatter ev = material_evaluate(surf, normal, view, rng);
-                if (ev.scatter) {
-                    light = v_add(light, v_mul(thr, mk(surf->emit[0], surf->emit[1], surf->emit[2])));
-                    thr = v_mul(thr, ev.color);
-                    const double p = rr_max(rr_max(thr.x, thr.y), thr.z);
-                    if (rng.next() > p) {
-                        ended = true;
-                    } else if (bounce >= rp.max_bounces) {  // loop bound of lib.rs:525; lib.rs:559
-                        ended = true;
-                    } else {
-                        thr = mk(thr.x / p, thr.y / p, thr.z / p);  // DivAssign, vecmath.rs:708-714
-                        dir = ev.dir;
-                        bd_next = (bounce + 1u) | (rng.draw << 16);
-                        goes_on = true;
-                    }
+                position = hit_position(o, d, t);
+                const HitPoint hp = hit_point<COMPACT>(rec, position, d);
+                hit_sid = hp.sid < 7u ? hp.sid : 7u;
+                const SurfaceDev* surf = hp.sid < n_surf_lds ? &s_surf[hp.sid] : sc.surfaces + hp.sid;
+                const Scatter ev = material_evaluate(surf, hp.normal, hp.view, rng);
+                if (ev.scatter && bounce_step(ev.color, surf->emit, rng.next(), bounce, rp.max_bounces, thr, light)) {
+                    dir = ev.dir;
+                    bd_next = (bounce + 1u) | (rng.draw << 16);
+                    goes_on = true;
                 } else {
-                    ended = true;  // lib.rs:550
+                    ended = true;  // the roulette, the loop's bound (lib.rs:559) or a surface that does not scatter (lib.rs:550)
                 }
                 if (ended) {  // radiance() returns `light`; main.rs:69 adds it to the pixel
                     ir.acc[0] += light.x;
@@ -1090,7 +1053,7 @@ __global__ void __launch_bounds__(256, 3) wf_miss_kernel(SceneDev sc, CameraDev 
             const V3 thr = first ? mk(1.0, 1.0, 1.0) : cur.thr;
             V3 light = mk(0.0, 0.0, 0.0);
             if (!first && ir.has_light()) light = EAGER ? cur.light : load_light(karg<WfDev, KA_WF>(), cur.slot);
-            const V3 result = v_add(light, v_mul(thr, background(karg<SceneDev, KA_SC>(), cur.d)));  // lib.rs:555
+            const V3 result = escape(karg<SceneDev, KA_SC>(), cur.d, thr, light);
             ir.acc[0] += result.x;
             ir.acc[1] += result.y;
             ir.acc[2] += result.z;
@@ -1200,19 +1163,10 @@ hipError_t wf_trav_occupancy(bool compact, uint32_t lds, int* blocks_per_cu) {
 }
 
 hipError_t wf_trav_raise_lds(bool compact, uint32_t lds) {
-    static std::mutex mutex;
-    static std::map<std::pair<int, bool>, uint32_t> raised;  // (device, compact): what the instances' limit there was last set to
-    int device = 0;
-    hipError_t e = hipGetDevice(&device);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(mutex);
-    uint32_t& set = raised[{device, compact}];
-    if (lds <= set) return hipSuccess;
+    hipError_t e = hipSuccess;
     for (int i = 0; i < 8 && e == hipSuccess; i++)  // (count, exact, pre): every instance of this layout, some of them twice
-        e = with_trav_instance([&](auto* kernel) {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }, compact, (i & 1) != 0, (i & 2) != 0, (i & 4) != 0);
-    if (e == hipSuccess) set = lds;
+        e = with_trav_instance([&](auto* kernel) { return raise_dynamic_lds(kernel, lds); }, compact, (i & 1) != 0, (i & 2) != 0,
+                               (i & 4) != 0);
     return e;
 }
 

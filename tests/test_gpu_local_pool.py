@@ -8,12 +8,14 @@ rayrs_tuning.local_pool = 1 -- streams its paths through the pool in HBM, three 
 for bit, its ray / path / escaped-path counts, and the work counters of the oracle's walk on the tree each
 walks (the local pool: the groups behind their gating boxes; the streaming kernels: the default tree of single
 primitives behind their own boxes)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import _oracle
 import rayrs_amd
-from rayrs_amd import procedural, scenes
+from rayrs_amd import _ffi, procedural, scenes
 from rayrs_amd.api import BvhHeuristic, Emission, Material, Object, Fresnel, Axis
 
 pytestmark = pytest.mark.gpu
@@ -80,9 +82,8 @@ def test_local_pool_streaming_and_oracle_agree(name, scene_fn, w, h, spp, mb, ch
         assert lst[k] == sst[k], k
 
 
-def test_emitters_and_light_side_array():
-    """Paths that have met an emitter carry `light` (lib.rs:534); the local pool keeps it in a side array in HBM,
-    as the streaming route does.  Emitters of several material kinds, met mid-path."""
+def emitter_scene():
+    """Emitters of several material kinds, met mid-path."""
     floor = Object.plane(Axis.Y, -25., 25., -25., 25., 0.,
                          Material.CookTorrance((1., 1., 1.), 0.5, Fresnel.SchlickMetallic((0.8, 0.8, 0.8))),
                          Emission.Dark())
@@ -92,10 +93,60 @@ def test_emitters_and_light_side_array():
             Object.sphere(1., (2.5, 1., 0.), Material.NoReflect(), Emission.Emissive(5.0, (1., 1., 1.))),  # lib.rs:550
             Object.sphere(0.5, (0., 0.5, 2.), Material.Reflect((0.9, 0.9, 0.9)), Emission.Dark())]
     cam_args = ((0., 4., 9.), (0., 1., 0.), (0., 1., 0.), 50., 4., 2., 100)
-    (loc, lst), (stream, sst), (ref, ost) = frames(cam_args, objs, BvhHeuristic.Sah(1000), 80, 40, 16, 50, 4)
+    return cam_args, objs, BvhHeuristic.Sah(1000)
+
+
+def test_emitters_and_light_side_array():
+    """Paths that have met an emitter carry `light` (lib.rs:534); the local pool keeps it in a side array in HBM,
+    as the streaming route does.  Emitters of several material kinds, met mid-path."""
+    cam_args, objs, heur = emitter_scene()
+    (loc, lst), (stream, sst), (ref, ost) = frames(cam_args, objs, heur, 80, 40, 16, 50, 4)
     assert lst["rays"] == sst["rays"] == ost["rays"]
     assert same_bits(loc, ref) and same_bits(stream, ref)
     assert ref.max() > 1.0
+
+
+# (scene, width, height, max_bounces, rendered by the local pool as well)
+SAMPLE_CASES = [
+    ("material_test", scenes.material_test, 61, 19, 50, True),    # its material kinds in one wave, a ragged edge
+    ("material_test_one_bounce", scenes.material_test, 61, 19, 1, True),   # the loop's bound
+    ("emitters", emitter_scene, 40, 24, 50, True),                # the light side array, NoReflect (lib.rs:550)
+    ("mesh", lambda: scenes.mesh_scene(0), 32, 24, 50, False),    # the compact layout, the one-lane queries' harness
+]
+SAMPLE_SEED, SAMPLE_SPP = 0x5EED, 3
+
+
+@pytest.mark.parametrize("name,scene_fn,w,h,mb,local", SAMPLE_CASES, ids=[c[0] for c in SAMPLE_CASES])
+def test_the_self_test_lane_and_the_render_routes_run_the_same_samples(name, scene_fn, w, h, mb, local):
+    """The self-test kernel (rayrs_test_path_trace: one lane runs a whole sample) and the kernels of a render call the
+    same functions for the loop of lib.rs:521-560 (device_path.h, the radiance section), so a frame is the self test's
+    samples summed in order (main.rs:67-69, :89): (((0 + r_0) + r_1) + r_2) * (1 / 3), bit for bit, on every route that
+    renders the scene.  Every r_s is finite here, so no NaN can hide a pixel that differs."""
+    cam_args, objs, heur = scene_fn()
+    cam_args = scenes.camera_for_resolution(cam_args, w, h)
+    scene = rayrs_amd.Scene(objs, 1e-6, 1e6, heur, HDRI, device=0)
+    cam = rayrs_amd.Camera(*cam_args)
+    assert scene.info()["local_pool"] == (1 if local else 0)
+    rows, cols = np.mgrid[0:h, 0:w]
+    packed = np.ascontiguousarray(((rows << 16) | cols).ravel(), dtype=np.uint32)
+    k = len(packed)
+    expected = np.zeros((k, 3))
+    for s in range(SAMPLE_SPP):
+        sam = np.full(k, s, dtype=np.uint32)
+        n = np.zeros(k, dtype=np.uint32); obj = np.zeros((k, 1), dtype=np.int64); t = np.zeros((k, 1))
+        thr = np.zeros((k, 1, 3)); draw = np.zeros((k, 1), dtype=np.uint32); rgb = np.full((k, 3), np.nan)
+        _ffi.check(scene._L.rayrs_test_path_trace(scene._h, C.byref(cam.desc), SAMPLE_SEED, mb, packed.ctypes.data,
+                                                  sam.ctypes.data, k, 1, 1, n.ctypes.data, obj.ctypes.data, t.ctypes.data,
+                                                  thr.ctypes.data, draw.ctypes.data, rgb.ctypes.data), "rayrs_test_path_trace")
+        assert np.isfinite(rgb).all(), (s, int((~np.isfinite(rgb)).any(axis=1).sum()))
+        expected = expected + rgb
+    expected = (expected * (1.0 / SAMPLE_SPP)).reshape(h, w, 3)
+    routes = [0, 1] if local else [0]
+    for local_pool in routes:   # rayrs_tuning.local_pool: 0 = the route the scene qualifies for, 1 = streaming
+        scene.set_tuning(local_pool=local_pool)
+        img, st = rayrs_amd.render(scene, cam, SAMPLE_SPP, mb, seed=SAMPLE_SEED, sample_chunk=0, out_f64=True)
+        assert st["local_pool"] == (1 if local and local_pool == 0 else 0)
+        assert same_bits(img, expected), (local_pool, int((img.view(np.uint64) != expected.view(np.uint64)).any(axis=2).sum()))
 
 
 def test_horizon_and_sky_primary_rays():
