@@ -33,6 +33,12 @@ RR_DEV uint32_t lanes_below(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// `avail` things handed to the lanes of a ballot, one each, lowest lane first (ranks below `avail`): how many are taken.
+RR_DEV uint32_t lanes_served(unsigned long long need_mask, uint32_t avail) {
+    const uint32_t wanted = (uint32_t)__popcll(need_mask);
+    return wanted < avail ? wanted : avail;
+}
+
 RR_DEV V3 mk(double x, double y, double z) { return V3{x, y, z}; }
 RR_DEV V3 v_add(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 RR_DEV V3 v_sub(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -788,7 +794,7 @@ RR_DEV bool bvh_intersect(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack
     const HotNodes hot{nullptr, 0u};
     // (the default walk on a scene with a hot group: every ray that enters the root box owes the group its test; the
     // wave-level calls inside need every lane of the wave here, so the branch is on the wave-uniform pointer only)
-    HotTally ht{0, 0, 0};
+    HotTally ht{};
     if (EXACT && sc.hot != nullptr) hot_group_step<COUNT>(sc, o, d, tv.cur != TRAV_DONE, tv, wc, ht);
     while (tv.cur != TRAV_DONE) {
         if (trav_at_interior(tv))
@@ -810,7 +816,7 @@ RR_DEV LaneStack lane_stack(uint32_t* lds, uint32_t* spill, const SceneDev& sc) 
 }
 template <bool COMPACT>  // the query, by the walk the scene names (sc.exact: the default walk)
 RR_DEV bool lane_query(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack, double& t_hit, uint32_t& prim_hit) {
-    WorkCount wc{0, 0, 0, 0, 0};
+    WorkCount wc{};
     return sc.exact ? bvh_intersect<COMPACT, false, true>(sc, o, d, stack, t_hit, prim_hit, wc)
                     : bvh_intersect<COMPACT, false, false>(sc, o, d, stack, t_hit, prim_hit, wc);
 }
@@ -1264,6 +1270,16 @@ RR_DEV unsigned long long wave_sum(unsigned long long v) {
 RR_DEV void wave_atomic_add(unsigned long long* dst, unsigned long long v) {
     const unsigned long long s = wave_sum(v);
     if ((threadIdx.x & 63u) == 0 && s) atomicAdd(dst, s);
+}
+
+// ------------------------------------------------------- a wave's bookkeeping
+// What a batch's queries found per surface row (bench.py: ray shares).  hit_sid: rows 7 and up together, 8 for no hit.
+RR_DEV void count_surface_hits(const RenderDev& rp, uint32_t hit_sid) {
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) {
+        const uint32_t c = (uint32_t)__popcll(__ballot(hit_sid == k));
+        if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&rp.counters->surface_hits[k], (unsigned long long)c);
+    }
 }
 
 }  // namespace rayrs

@@ -159,8 +159,7 @@ RR_DEV uint32_t lp_gen(const Pool& pl, bool valid, uint32_t p, const SceneDev& s
                 has_item = true, fresh = true, need = false;
             }
         }
-        const uint32_t wanted = (uint32_t)__popcll(need_mask);
-        range.next += wanted < avail ? wanted : avail;
+        range.next += lanes_served(need_mask, avail);
         need_mask = __ballot(need);
     }
     uint32_t ns = LP_DEAD;
@@ -378,7 +377,7 @@ __global__ void __launch_bounds__(256, LP_WPS) lp_path_kernel(SceneDev sc, Local
     for (uint32_t s = 0; s < LP_NSTATE; s++) cnt[s] = 0;
     cnt[LP_GEN] = P;
     LpRange range{0u, 0u, false};
-    LpCount n{0, 0, 0, 0, 0, 0, 0, 0};
+    LpCount n{};
     unsigned long long u_wave = 0, u_lane = 0;
     unsigned long long tk_isect = 0, tk_shade = 0, tk_other = 0, tk_last = COUNT ? lp_clock() : 0ull;
     unsigned long long n_isect = 0, n_shade = 0, t_mid = 0;
@@ -424,13 +423,7 @@ __global__ void __launch_bounds__(256, LP_WPS) lp_path_kernel(SceneDev sc, Local
         } else {
             uint32_t hit_sid = 8u;
             ns = lp_shade<COMPACT>(pl, valid, p, (int)(ph - LP_SHADE0), cam, rp, lp, s_surf, s_prims, hit_sid);
-            if (COUNT) {  // what the queries found, per surface row (bench.py: ray shares)
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; k++) {
-                    const uint32_t c = (uint32_t)__popcll(__ballot(hit_sid == k));
-                    if (lane == 0 && c) atomicAdd(&rp.counters->surface_hits[k], (unsigned long long)c);
-                }
-            }
+            if (COUNT) count_surface_hits(rp, hit_sid);  // what the queries found, per surface row (bench.py: ray shares)
         }
         if (ph >= LP_SHADE0) {
             if (COUNT) t_mid = lp_clock();
@@ -462,9 +455,9 @@ __global__ void __launch_bounds__(256, LP_WPS) lp_path_kernel(SceneDev sc, Local
     wave_atomic_add(&c->escaped_paths, n.escaped);
     wave_atomic_add(&c->direct_rays, n.direct);
     if (COUNT) {
-        wave_atomic_add(&c->interior_visits, n.interior);
-        wave_atomic_add(&c->tri_tests, n.tri);
-        wave_atomic_add(&c->sphere_tests, n.sphere);
+        wave_atomic_add(&c->interior_visits, n.interior);  // (own fields, not a WorkCount: held in or beside LpCount it gives
+        wave_atomic_add(&c->tri_tests, n.tri);             //  the counting instances other register numbers,
+        wave_atomic_add(&c->sphere_tests, n.sphere);       //  docs/EXPERIMENT_LOG.md A.10)
         wave_atomic_add(&c->plane_tests, n.plane);
         if (lane == 0) {
             atomicAdd(&c->step_wave, u_wave * 64ull);

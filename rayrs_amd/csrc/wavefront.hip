@@ -53,24 +53,40 @@ RR_DEV StateWords load_state_words(const WfDev& wf, uint32_t win) {
     return r;
 }
 
-RR_DEV uint32_t compact_words(const StateWords& sw, uint8_t want, uint16_t* list) {
+// The compaction every kernel here begins with, `passes` times over a window's state bytes: a ballot per byte of the lanes
+// whose slot is listed in this pass, the slot's entry stored at the lane's rank in it.  listed(state byte, pass, tag&): is it
+// listed, and what of the byte the entry carries; entry_of(tag, lane, byte index): the entry.  Returns the list's length.
+// MASK_RANK: the rank from a mask in two registers, else from lanes_below -- v_mbcnt costs the traversal kernel its last
+// registers, the mask the hit and miss kernels theirs.  (Why the passes are a loop in here: docs/EXPERIMENT_LOG.md A.10.)
+template <bool MASK_RANK, class Entry, class Listed, class EntryOf>
+RR_DEV uint32_t compact_states(const StateWords& sw, Entry* list, uint32_t passes, Listed listed, EntryOf entry_of) {
     const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long lanemask_lt = (1ull << lane) - 1ull;  // (v_mbcnt here costs the traversal kernel its last registers)
-    const uint32_t* words = sw.w;
+    unsigned long long lanemask_lt = 0ull;
+    if constexpr (MASK_RANK) lanemask_lt = (1ull << lane) - 1ull;
     uint32_t count = 0;
+#pragma nounroll
+    for (uint32_t pass = 0; pass < passes; pass++) {
 #pragma unroll
-    for (int j = 0; j < (int)SPL; j++) {
-        const uint32_t s = (words[j >> 2] >> ((j & 3) * 8)) & 0xffu;
-        const bool m = s == (uint32_t)want;
-        const unsigned long long mask = __ballot(m);
-        if (m) list[count + (uint32_t)__popcll(mask & lanemask_lt)] = (uint16_t)(lane * SPL + (uint32_t)j);
-        count += (uint32_t)__popcll(mask);
+        for (int j = 0; j < (int)SPL; j++) {
+            const uint32_t s = (sw.w[j >> 2] >> ((j & 3) * 8)) & 0xffu;
+            uint32_t tag = 0;
+            const bool m = listed(s, pass, tag);
+            const unsigned long long mask = __ballot(m);
+            if (m) {
+                const Entry entry = entry_of(tag, lane, (uint32_t)j);
+                if constexpr (MASK_RANK) list[count + (uint32_t)__popcll(mask & lanemask_lt)] = entry;
+                else list[count + lanes_below(mask)] = entry;
+            }
+            count += (uint32_t)__popcll(mask);
+        }
     }
     return count;
 }
 
-RR_DEV uint32_t compact_window(const WfDev& wf, uint32_t win, uint8_t want, uint16_t* list) {
-    return compact_words(load_state_words(wf, win), want, list);
+// The slots whose state is `want`, as offsets inside the window (compact_words_abs: as pool-wide slot indices).
+RR_DEV uint32_t compact_words(const StateWords& sw, uint8_t want, uint16_t* list) {
+    return compact_states<true>(sw, list, 1u, [want](uint32_t s, uint32_t, uint32_t&) { return s == (uint32_t)want; },
+                                [](uint32_t, uint32_t lane, uint32_t j) { return (uint16_t)(lane * SPL + j); });
 }
 
 // A READY state carries the octant of its ray's direction in the high nibble, and the traversal kernel builds its list
@@ -97,22 +113,12 @@ RR_DEV uint32_t compact_window_ready(const WfDev& wf, uint32_t win, uint16_t* li
 RR_DEV uint8_t ready_state_pre(uint32_t mask) { return (uint8_t)(WF_READY | (mask << 3)); }
 RR_DEV uint32_t compact_window_ready_pre(const WfDev& wf, uint32_t win, uint16_t* list) {
     const StateWords sw = load_state_words(wf, win);
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long lanemask_lt = (1ull << lane) - 1ull;
-    uint32_t count = 0;
-#pragma nounroll
-    for (uint32_t key = 0; key < 4u; key++) {
-#pragma unroll
-        for (int j = 0; j < (int)SPL; j++) {
-            const uint32_t s = (sw.w[j >> 2] >> ((j & 3) * 8)) & 0xffu;
-            const uint32_t m = (s >> 3) & 15u;
-            const bool hit = (s & 7u) == (uint32_t)WF_READY && (m & (0u - m)) == (1u << key);
-            const unsigned long long mask = __ballot(hit);
-            if (hit) list[count + (uint32_t)__popcll(mask & lanemask_lt)] = (uint16_t)((lane * SPL + (uint32_t)j) | (m << 9));
-            count += (uint32_t)__popcll(mask);
-        }
-    }
-    return count;
+    return compact_states<true>(sw, list, 4u,
+        [](uint32_t s, uint32_t key, uint32_t& m) {
+            m = (s >> 3) & 15u;
+            return (s & 7u) == (uint32_t)WF_READY && (m & (0u - m)) == (1u << key);
+        },
+        [](uint32_t m, uint32_t lane, uint32_t j) { return (uint16_t)((lane * SPL + j) | (m << 9)); });
 }
 
 // The hit and miss kernels' walk over their slots: wave g of n_waves takes windows g,
@@ -133,18 +139,8 @@ struct BatchFeed {
 };
 
 RR_DEV uint32_t compact_words_abs(const StateWords& sw, uint8_t want, uint32_t base, uint32_t* list) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t* words = sw.w;
-    uint32_t count = 0;
-#pragma unroll
-    for (int j = 0; j < (int)SPL; j++) {
-        const uint32_t s = (words[j >> 2] >> ((j & 3) * 8)) & 0xffu;
-        const bool m = s == (uint32_t)want;
-        const unsigned long long mask = __ballot(m);
-        if (m) list[count + lanes_below(mask)] = base + lane * SPL + (uint32_t)j;
-        count += (uint32_t)__popcll(mask);
-    }
-    return count;
+    return compact_states<false>(sw, list, 1u, [want](uint32_t s, uint32_t, uint32_t&) { return s == (uint32_t)want; },
+                                 [base](uint32_t, uint32_t lane, uint32_t j) { return base + lane * SPL + j; });
 }
 
 RR_DEV void feed_init(BatchFeed& f, const WfDev& wf, uint32_t wave, uint32_t n_waves, uint8_t want, uint32_t* list) {
@@ -198,6 +194,14 @@ RR_DEV const T& karg() {
 RR_DEV RaySlot* ray_slot(const WfDev& wf, uint32_t slot) { return &wf.slots[slot].ray; }
 RR_DEV TailSlot* tail_slot(const WfDev& wf, uint32_t slot) { return &wf.slots[slot].tail; }
 RR_DEV double* light_slot(const WfDev& wf, uint32_t slot) { return wf.light + (size_t)slot * 4u; }
+
+// A ray into its slot; the state byte that goes with it is the caller's to store.
+RR_DEV void store_ray(const WfDev& wf, uint32_t slot, V3 o, V3 d, uint32_t bd) {
+    RaySlot* rs = ray_slot(wf, slot);
+    rs->o[0] = o.x, rs->o[1] = o.y, rs->o[2] = o.z;
+    rs->d[0] = d.x, rs->d[1] = d.y, rs->d[2] = d.z;
+    rs->bd = bd;
+}
 
 // ------------------------------------------------------------------- init
 
@@ -296,9 +300,7 @@ RR_DEV bool refill_item_range(const RenderDev& rp, ItemRange& range) {
     unsigned long long first = ITEMS_GONE;
     if (range.end != ITEMS_GONE) {
         if ((threadIdx.x & 63u) == 0) first = atomicAdd(rp.next_item, (unsigned long long)ITEM_RESERVE);
-        const uint32_t flo = __builtin_amdgcn_readfirstlane((uint32_t)first);
-        const uint32_t fhi = __builtin_amdgcn_readfirstlane((uint32_t)(first >> 32));
-        first = ((unsigned long long)fhi << 32) | flo;
+        first = wave_uniform64(first);
     }
     if (first >= rp.total_items) {
         range.next = range.end = ITEMS_GONE;
@@ -342,7 +344,7 @@ RR_DEV void finish_rays(bool got, bool enters, bool primary, uint32_t slot, V3 o
     const WfDev& wf = karg<WfDev, KA_WF>();
     Trav tv;
     tv.inv = inv, tv.best_t = sc.t1, tv.best_prim = 0xffffffffu, tv.cur = TRAV_DONE, tv.sp = 0;
-    WorkCount wc{0, 0, 0, 0, 0};
+    WorkCount wc{};
     const bool live = got && enters;
     hot_group_step<false>(sc, o, d, live, tv, wc, sn.hot);
     const uint32_t slots = live ? hot_root_record_entered(sc, o, inv) : 0u;
@@ -351,12 +353,10 @@ RR_DEV void finish_rays(bool got, bool enters, bool primary, uint32_t slot, V3 o
     sn.pre_done += (uint32_t)__popcll(__ballot(live && !walk));
     sn.pre_miss += (uint32_t)__popcll(__ballot(got && !enters && !primary));
     if (got) {
-        RaySlot* rs = ray_slot(wf, slot);
-        rs->o[0] = o.x, rs->o[1] = o.y, rs->o[2] = o.z;
-        rs->d[0] = d.x, rs->d[1] = d.y, rs->d[2] = d.z;
-        rs->bd = bd;
+        store_ray(wf, slot, o, d, bd);
         const bool hit = tv.best_prim != 0xffffffffu;
         if (walk || hit) {  // (a MISS says it all: nothing reads t or prim of such a slot)
+            RaySlot* rs = ray_slot(wf, slot);
             rs->t = tv.best_t;
             rs->prim = tv.best_prim;
         }
@@ -443,8 +443,7 @@ RR_DEV NewRays next_sample(bool want, uint32_t slot, const ItemRegs& ir, bool ac
                     need = false;
                 }
             }
-            const uint32_t wanted = (uint32_t)__popcll(need_mask);
-            range.next += wanted < avail ? wanted : avail;
+            range.next += lanes_served(need_mask, avail);
             need_mask = __ballot(need);
         }
         if (todo && dead) {
@@ -514,10 +513,7 @@ RR_DEV void emit_rays(uint32_t slot, const NewRays& nr, SampleCount& sn) {
         finish_rays(got, enters, primary, slot, o, d, inv, bd, sn);
     } else if (got) {
         const WfDev& wf = karg<WfDev, KA_WF>();
-        RaySlot* rs = ray_slot(wf, slot);
-        rs->o[0] = o.x, rs->o[1] = o.y, rs->o[2] = o.z;
-        rs->d[0] = d.x, rs->d[1] = d.y, rs->d[2] = d.z;
-        rs->bd = bd;
+        store_ray(wf, slot, o, d, bd);
         if (primary && !enters) {  // DEFER
             wf.state[slot] = WF_MISS;  // the root box test was this ray's query (bvh.rs:394): the miss kernel's
             sn.deferred++;
@@ -564,10 +560,10 @@ __global__ void __launch_bounds__(256) wf_gen_kernel(SceneDev sc, CameraDev cam,
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
     const uint32_t n_windows = wf.np / WINDOW;
-    SampleCount sn{0, 0, 0, 0, HotTally{0, 0, 0}, 0, 0, 0};
+    SampleCount sn{};
     ItemRange range = load_item_range(wf, wave);
     for (uint32_t win = wave; win < n_windows; win += n_waves) {
-        const uint32_t count = compact_window(wf, win, WF_IDLE, list);
+        const uint32_t count = compact_words(load_state_words(wf, win), WF_IDLE, list);
         for (uint32_t k = 0; k < count; k += 64u) {
             const bool valid = k + lane < count;
             const uint32_t slot = win * WINDOW + (valid ? (uint32_t)list[k + lane] : 0u);
@@ -656,7 +652,7 @@ __global__ void __launch_bounds__(256, 5) wf_trav_kernel(SceneDev sc, RenderDev 
     V3 o = mk(0, 0, 0), d = mk(0, 0, 1);
     Trav tv;
     tv.inv = mk(0, 0, 0), tv.best_t = 0, tv.best_prim = 0xffffffffu, tv.cur = TRAV_DONE, tv.sp = 0;
-    WorkCount wc{0, 0, 0, 0, 0};
+    WorkCount wc{};
     unsigned long long n_rays = 0;
     unsigned long long u_int_wave = 0, u_int_lane = 0, u_leaf_wave = 0, u_leaf_lane = 0;
     unsigned long long tk_int = 0, tk_leaf = 0, tk_refill = 0, tk_last = COUNT ? clock64() : 0ull;
@@ -757,8 +753,7 @@ __global__ void __launch_bounds__(256, 5) wf_trav_kernel(SceneDev sc, RenderDev 
                     }
                     need = false;
                 }
-                const uint32_t wanted = (uint32_t)__popcll(need_mask);
-                list_pos += wanted < avail ? wanted : avail;
+                list_pos += lanes_served(need_mask, avail);
                 need_mask = __ballot(need);
             }
             if (COUNT) {
@@ -871,7 +866,7 @@ __global__ void __launch_bounds__(256, 3) wf_hit_kernel(SceneDev sc, CameraDev c
     uint32_t* list = lists[threadIdx.x >> 6];
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-    SampleCount sn{0, 0, 0, 0, HotTally{0, 0, 0}, 0, 0, 0};
+    SampleCount sn{};
     if (blockIdx.x == 0 && threadIdx.x == 0) wf.ctl->next_window = 0;  // the traversal kernel's window cursor
     ItemRange range = load_item_range<true>(wf, wave);
     BatchFeed feed;
@@ -953,12 +948,7 @@ __global__ void __launch_bounds__(256, 3) wf_hit_kernel(SceneDev sc, CameraDev c
                 if (keep_light != ir.has_light()) lt->s_cur = ir.cursor() | (keep_light ? SLOT_LIGHT_BIT : 0u) | SLOT_ITEM_BIT;
             }
             if (karg<RenderDev, KA_RP>().count_work) {  // wave-uniform; what the queries found, per surface row (bench.py: ray shares)
-                const RenderDev& rp = karg<RenderDev, KA_RP>();
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; k++) {
-                    const uint32_t c = (uint32_t)__popcll(__ballot(hit_sid == k));
-                    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&rp.counters->surface_hits[k], (unsigned long long)c);
-                }
+                count_surface_hits(karg<RenderDev, KA_RP>(), hit_sid);
             }
             RR_TICK(3)
             // ---- batch b + 1's slot records are requested HERE, behind Material::evaluate: every call of an elementary function
@@ -1025,7 +1015,7 @@ __global__ void __launch_bounds__(256, 3) wf_miss_kernel(SceneDev sc, CameraDev 
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
     unsigned long long n_escaped = 0;
-    SampleCount sn{0, 0, 0, 0, HotTally{0, 0, 0}, 0, 0, 0};
+    SampleCount sn{};
     ItemRange range = load_item_range(wf, wave);
     BatchFeed feed;
     feed_init(feed, wf, wave, n_waves, WF_MISS, list);
@@ -1089,14 +1079,11 @@ __global__ void __launch_bounds__(256) wf_intake_kernel(SceneDev sc, CameraDev c
     const V3 inv = mk(1.0 / rd.x, 1.0 / rd.y, 1.0 / rd.z);
     const bool enters = got && root_box_hit(sc, ro, inv);
     if (sc.hot != nullptr) {  // wave-uniform: every lane takes part in finish_rays' ballots
-        SampleCount sn{0, 0, 0, 0, HotTally{0, 0, 0}, 0, 0, 0};
+        SampleCount sn{};
         finish_rays(got, enters, false, slot, ro, rd, inv, 1u, sn);
         if ((threadIdx.x & 63u) == 0 && sn.pre_done) atomicAdd(answered, (unsigned long long)sn.pre_done);
     } else if (got) {
-        RaySlot* rs = ray_slot(wf, slot);
-        rs->o[0] = ro.x, rs->o[1] = ro.y, rs->o[2] = ro.z;
-        rs->d[0] = rd.x, rs->d[1] = rd.y, rs->d[2] = rd.z;
-        rs->bd = 1u;
+        store_ray(wf, slot, ro, rd, 1u);
         wf.state[slot] = enters ? ready_state(rd) : WF_MISS;
     }
     if (!got && slot < wf.np) wf.state[slot] = WF_DEAD;
