@@ -1,5 +1,5 @@
 // film_abi.cpp -- the progressive film of include/rayrs_hip.h (rayrs_film_*): a film's lifetime, a pass as a render of a
-// sample window whose chunk sums go to the film's records (abi.cpp render_enqueue, film.hip), the frame and the status
+// sample window whose chunk sums go to the film's records (render.cpp render_enqueue, film.hip), the frame and the status
 // read from the records, and the checkpoint image.
 #include <hip/hip_runtime.h>
 
@@ -50,6 +50,7 @@ struct rayrs_film {
     DevBuf d_flags;   // an adaptive pass: one word per tile of the share (film_select_kernel) ...
     DevBuf d_list;    // ... and the list made of them, one TileRef per tile of the share at most
     DevBuf d_select;  // one FilmSelect
+    PinnedBuf h_word; // one word of it, read back (film_select)
     DevBuf d_counts;  // one FilmCounts
     DevBuf d_out;     // the frame rayrs_film_read copies out, grown on demand
     PinnedBuf h_stage;
@@ -83,7 +84,7 @@ struct rayrs_film {
 static int film_enter(rayrs_film* f) { return scene_settle(f->scene); }
 
 // Makes the list of a pass over some of the share's tiles (film.hip): those an adaptive pass of n samples selects at tau
-// under the cap, or all of them.  One word of the result comes back through the scene's pinned words -- the list's length,
+// under the cap, or all of them.  One word of the result comes back through the film's pinned word -- the list's length,
 // which the pass is planned from, or (all) the largest N_t, which bounds the pass -- and that copy is the only wait.
 static int film_select(rayrs_film* f, uint32_t n, uint32_t cap, double tau, bool all, uint32_t* word) {
     HIP_TRY(f->d_flags.reserve((size_t)f->share.n_local_tiles * sizeof(uint32_t)));
@@ -92,7 +93,7 @@ static int film_select(rayrs_film* f, uint32_t n, uint32_t cap, double tau, bool
     FilmSelect* sel = f->d_select.as<FilmSelect>();
     HIP_TRY(launch_film_select(cam, f->share, f->d_rec.as<double>(), f->d_tile_n.as<uint32_t>(), f->prm.sample_chunk, n, cap, tau * tau,
                                all ? 1u : 0u, f->d_flags.as<uint32_t>(), f->d_list.as<TileRef>(), sel, nullptr));
-    uint32_t* h_word = f->scene->pool.h_live.as<uint32_t>();
+    uint32_t* h_word = f->h_word.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(h_word, all ? &sel->max_samples : &sel->n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     *word = *h_word;
@@ -161,6 +162,7 @@ int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayr
     HIP_TRY(f->d_tile_n.reserve(f->count_bytes()));
     HIP_TRY(hipMemset(f->d_tile_n.as<>(), 0, f->count_bytes()));
     HIP_TRY(f->d_select.reserve(sizeof(FilmSelect)));
+    HIP_TRY(f->h_word.alloc(sizeof(uint32_t)));
     HIP_TRY(f->d_counts.reserve(sizeof(FilmCounts)));
     *out = f.release();
     return RAYRS_OK;

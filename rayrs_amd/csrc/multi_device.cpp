@@ -178,6 +178,7 @@ void render_rank(Rank& r, const rayrs_camera* camera, rayrs_render_params params
 
 }  // namespace
 
+#define RAYRS_SUM(name) stats->name += s.name;  // (defined out here: no directive inside RAYRS_GUARDED's argument)
 extern "C" int rayrs_render_multi(rayrs_scene* const* scenes, uint32_t n, const rayrs_camera* camera,
                                   const rayrs_render_params* params, void* out_host, rayrs_render_stats* stats) {
     RAYRS_GUARDED({
@@ -190,7 +191,7 @@ extern "C" int rayrs_render_multi(rayrs_scene* const* scenes, uint32_t n, const 
         }
         const bool f64 = params->out_format == RAYRS_OUT_F64;
         const size_t count = (size_t)camera->x_pixels * camera->y_pixels * 3;
-        const size_t bytes = count * (f64 ? 8 : 4);
+        const size_t bytes = frame_bytes(camera->x_pixels, camera->y_pixels, params->out_format);
 
         // ---- every rank renders its tiles on its own host thread and stream
         std::vector<Rank> ranks(n);
@@ -250,17 +251,7 @@ extern "C" int rayrs_render_multi(rayrs_scene* const* scenes, uint32_t n, const 
             *stats = ranks[0].stats;  // every counter summed over the ranks; times and launches: the slowest rank's
             for (uint32_t i = 1; i < n; i++) {
                 const rayrs_render_stats& s = ranks[i].stats;
-                stats->rays += s.rays, stats->paths += s.paths, stats->nan_pixels += s.nan_pixels;
-                stats->neg_pixels += s.neg_pixels, stats->escaped_paths += s.escaped_paths;
-                stats->interior_visits += s.interior_visits, stats->tri_tests += s.tri_tests;
-                stats->sphere_tests += s.sphere_tests, stats->plane_tests += s.plane_tests;
-                stats->direct_rays += s.direct_rays;
-                stats->step_wave += s.step_wave, stats->step_lane += s.step_lane;
-                stats->inner_wave += s.inner_wave, stats->leaf_wave += s.leaf_wave;
-                stats->interior_ticks += s.interior_ticks, stats->leaf_ticks += s.leaf_ticks;
-                stats->refill_ticks += s.refill_ticks;
-                stats->pre_rays += s.pre_rays, stats->pre_root_records += s.pre_root_records, stats->hot_lane += s.hot_lane;
-                stats->hot_prim_tests += s.hot_prim_tests, stats->hot_tri_divided += s.hot_tri_divided;
+                RAYRS_WORK_COUNTERS(RAYRS_SUM)
                 for (int k = 0; k < 8; k++) stats->surface_hits[k] += s.surface_hits[k];
                 if (s.total_ms > stats->total_ms) stats->total_ms = s.total_ms;
                 if (s.trace_ms > stats->trace_ms) stats->trace_ms = s.trace_ms;
@@ -273,6 +264,8 @@ extern "C" int rayrs_render_multi(rayrs_scene* const* scenes, uint32_t n, const 
         return st;
     })
 }
+
+#undef RAYRS_SUM
 
 // ---- rayrs_lab.h: the calls rayrs_render_multi's reduce makes on an N-GPU node, rehearsed without one ----
 namespace {

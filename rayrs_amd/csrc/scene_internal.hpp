@@ -1,4 +1,4 @@
-// scene_internal.hpp -- the handles behind include/rayrs_hip.h, shared by abi.cpp, selftest.cpp and multi_device.cpp.
+// scene_internal.hpp -- the handles behind include/rayrs_hip.h, shared by the host units (abi.cpp, scene_device.cpp, render.cpp, film_abi.cpp, selftest.cpp, multi_device.cpp ...).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include "../../include/rayrs_hip.h"
 #include "device_mem.hpp"
 #include "film.h"
+#include "frame_plan.hpp"
 #include "local_pool.h"
 #include "rayrs_lab.h"
 #include "scene_host.hpp"
@@ -18,6 +19,21 @@ struct rayrs_objects {
     rayrs::ObjectList list;
 };
 
+// The work counters that layout.h Counters and rayrs_render_stats share under one name each, in Counters' order
+// (surface_hits[8], which sits among them, apart): X(name) once per counter.
+#define RAYRS_WORK_COUNTERS(X)                                                                                  \
+    X(rays) X(paths) X(nan_pixels) X(neg_pixels)                                                                \
+    X(interior_visits) X(tri_tests) X(sphere_tests) X(plane_tests) X(escaped_paths)                             \
+    X(step_wave) X(step_lane) X(inner_wave) X(leaf_wave)                                                        \
+    X(interior_ticks) X(leaf_ticks) X(refill_ticks)                                                             \
+    X(direct_rays) X(pre_rays) X(pre_root_records) X(hot_lane) X(hot_prim_tests) X(hot_tri_divided)
+#ifndef RAYRS_LAB_TICKS
+#define RAYRS_COUNT_ONE(name) +1
+static_assert(((RAYRS_WORK_COUNTERS(RAYRS_COUNT_ONE)) + 8) * sizeof(unsigned long long) == sizeof(rayrs::Counters),
+              "RAYRS_WORK_COUNTERS and surface_hits[8] are all of Counters");
+#undef RAYRS_COUNT_ONE
+#endif
+
 struct rayrs_scene {
     rayrs::FlatScene flat;
     std::vector<rayrs::SurfaceDev> surfaces;
@@ -26,11 +42,7 @@ struct rayrs_scene {
     // Every device resource below has an owner (device_mem.hpp): the destructor waits for a render in flight on the
     // scene's device, then the members release themselves.
     ~rayrs_scene();
-    rayrs::DevBuf d_prims, d_surfaces, d_hdri, d_counters;
-    rayrs::DevBuf d_partial;  // the item sums: 3 doubles per (pixel, chunk) item, grown to the largest frame so far
-    rayrs::Event ev[3];       // a frame's start, the end of its path rounds, the end of its resolve
-    hipStream_t last_stream = nullptr;
-    bool pending = false;
+    rayrs::DevBuf d_prims, d_surfaces, d_hdri;
     int cu_count = 0;
     // How the traversal kernel walks each of the scene's two trees: [0] FlatScene::walk (rayrs_render_params.fast_traversal),
     // [1] FlatScene::gate (the default walk).
@@ -44,15 +56,11 @@ struct rayrs_scene {
     // [2] FlatScene::gate_hot (the default walk on a scene with a hot group: layout.h HotGroupDev).
     Walk trav[3];
     const rayrs::WalkTree& tree(int which) const { return which == 2 ? flat.gate_hot : which == 1 ? flat.gate : flat.walk; }
+    uint32_t stack_depth(int which) const { return tree(which).depth ? tree(which).depth : 1; }  // entries of a lane's stack
     rayrs::DevBuf d_hot;  // one HotGroupDev
-    // which of the three a frame walks: the fast walk [0] (or [1] with rayrs_lab_tuning.gate_tree), the default walk [2] if the
-    // scene has a hot group and the lab has not switched it off, else [1]
-    int walk_index(bool exact) const {
-        if (!exact) return lab.gate_tree ? 1 : 0;
-        return (flat.has_hot && lab.hot_group != 0xffffffffu) ? 2 : 1;
-    }
+    int walk_index(bool exact) const { return rayrs::walk_index(exact, flat.has_hot, lab); }  // which of the three a frame walks
     uint64_t device_bytes = 0;
-    // The path pool of the streaming route (abi.cpp rayrs_render_launch): slots, state bytes, control words,
+    // The path pool of the streaming route (render.cpp enqueue_streaming): slots, state bytes, control words,
     // per-wave item ranges and traversal-stack overflow strips, kept between renders.
     struct Pool {
         rayrs::DevBuf block;          // one allocation holding the slot records, the light entries and the state bytes
@@ -64,17 +72,32 @@ struct rayrs_scene {
         std::vector<rayrs::Event> ev_round;  // four per round: around the traversal, hit and miss launches
         uint32_t timed_rounds = 0;
     };
-    Pool pool;
-    rayrs::DevBuf d_next_item;  // the device-wide item counter
-    uint32_t rounds = 0;
+    // Everything a frame in flight uses, and what is kept of it between frames: one frame per scene at a time.
+    struct Frame {
+        rayrs::DevBuf d_counters;
+        rayrs::DevBuf d_partial;    // the item sums: 3 doubles per (pixel, chunk) item, grown to the largest frame so far
+        rayrs::DevBuf d_next_item;  // the device-wide item counter
+        rayrs::Event ev[3];         // a frame's start, the end of its path rounds, the end of its resolve
+        hipStream_t last_stream = nullptr;
+        bool pending = false;
+        uint32_t rounds = 0;
+        Pool pool;
+        rayrs::DevBuf d_local_light;      // 4 doubles per resident path
+        rayrs::DevBuf d_local_items;      // one item counter per launch segment
+        // What the frame took, written when it is enqueued: all that rayrs_render_finish reports of route and walk.
+        struct Taken {
+            bool use_local;  // the local-pool route
+            bool exact;      // the exact walk (asked for, or a far camera: frame_plan.cpp camera_is_far)
+            bool hot_group;  // the streaming route's default walk on the hot-group tree
+        } taken = {};
+        // The one wait for a frame in flight (the scene's device is current).  Touches no error text.
+        hipError_t wait();
+    };
+    Frame frame;
     // Scenes whose walk tree is at most one record are rendered by local_pool.hip: every path resident in LDS.
     bool local_ok = false;
-    bool last_local = false;          // the render in flight took that route
-    bool last_exact = false;          // ... with the exact walk (asked for, or a far camera: abi.cpp camera_is_far)
     rayrs::LocalScene local = {};
     int local_blocks_per_cu = 1;      // local-pool kernel, from the occupancy query with the scene's LDS size
-    rayrs::DevBuf d_local_light;      // 4 doubles per resident path
-    rayrs::DevBuf d_local_items;      // one item counter per launch segment
     // rayrs_render_multi: this rank's stream and zeroed full-size framebuffer, kept between calls
     rayrs::Stream multi_stream;
     rayrs::DevBuf multi_out;
@@ -86,32 +109,31 @@ namespace rayrs {
 // thread-local text behind rayrs_last_error()
 void set_last_error(const std::string& text);
 int hip_fail(hipError_t e, const char* what);
-// sets the scene's device (>= 0) and waits for what the scene still has in flight on it (abi.cpp)
+// sets the scene's device (>= 0) and waits for what the scene still has in flight on it (render.cpp)
 int scene_settle(rayrs_scene* s);
 // the bytes of a w x h frame in an out_format
 inline size_t frame_bytes(uint32_t w, uint32_t h, uint32_t out_format) {
     return (size_t)w * h * 3 * (out_format == RAYRS_OUT_F64 ? 8 : 4);
 }
-// uploads s->flat to s->device and sizes the traversal kernel's LDS (abi.cpp)
+// the gating boxes of a scene the local-pool route can render, before the upload (scene_device.cpp)
+void scene_configure_local(rayrs_scene* s);
+// uploads s->flat to s->device and sizes the traversal kernel's LDS (scene_device.cpp)
 int scene_upload(rayrs_scene* s);
-// what a render hands its kernels, for the self tests too (abi.cpp)
+// sizes the traversal workgroup's LDS again, after the lab knobs changed (scene_device.cpp)
+int scene_configure_traversal(rayrs_scene* s);
+// what a render hands its kernels, for the self tests too (scene_device.cpp)
 SceneDev make_scene_dev(const rayrs_scene* s, bool exact);
 CameraDev make_camera_dev(const rayrs_camera* c);
-// The route and the walk of a frame with these settings (abi.cpp).  exact: the default walk, asked for or by the camera rule of
-// rayrs_render_params.fast_traversal; the local-pool route's walk is exact whatever it says.
-struct FrameWalk {
-    bool use_local, exact;
-};
+// the route and the walk of a frame with these settings (frame_plan.hpp frame_route, camera_is_far)
 FrameWalk frame_walk(const rayrs_scene* s, const rayrs_camera* c, uint32_t fast_traversal);
-// words of the traversal stacks' overflow strip for a launch of `threads` threads: the entries beyond the LDS part
-inline size_t stack_spill_words(const SceneDev& sc, uint64_t threads) { return (size_t)(sc.stack_depth - sc.stack_lds) * threads; }
-uint32_t trav_settings(const rayrs_scene* s, bool exact, uint32_t np, RenderDev& rp);
-constexpr size_t POOL_SLOT_BYTES = sizeof(PathSlot) + 4 * sizeof(double) + 1u;  // a slot record, its light entry, its state byte
+// the traversal kernel's settings on a pool of np slots of this scene (frame_plan.hpp plan_traversal)
+TravPlan trav_settings(const rayrs_scene* s, bool exact, uint32_t np);
 WfDev pool_wf(const DevBuf& block, uint32_t np, const DevBuf& ctl, uint32_t trav_blocks, const DevBuf& spill);
 // enqueues a frame (film == nullptr, sample0 = 0: rayrs_render_launch) or a film's pass over the samples sample0 ..
-// sample0 + params->spp - 1 (film_abi.cpp); rayrs_render_finish waits for either (abi.cpp)
+// sample0 + params->spp - 1 (film_abi.cpp); render_finish waits for either and reads its counters and times (render.cpp)
 int render_enqueue(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_render_params* params, uint32_t sample0,
                    const FilmPassDev* film, void* out_device, void* hip_stream);
+int render_finish(rayrs_scene* scene, rayrs_render_stats* stats);
 }  // namespace rayrs
 
 #define HIP_TRY(expr)                                       \

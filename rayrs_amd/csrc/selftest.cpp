@@ -79,11 +79,12 @@ int rayrs_test_trace(rayrs_scene* scene, const double* o, const double* d, uint6
     // the pool: rayrs_tuning.pool_slots slots if set (the rays then go through it in chunks of that many), whole windows
     // (laid out as a render's, pool_wf: that includes the light entries, a quarter more memory, which no kernel run here touches)
     uint64_t np64 = scene->tuning.pool_slots ? scene->tuning.pool_slots : (n < (1u << 20) ? n : (1u << 20));
-    np64 = np64 < 1024u ? 1024u : (np64 + 1023u) & ~1023ull;
-    const uint32_t np = (uint32_t)np64;
+    const uint32_t np = (uint32_t)pool_whole_windows(np64 ? np64 : 1u);  // (at least one 1024)
     RenderDev rp;
     std::memset(&rp, 0, sizeof(rp));
-    const uint32_t trav_blocks = trav_settings(scene, ex, np, rp);
+    const TravPlan trav = trav_settings(scene, ex, np);
+    trav.fill(rp);
+    const uint32_t trav_blocks = trav.blocks;
     DevBuf dblock, dctl, dspill, dcount, dans, dorg, ddir;
     HIP_TRY(alloc(dblock, (size_t)np * POOL_SLOT_BYTES));
     HIP_TRY(alloc(dctl, sizeof(WfCtl)));
@@ -104,7 +105,7 @@ int rayrs_test_trace(rayrs_scene* scene, const double* o, const double* d, uint6
         HIP_TRY(hipMemcpy(dorg.as<>(), o + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(ddir.as<>(), d + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice));
         HIP_TRY(wf_launch_intake(sc, wf, dorg.as<const double>(), ddir.as<const double>(), m, dans.as<unsigned long long>(), nullptr));
-        // the traversal rounds of a render (abi.cpp rayrs_render_launch): there the hit kernel resets the window cursor
+        // the traversal rounds of a render (render.cpp enqueue_streaming): there the hit kernel resets the window cursor
         uint32_t round = 0;
         for (;; round++) {
             WfCtl ctl;

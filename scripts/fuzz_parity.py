@@ -61,7 +61,7 @@ for seed in range(first, first + count):
     for k in ("rays", "paths", "escaped_paths"):
         ok = ok and st[k] == ost0[k]
     # the oracle's walk on the records the frame's queries walked: the gate tree with nothing culled unless the frame
-    # took the fast walk (asked for, the streaming route, the camera not far from the scene: abi.cpp camera_is_far)
+    # took the fast walk (asked for, the streaming route, the camera not far from the scene: frame_plan.cpp camera_is_far)
     n_far += fast and bool(st["exact_walk"]) and not st["local_pool"]
     ref, ost = osc.use_product_walk(scene, fast=not st["exact_walk"]).render(ocam, spp, mb, seed=seed, sample_chunk=chunk, traversal=2)
     ok = ok and np.array_equal(img.view(np.uint64), ref.view(np.uint64))

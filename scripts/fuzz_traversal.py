@@ -7,7 +7,7 @@ on the product's own trees (host-only scene, device = -1), walked by the oracle 
             primitives behind their widened boxes, slots entered beyond closest_t * (1 + 2^-10) culled: two bets on the
             reference's arithmetic (include/rayrs_hip.h).  REQUIRED to match on the general family and on grazing rays
             1e-7 rad and more off the plane from origins within 8 root-box diagonals AND 4096 small-primitive sizes of
-            the scene -- beyond that a frame's camera gets the default walk whatever was asked (abi.cpp camera_is_far),
+            the scene -- beyond that a frame's camera gets the default walk whatever was asked (frame_plan.cpp camera_is_far),
             and bounce rays start on the scene; counted and reported elsewhere;
   leaves    the fast walk's tree with no culling: which of its mismatches are the leaf boxes' alone.
 The geometry is where Moeller-Trumbore is least accurate: sliver triangles, nearly coplanar tessellated sheets whose
@@ -113,8 +113,8 @@ def rays_for(rng, verts, scale, n):
     return o, d
 
 
-NEAR = 8.0        # abi.cpp RAYRS_FAR_DIAGONALS: diagonals of the root box between it and the origin
-NEAR_PRIMS = 4096.0  # abi.cpp RAYRS_FAR_PRIMITIVES: ... and small-primitive sizes (5th percentile of the largest extents)
+NEAR = 8.0        # frame_plan.cpp RAYRS_FAR_DIAGONALS: diagonals of the root box between it and the origin
+NEAR_PRIMS = 4096.0  # frame_plan.cpp RAYRS_FAR_PRIMITIVES: ... and small-primitive sizes (5th percentile of the largest extents)
 
 
 def small_extent(verts, idx):
@@ -126,7 +126,7 @@ def small_extent(verts, idx):
 
 
 def is_near(o, root_box, small=0.0):
-    """abi.cpp camera_is_far, negated: the origins from which a frame's camera gets the fast walk when it asks for it."""
+    """frame_plan.cpp camera_is_far, negated: the origins from which a frame's camera gets the fast walk when it asks for it."""
     b = np.asarray(root_box, dtype=np.float64)
     lo, hi = b[0::2], b[1::2]
     out = np.maximum(np.maximum(lo - o, o - hi), 0.0)

@@ -4,7 +4,7 @@ In the reference's scenes every path ends within tens of bounces (albedo <= 0.8,
 narrow per-path fields -- bounce and RNG draw index packed as `bounce | draw << 16` (wavefront.h RaySlot::bd; 15 + 16 bits
 in the local pool) -- never get near the 8000-bounce budget the launch accepts, and a frame's long tail (a handful of slots
 live for thousands of rounds: 4-round batches, the traversal kernel's static windows once few slots are live, a leaf queue
-with one waiting lane, rounds beyond the MAX_TIMED events of abi.cpp) is never rendered.  Here the rooms are closed and
+with one waiting lane, rounds beyond the MAX_TIMED events of render.cpp) is never rendered.  Here the rooms are closed and
 their surfaces scatter with a weight of exactly (1, 1, 1), so `rng_next() > max(throughput) = 1` never fires
 (lib.rs:539-545) and every path runs to its budget; or their weights are close to one and some paths run to 8000 bounces
 drawing four numbers at each, the case the limit is derived from (draw index 2 + 4 x 8000 = 32002)."""
@@ -159,7 +159,7 @@ def test_hot_group_room_streams_every_path_to_its_budget(lab):
 
 def test_more_rounds_than_timed_rounds():
     """A pool of 1024 slots for 2048 paths of 8000 bounces each: slots take two samples one after the other and the
-    frame runs about 16000 rounds, past the 8192 rounds whose kernel times are recorded (abi.cpp MAX_TIMED).  The frame
+    frame runs about 16000 rounds, past the 8192 rounds whose kernel times are recorded (render.cpp MAX_TIMED).  The frame
     and counters are the oracle's, the round times stop at 8192 without an error, and an ordinary frame rendered next on
     the same scene is the oracle's too (counters, wave_items and the item counter are reset after a long frame)."""
     budget, w, h, spp = 8000, 32, 16, 4

@@ -226,7 +226,7 @@ def many_reference(name):
 
 
 def launches(n_tiles, chunks_per_tile, segment=SEGMENT):
-    """The local-pool route's launches for a pass (abi.cpp plan_frame): segments of whole tiles, as many as hold `segment`
+    """The local-pool route's launches for a pass (frame_plan.cpp plan_frame): segments of whole tiles, as many as hold `segment`
     items of 64 pixels x the pass's chunks per tile."""
     seg_tiles = -(-segment // (64 * chunks_per_tile))
     return -(-n_tiles // seg_tiles)

@@ -3,7 +3,7 @@
 The launch accepts image sides up to 65535 pixels (TailSlot::pix is row << 16 | col) and frames of up to 2^32 - 1
 (pixel, chunk) items (item ids are uint32_t: wavefront.hip next_sample, local_pool.hip lp_gen, layout.h item_geometry).
 Frames at those limits: the widest and the tallest image, and item ids past 2^31 on both routes -- on the local pool
-spread over about 32 segments of whole tiles (abi.cpp), whose last one ends the frame."""
+spread over about 32 segments of whole tiles (frame_plan.cpp plan_frame), whose last one ends the frame."""
 import numpy as np
 import pytest
 import torch

@@ -267,7 +267,7 @@ def test_a_camera_far_from_the_scene_gets_the_default_walk_whatever_was_asked():
     primitive sizes away (profiles/r04_tight_leaves.txt) and were never seen to fail from nearby.  Bounce rays start on
     the scene; only a camera can stand far out -- and a frame whose camera is more than 8 root-box diagonals, or 4096 of
     the scene's small primitives, from the root box takes the default walk also when the fast one is asked for
-    (abi.cpp camera_is_far).  rayrs_render_stats.exact_walk reports the walk; the far frame's counters are the oracle's
+    (frame_plan.cpp camera_is_far).  rayrs_render_stats.exact_walk reports the walk; the far frame's counters are the oracle's
     for the gate tree with nothing culled."""
     mesh = lambda: scenes.mesh_scene(3)
     scene, cam, osc, ocam = both(mesh, 64, 48, 4)

@@ -178,7 +178,7 @@ def test_both_bets_on_slivers_flat_sheets_and_grazing_rays():
     general directions down to 1e-7 rad over the sheet and rays aimed along a triangle's own plane.
     The fast walk must match on the general family and on grazing rays 1e-7 rad and more off the plane from
     within 8 root-box diagonals and 4096 small-primitive sizes of the scene (from farther out a frame takes the default
-    walk whatever it asks for: abi.cpp camera_is_far) -- on the sheets of 6 ... 40 quads per side on which that was
+    walk whatever it asks for: frame_plan.cpp camera_is_far) -- on the sheets of 6 ... 40 quads per side on which that was
     measured in round 4, with a floor under them, and on a sheet of 350 well-shaped quads per side; on a sheet of 320
     SLIVER quads per side (seed 11, round 5) its culling loses hits to in-plane rays at 1e-7 rad and more from ANY
     distance (a few in 10^4): counted here, not required -- which is why the fast walk is the caller's choice and not
