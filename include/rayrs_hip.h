@@ -520,7 +520,7 @@ int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes);
  *       w = (h[|dy|]*h[|dx|]) * rr_exp(-e)   (include/rayrs_numeric.h);
  *       num += c_q * w per component (the product first, then the sum); den += w;
  *   - if den == 0 (the pixel's own features are NaN), c'_p = c_p; else c'_p = num / den, an f64 division per component.
- * A feature plane that is absent (NULL) contributes no term.  No albedo demodulation, nothing temporal; the weight that is
+ * A feature plane that is absent (NULL) contributes no term.  No albedo demodulation, nothing temporal (that is TEMPORAL ACCUMULATION below); the weight that is
  * guided by the film's own noise estimate is the GUIDED FILTER below.
  *
  * Refusals, all decided before the device is touched: RAYRS_INVALID_ARG for samples = 0 or >= 2^30, levels outside 1 .. 16,
@@ -610,6 +610,108 @@ int rayrs_image_denoise_guided(int device, uint32_t w, uint32_t h, const double*
                                const double* normal, const double* albedo, const double* depth, uint32_t levels,
                                double kn, double ka, double kz, double kv, double* out, double* out_variance);
 
+/* ---- temporal accumulation: a history of what earlier views have seen, reprojected into each new view and blended with its
+ * frame -- the temporal half of SVGF (Schied et al. 2017), where GUIDED FILTER above is the spatial half.  A film is bound to
+ * one camera; a history carries the samples of a static scene from one camera to the next, so that a turntable or a
+ * fly-through at 16 samples a frame shows more than 16 samples a frame.  Nothing here touches a path kernel or a film's state.
+ *
+ * TEMPORAL ACCUMULATION, specified to the operation.  A VIEW is a rayrs_camera and planes over its H x W pixels
+ * (H = y_pixels, W = x_pixels, row-major, origin upper left): colour c (3 f64), variance v (of (c.x+c.y)+c.z, as GUIDED FILTER
+ * has it), weight m (f64: how many samples the pixel stands for), and FEATURES' normal n, albedo a, depth z, coverage k,
+ * object o.  The history is a view B (primed below), the incoming frame a view A whose weight plane is wc; the scalars are
+ * max_weight > 0, tz2 = depth_tol*depth_tol and tn2 = normal_tol*normal_tol, formed on the host.  Ray::direction is not
+ * normalised (lib.rs:31) and e_x, e_y are perpendicular to z (lib.rs:117-131), so a primary hit's t is its planar view depth
+ * over |z| whatever the jitter, and with T the mean hit t the world point of a pixel centre is origin + T*(z + x*e_x + y*e_y):
+ * the reprojection needs no square root and no elementary function.  For pixel p = (r, col) of A every expression is f64,
+ * unfused, in the order written, and every condition is written in its positive form, so that a NaN takes the "no" side.
+ * "No history" means out = (c_p, v_p, wc_p).  dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *   1. Pass-through.  If a component of c_p is not finite, or not wc_p > 0: out colour = c_p, out variance = v_p, out
+ *      weight = wc_p if wc_p > 0, else +0.  (This step comes first on an empty history too.)
+ *   2. The centre ray of the pixel, the render's flipped indices (main.rs:74-75) with the jitter replaced by 0.5:
+ *        x = ((double)(W - col) + 0.5) / (double)ppc - width/2.
+ *        y = ((double)(H - r) + 0.5) / (double)ppc - height/2.
+ *        d = (z_cam + x*e_x) + y*e_y   per component, as lib.rs:209 forms it.
+ *   3. The source vector.  If k_p > 0 (a hit pixel): T = z_p / k_p, P = origin_A + d*T, u = P - origin_B.  If k_p == 0
+ *      (background: the environment is at infinity, only the direction matters): u = d.  Otherwise: no history.
+ *   4. Into B.  s = dot(u, z'), zz = dot(z', z').  No history unless s > 0.  tp = s/zz,
+ *        xp = (dot(u,e_x')*zz)/s,  yp = (dot(u,e_y')*zz)/s,
+ *        fx = ((double)W' + 0.5) - (xp + width'/2.)*(double)ppc'
+ *        fy = ((double)H' + 0.5) - (yp + height'/2.)*(double)ppc'
+ *      (fx == col' is the centre of column col').  No history unless fx >= -1 && fx < W' && fy >= -1 && fy < H'.
+ *      x0 = floor(fx), ax = fx - x0; y0, ay likewise.
+ *   5. The taps.  bs = 0, hc = (0,0,0), hv = 0, hm = 0, and for j = 0,1 (outer), i = 0,1 (inner), q = (y0+j, x0+i),
+ *      b = (i ? ax : 1-ax) * (j ? ay : 1-ay):  skip q if it lies outside B; if b == 0; if a component of c'_q is not finite; if
+ *      not v'_q >= 0; if not m'_q > 0; if it is not geometrically valid -- for a background p: k'_q == 0; for a hit p all of
+ *        k'_q > 0 and o'_q == o_p;
+ *        with Tq = z'_q/k'_q and dt = Tq - tp:  dt*dt <= tz2*(tp*tp);
+ *        ((n_p.x-n'_q.x)^2 + (n_p.y-n'_q.y)^2) + (n_p.z-n'_q.z)^2 <= tn2.
+ *      (Each is a plain skip: the order they are tried in changes no result.)  For a valid tap
+ *        bs += b;  hc += c'_q*b per component (the product first);  hv += v'_q*b;  hm += m'_q*b.
+ *      The variance is interpolated linearly: an upper bound under full correlation, which is the case for neighbouring taps
+ *      of a filtered history.
+ *   6. If bs == 0 (no valid tap): no history.
+ *   7. C = hc/bs per component, V = hv/bs, M0 = hm/bs, M = (M0 < max_weight) ? M0 : max_weight.
+ *   8. Healing -- a frame with fewer than two chunks must not poison a static view for ever:
+ *        vp = (v_p >= 0) ? v_p : +infinity;
+ *        if vp == +infinity and V < +infinity:  vp = (V*M0)/wc_p;  else if V == +infinity and vp < +infinity:  V = (vp*wc_p)/M0.
+ *   9. The blend.  alpha = wc_p/(wc_p + M), beta = 1 - alpha;
+ *        out colour = C*beta + c_p*alpha per component (two products, then the sum);
+ *        out variance = tb + ta,  tb = (beta*beta == 0) ? +0 : V*(beta*beta),  ta = (alpha*alpha == 0) ? +0 : vp*(alpha*alpha);
+ *        out weight = M + wc_p.
+ *  10. After the push the history's camera and feature planes are A's, unchanged; its colour, variance and weight are the
+ *      outputs.  A push into an empty history is step 1, and "no history" for every other pixel.  B's size may differ from A's.
+ * KNOWN LIMIT.  What is reprojected is the first hit: reflections and refractions in mirror and glass objects move with the
+ * surface that shows them and lag behind the view.  max_weight bounds the lag (alpha >= wc/(wc + max_weight)).
+ *
+ * ORBIT.  rayrs_camera_orbit turns `origin` by `degrees` about the axis through `lookat` along `up` (Rodrigues' rotation) with
+ * rr_sin / rr_cos of include/rayrs_numeric.h, so that every caller builds the same cameras to the bit:
+ *     n2 = (up.x*up.x + up.y*up.y) + up.z*up.z;  inv = 1.0/rr_sqrt(n2);  k = up*inv;  v = origin - lookat;
+ *     rad = degrees * (RR_PI/180.0);  c = rr_cos(rad);  s = rr_sin(rad);
+ *     kv = (k.x*v.x + k.y*v.y) + k.z*v.z;  g = kv*(1.0 - c);
+ *     x = (k.y*v.z - k.z*v.y, k.z*v.x - k.x*v.z, k.x*v.y - k.y*v.x);
+ *     out = lookat + ((v*c + x*s) + k*g)   per component;
+ * degrees == 0 returns `origin` itself, bit for bit, so that the first frame of an orbit is the frame of the camera as given.
+ * RAYRS_INVALID_ARG for a null pointer, degrees that are not finite, an `up` whose n2 is not > 0 or not finite.
+ *
+ * Refusals, all decided before the device is touched, mirroring rayrs_film_denoise_guided: RAYRS_INVALID_ARG for a NULL
+ * required plane, an empty image, max_weight not > 0 or not finite, a negative or non-finite tolerance, a bad out_format,
+ * levels or k as DENOISER has them, an empty film, a film with tile_ranks > 1, a film on another device than the history, a
+ * read or a filter on an empty history; RAYRS_UNSUPPORTED for an image side > 65535; then RAYRS_NO_DEVICE (a history made
+ * with device = -1).  Neither film call changes anything a later pass, rayrs_film_read, rayrs_film_status_get or
+ * rayrs_film_state_get returns.  The calls on one history, and on the film it is handed, come from one thread at a time. */
+typedef struct rayrs_history rayrs_history;
+
+/* An empty history on HIP device `device`, which is first touched by a push. */
+int rayrs_history_create(int device, rayrs_history** out);
+void rayrs_history_destroy(rayrs_history* history);
+/* Empties the history; its buffers are kept. */
+int rayrs_history_reset(rayrs_history* history);
+/* Pushes a view of the caller's: host planes of the camera's H x W pixels -- color, normal, albedo: H*W*3 f64; variance,
+ * weight, depth, coverage: H*W f64; object: H*W u32.  albedo may be NULL: it is only carried for the filter, which then has
+ * no albedo term. */
+int rayrs_history_push_image(rayrs_history* history, const rayrs_camera* camera, const double* color, const double* variance,
+                             const double* weight, const double* normal, const double* albedo, const double* depth,
+                             const double* coverage, const uint32_t* object, double max_weight, double depth_tol,
+                             double normal_tol);
+/* Pushes the film as it stands, everything staying on the device: the frame rayrs_film_read(RAYRS_OUT_F64) returns, the plane
+ * rayrs_film_noise returns, weight = (double)N_t of the pixel's tile, and the film's features of `feature_samples` samples
+ * (the object plane as rayrs_film_features numbers it). */
+int rayrs_history_push_film(rayrs_history* history, rayrs_film* film, uint32_t feature_samples, double max_weight,
+                            double depth_tol, double normal_tol);
+/* HIP-event times of the last push, if it was a rayrs_history_push_film (else RAYRS_INVALID_ARG), in milliseconds: the
+ * features pass (0 if the film held them), the frame, the noise plane, the copies of the features into the history, the
+ * reprojection. */
+int rayrs_history_push_times(rayrs_history* history, double ms[5]);
+/* The history's colour (H*W*3), variance and weight (H*W each) into host buffers, each of which may be NULL; RAYRS_OUT_F64,
+ * or RAYRS_OUT_F32: every f64 value converted.  RAYRS_INVALID_ARG on an empty history. */
+int rayrs_history_read(rayrs_history* history, uint32_t out_format, void* color, void* variance, void* weight);
+/* GUIDED FILTER on the history's colour and variance with its current normal, albedo and depth planes; out_host and
+ * out_variance as rayrs_film_denoise_guided's. */
+int rayrs_history_denoise_guided(rayrs_history* history, uint32_t levels, double kn, double ka, double kz, double kv,
+                                 uint32_t out_format, void* out_host, double* out_variance);
+/* ORBIT above. */
+int rayrs_camera_orbit(const double origin[3], const double up[3], const double lookat[3], double degrees, double out_origin[3]);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -617,7 +719,7 @@ int rayrs_image_denoise_guided(int device, uint32_t w, uint32_t h, const double*
  * rayrs_film_status; no existing struct changed); still 7 with rayrs_film_render_adaptive and rayrs_film_tile_samples: entry points
  * were added, no struct or existing call changed; and with rayrs_render_features, rayrs_film_features, rayrs_film_denoise and
  * rayrs_image_denoise, for the same reason, and with rayrs_film_noise, rayrs_film_denoise_guided and
- * rayrs_image_denoise_guided.  The layout table below begins with this
+ * rayrs_image_denoise_guided, and with rayrs_history_* and rayrs_camera_orbit (TEMPORAL ACCUMULATION).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

@@ -27,6 +27,8 @@ SYMBOLS = [
     "rayrs_film_render_adaptive", "rayrs_film_tile_samples",
     "rayrs_render_features", "rayrs_film_features", "rayrs_film_denoise", "rayrs_image_denoise",
     "rayrs_film_noise", "rayrs_film_denoise_guided", "rayrs_image_denoise_guided",
+    "rayrs_history_create", "rayrs_history_destroy", "rayrs_history_reset", "rayrs_history_push_image", "rayrs_history_push_film",
+    "rayrs_history_push_times", "rayrs_history_read", "rayrs_history_denoise_guided", "rayrs_camera_orbit",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -214,9 +216,20 @@ def lib():
                        ("rayrs_film_noise", [vp, vp]),
                        ("rayrs_film_denoise_guided", [vp, C.c_uint32, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, vp, vp]),
                        ("rayrs_image_denoise_guided", [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32] + [C.c_double] * 4
-                        + [vp, vp])):
+                        + [vp, vp]),
+                       ("rayrs_history_create", [C.c_int, C.POINTER(vp)]),
+                       ("rayrs_history_destroy", [vp]),
+                       ("rayrs_history_reset", [vp]),
+                       ("rayrs_history_push_image", [vp, C.POINTER(CameraDesc)] + [vp] * 8 + [C.c_double] * 3),
+                       ("rayrs_history_push_film", [vp, vp, C.c_uint32] + [C.c_double] * 3),
+                       ("rayrs_history_push_times", [vp, dp]),
+                       ("rayrs_history_read", [vp, C.c_uint32, vp, vp, vp]),
+                       ("rayrs_history_denoise_guided", [vp, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, vp, vp]),
+                       ("rayrs_camera_orbit", [dp, dp, dp, C.c_double, dp])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
+    if hasattr(L, "rayrs_history_destroy"):
+        L.rayrs_history_destroy.restype = None
     L.rayrs_test_math.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
     L.rayrs_test_rng.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
     L.rayrs_test_intersect.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp]

@@ -761,3 +761,148 @@ def render_until(film, tau: float, max_unconverged_fraction: float = 0.0, pass_s
         st["tile_samples_max"] = int(per_pixel.max()) if per_pixel.size else 0
         st["pixel_samples"] = int(per_pixel.astype(np.uint64).sum())
     return st, reason
+
+
+# ---- temporal accumulation (include/rayrs_hip.h TEMPORAL ACCUMULATION)
+
+# Starting points, not tuned values: the weight a history pixel may carry into a blend, in samples (16 frames of 16); the
+# relative depth difference and the distance of unit normals within which a tap of the history counts as the same surface.
+TEMPORAL_MAX_SAMPLES = 256
+TEMPORAL_DEPTH_TOL = 0.02
+TEMPORAL_NORMAL_TOL = 0.25
+
+
+def orbit(camera: Camera, degrees: float) -> Camera:
+    """The camera turned by `degrees` about the axis through its lookat along its up (rayrs_camera_orbit: the same origin,
+    to the bit, as the command line's --orbit builds)."""
+    origin, up, lookat, fov, width, height, ppi = camera.args
+    out = (C.c_double * 3)()
+    st = _ffi.lib().rayrs_camera_orbit(_d3(origin), _d3(up), _d3(lookat), float(degrees), out)
+    if st == -1:
+        raise ValueError("rayrs_camera_orbit: invalid argument")
+    _ffi.check(st, "rayrs_camera_orbit")
+    return Camera(tuple(out), up, lookat, fov, width, height, ppi)
+
+
+class History:
+    """What earlier views of a static scene have seen, reprojected into each new view and blended with its frame
+    (include/rayrs_hip.h TEMPORAL ACCUMULATION).  push(film) takes a film as it stands, on the device; image(),
+    variance() and weight() read the history, denoised_guided() puts it through the variance-guided filter.  The defaults
+    of max_samples, depth_tol and normal_tol are starting points (TEMPORAL_* above), as the filters' sigmas are."""
+
+    def __init__(self, device: int = 0):
+        self._L, self._h = _ffi.lib(), None
+        self.camera, self.scene = None, None
+        h = C.c_void_p()
+        _ffi.check(self._L.rayrs_history_create(int(device), C.byref(h)), "rayrs_history_create")
+        self._h = h
+
+    def push(self, film: "Film", feature_samples: int = 16, max_samples: float = TEMPORAL_MAX_SAMPLES,
+             depth_tol: float = TEMPORAL_DEPTH_TOL, normal_tol: float = TEMPORAL_NORMAL_TOL):
+        """Blends the film's frame, with its noise plane and its tiles' sample counts as weights, into the history as seen
+        from the film's camera.  The film is unchanged."""
+        _ffi.check(self._L.rayrs_history_push_film(self._h, film._h, int(feature_samples), float(max_samples), float(depth_tol),
+                                                   float(normal_tol)), "rayrs_history_push_film")
+        self.camera, self.scene = film.camera, film.scene
+        return self
+
+    def push_image(self, camera: Camera, color, variance, weight, normal, albedo, depth, coverage, object,
+                   max_samples: float = TEMPORAL_MAX_SAMPLES, depth_tol: float = TEMPORAL_DEPTH_TOL,
+                   normal_tol: float = TEMPORAL_NORMAL_TOL):
+        """The same with planes of the caller's, (H, W[, 3]) of the camera's size; albedo may be None."""
+        color, (variance, weight, normal, albedo, depth, coverage) = _filter_inputs(
+            color, [(variance, ()), (weight, ()), (normal, (3,)), (albedo, (3,)), (depth, ()), (coverage, ())], "plane", variance=True)
+        H, W = color.shape[:2]
+        obj = np.ascontiguousarray(object, dtype=np.uint32)
+        if (H, W) != (camera.y_pixels(), camera.x_pixels()) or obj.shape != (H, W):
+            raise ValueError(f"planes must be {(camera.y_pixels(), camera.x_pixels())}")
+        if weight is None or normal is None or depth is None or coverage is None:
+            raise ValueError("weight, normal, depth and coverage are required")
+        _ffi.check(self._L.rayrs_history_push_image(self._h, C.byref(camera.desc), color.ctypes.data, variance.ctypes.data,
+                                                    weight.ctypes.data, normal.ctypes.data, _ptr(albedo), depth.ctypes.data,
+                                                    coverage.ctypes.data, obj.ctypes.data, float(max_samples), float(depth_tol),
+                                                    float(normal_tol)), "rayrs_history_push_image")
+        self.camera = camera
+        return self
+
+    def _shape(self):
+        if self.camera is None:
+            raise _ffi.RayrsError(-1, "rayrs_history_read")  # an empty history
+        return self.camera.y_pixels(), self.camera.x_pixels()
+
+    def read(self, out_f64: bool = True):
+        """(colour, variance, weight) in one call."""
+        H, W = self._shape()
+        dt = np.float64 if out_f64 else np.float32
+        c, v, m = np.zeros((H, W, 3), dtype=dt), np.zeros((H, W), dtype=dt), np.zeros((H, W), dtype=dt)
+        _ffi.check(self._L.rayrs_history_read(self._h, 1 if out_f64 else 0, c.ctypes.data, v.ctypes.data, m.ctypes.data),
+                   "rayrs_history_read")
+        return c, v, m
+
+    def image(self, out_f64: bool = False):
+        H, W = self._shape()
+        out = np.zeros((H, W, 3), dtype=np.float64 if out_f64 else np.float32)
+        _ffi.check(self._L.rayrs_history_read(self._h, 1 if out_f64 else 0, out.ctypes.data, None, None), "rayrs_history_read")
+        return out
+
+    def variance(self):
+        H, W = self._shape()
+        out = np.zeros((H, W))
+        _ffi.check(self._L.rayrs_history_read(self._h, 1, None, out.ctypes.data, None), "rayrs_history_read")
+        return out
+
+    def weight(self):
+        H, W = self._shape()
+        out = np.zeros((H, W))
+        _ffi.check(self._L.rayrs_history_read(self._h, 1, None, None, out.ctypes.data), "rayrs_history_read")
+        return out
+
+    def push_times(self) -> dict:
+        """HIP-event times of the last push(film), in milliseconds."""
+        ms = (C.c_double * 5)()
+        _ffi.check(self._L.rayrs_history_push_times(self._h, ms), "rayrs_history_push_times")
+        return dict(zip(("features_ms", "read_ms", "noise_ms", "copy_ms", "reproject_ms"), ms))
+
+    def denoised_guided(self, levels: int = 5, sigma_normal=SIGMA_NORMAL, sigma_albedo=SIGMA_ALBEDO, sigma_depth="scene",
+                        sigma_luminance=SIGMA_LUMINANCE, out_f64: bool = False, return_variance: bool = False):
+        """The history through the variance-guided filter (GUIDED FILTER) with the features of the view pushed last; sigmas
+        as Film.denoised_guided -- sigma_depth="scene" is the default of the scene of the film pushed last, and no depth term
+        after push_image."""
+        if isinstance(sigma_depth, str):
+            sigma_depth = scene_sigma_depth(self.scene) if self.scene is not None else None
+        H, W = self._shape()
+        out = np.zeros((H, W, 3), dtype=np.float64 if out_f64 else np.float32)
+        out_var = np.zeros((H, W)) if return_variance else None
+        _ffi.check(self._L.rayrs_history_denoise_guided(self._h, int(levels), _k(sigma_normal), _k(sigma_albedo), _k(sigma_depth),
+                                                        _k(sigma_luminance), 1 if out_f64 else 0, out.ctypes.data, _ptr(out_var)),
+                   "rayrs_history_denoise_guided")
+        return (out, out_var) if return_variance else out
+
+    def reset(self):
+        _ffi.check(self._L.rayrs_history_reset(self._h), "rayrs_history_reset")
+        self.camera = None
+
+    def close(self):
+        if self._h is not None:
+            self._L.rayrs_history_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def render_sequence(scene: Scene, cameras, samples: int, sample_chunk: int = 4, history: Optional[History] = None,
+                    feature_samples: int = 16, max_samples: float = TEMPORAL_MAX_SAMPLES, depth_tol: float = TEMPORAL_DEPTH_TOL,
+                    normal_tol: float = TEMPORAL_NORMAL_TOL, **film_args):
+    """For each camera: a film of `samples` samples, pushed into the history (a new one on the scene's device unless given).
+    Yields (film, history) per camera, the history as it stands after that film's push; film_args go to Film()."""
+    if history is None:
+        history = History(device=int(scene._L.rayrs_scene_device(scene._h)))
+    for camera in cameras:
+        film = Film(scene, camera, sample_chunk=sample_chunk, **film_args)
+        film.render(int(samples))
+        history.push(film, feature_samples=feature_samples, max_samples=max_samples, depth_tol=depth_tol, normal_tol=normal_tol)
+        yield film, history

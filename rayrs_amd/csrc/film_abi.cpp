@@ -13,6 +13,7 @@
 #include "denoise_host.hpp"
 #include "features_host.hpp"
 #include "film.h"
+#include "film_host.hpp"
 #include "scene_internal.hpp"
 
 using namespace rayrs;
@@ -438,3 +439,39 @@ int rayrs_film_state_set(rayrs_film* film, const void* in_host, uint64_t bytes) 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ film_host.hpp: a film's view for a history
+
+namespace rayrs {
+
+int film_view_check(const rayrs_film* film, uint32_t feature_samples, int* device) {
+    if (!film || film->samples == 0) return RAYRS_INVALID_ARG;
+    if (film->prm.tile_ranks > 1u) return RAYRS_INVALID_ARG;  // reprojection reads a pixel's neighbours, as the filters do
+    RAYRS_TRY(features_check(&film->camera, feature_samples, film->prm.tile_rank, film->prm.tile_ranks, film->prm.fast_traversal));
+    *device = film->scene->device;
+    return RAYRS_OK;
+}
+
+// (the sequence rayrs_film_denoise_guided prepares its inputs with, here with the events between its steps)
+int film_view(rayrs_film* film, uint32_t feature_samples, FilmView* out, const hipEvent_t* marks) {
+    RAYRS_TRY(film_enter(film));
+    RAYRS_TRY(film_features(film, feature_samples));
+    if (marks) HIP_TRY(hipEventRecord(marks[0], nullptr));
+    const uint32_t w = film->camera.x_pixels, h = film->camera.y_pixels;
+    HIP_TRY(film->d_out.reserve(frame_bytes(w, h, RAYRS_OUT_F64)));
+    const CameraDev cam = make_camera_dev(&film->camera);
+    HIP_TRY(launch_film_read(cam, film->share.tiles_x, film->d_rec.as<double>(), film->d_tile_n.as<uint32_t>(), RAYRS_OUT_F64,
+                             film->d_out.as<>(), nullptr));
+    if (marks) HIP_TRY(hipEventRecord(marks[1], nullptr));
+    RAYRS_TRY(film_noise_plane(film));
+    if (marks) HIP_TRY(hipEventRecord(marks[2], nullptr));
+    out->scene = film->scene, out->camera = &film->camera;
+    out->color = film->d_out.as<double>(), out->variance = film->d_var.as<double>();
+    out->tile_n = film->d_tile_n.as<uint32_t>(), out->tiles_x = film->share.tiles_x;
+    out->normal = film->feat.normal.as<double>(), out->albedo = film->feat.albedo.as<double>();
+    out->depth = film->feat.depth.as<double>(), out->coverage = film->feat.coverage.as<double>();
+    out->prim = film->feat.prim.as<uint32_t>();
+    return RAYRS_OK;
+}
+
+}  // namespace rayrs

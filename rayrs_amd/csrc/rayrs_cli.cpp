@@ -147,6 +147,11 @@ int main(int argc, char** argv) {
     uint32_t denoise_levels = 5;
     bool want_guided = false, want_noise = false;
     uint32_t guided_levels = 5;
+    uint32_t orbit_frames = 0;  // --orbit FRAMES DEGREES: frame i from the camera turned by i * DEGREES / FRAMES about its up through its lookat
+    double orbit_degrees = 0.0;
+    bool orbit_given = false, temporal = false;  // --temporal: every frame's film is pushed into one history
+    // starting points, as rayrs_amd/api.py TEMPORAL_*: the history's weight cap in samples, relative depth and normal tolerance
+    constexpr double TEMPORAL_MAX_SAMPLES = 256.0, TEMPORAL_DEPTH_TOL = 0.02, TEMPORAL_NORMAL_TOL = 0.25;
     constexpr double SIGMA_LUMINANCE = 4.0;  // rayrs_amd/api.py SIGMA_LUMINANCE: SVGF's, in standard deviations of the pixel
     constexpr uint32_t FEATURE_SAMPLES = 16;
     // starting points chosen by eye, as rayrs_amd/api.py SIGMA_*: normal, albedo, depth as a fraction of the root-box diagonal, colour
@@ -174,6 +179,20 @@ int main(int argc, char** argv) {
         if (opt == "--noise") {
             want_noise = true;
             i--;
+            continue;
+        }
+        if (opt == "--temporal") {
+            temporal = true;
+            i--;
+            continue;
+        }
+        if (opt == "--orbit") {  // two values
+            orbit_given = true;
+            if (i + 2 < argc) {
+                orbit_frames = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10);
+                orbit_degrees = std::strtod(argv[i + 2], nullptr);
+            }
+            i++;
             continue;
         }
         if (opt == "--denoise-guided") {  // the level count is optional
@@ -233,6 +252,22 @@ int main(int argc, char** argv) {
     }
     if ((want_guided || want_noise) && !use_film) {
         std::fprintf(stderr, "Usage: --denoise-guided and --noise read a film's noise estimate: give --pass N (or --until-noise TAU)\n");
+        return 2;
+    }
+    if ((orbit_given || temporal) && (!use_film || pass == 0)) {
+        std::fprintf(stderr, "Usage: --orbit FRAMES DEGREES and --temporal render every frame through a film: give --pass N\n");
+        return 2;
+    }
+    if (temporal && !orbit_given) {
+        std::fprintf(stderr, "Usage: --temporal accumulates the frames of an orbit: give --orbit FRAMES DEGREES\n");
+        return 2;
+    }
+    if (orbit_given && (orbit_frames == 0 || !std::isfinite(orbit_degrees))) {
+        std::fprintf(stderr, "Usage: --orbit FRAMES DEGREES, FRAMES >= 1\n");
+        return 2;
+    }
+    if (orbit_given && (adaptive || until_noise || want_features || want_noise || want_denoise)) {
+        std::fprintf(stderr, "Usage: --orbit writes each frame, with --temporal the history and with --denoise-guided the filtered one; it takes no other extra\n");
         return 2;
     }
     if (use_film && (!chunk_given || sample_chunk == 0)) sample_chunk = 4;
@@ -298,7 +333,7 @@ int main(int argc, char** argv) {
     // --denoise filters the f64 frame: a plain render is then asked for f64 and converted here, which is the conversion
     // the f32 output format makes at its store -- the same <scene>.png and <scene>.hdr
     std::vector<double> rgb64(want_denoise && !use_film ? npix * 3 : 0);
-    std::vector<float> extra(want_denoise || want_features || want_guided || want_noise ? npix * 3 : 0);
+    std::vector<float> extra(want_denoise || want_features || want_guided || want_noise || temporal ? npix * 3 : 0);
     auto write_extra = [&](const char* suffix, double gamma, bool png) -> int {
         const std::string name = scene_name + suffix + (png ? ".png" : ".hdr");
         if (!png) return rayrs_hdr_save(name.c_str(), extra.data(), cam.x_pixels, cam.y_pixels);
@@ -347,6 +382,57 @@ int main(int argc, char** argv) {
         if ((s = rayrs_hdr_save((scene_name + ".hdr").c_str(), rgb.data(), cam.x_pixels, cam.y_pixels)) != RAYRS_OK) return fail("hdr", s), s;
         return RAYRS_OK;
     };
+    if (orbit_given) {
+        // <scene>_%04d.png/.hdr per frame; --temporal: <scene>_%04d_temporal.*, the history after the frame's push;
+        // --denoise-guided: <scene>_%04d_guided.*, the history (--temporal) or the frame's film through the guided filter
+        const std::string base = scene_name;
+        const rayrs_camera cam0 = cam;
+        const double kv = 1.0 / (SIGMA_LUMINANCE * SIGMA_LUMINANCE);
+        rayrs_history* history = nullptr;
+        if (temporal && (st = rayrs_history_create(devices[0], &history)) != RAYRS_OK) return fail("history", st);
+        for (uint32_t frame = 0; frame < orbit_frames; frame++) {
+            char tag[16];
+            std::snprintf(tag, sizeof tag, "_%04u", frame);
+            scene_name = base + tag;
+            double origin[3];
+            if ((st = rayrs_camera_orbit(def.cam_origin, up, def.cam_lookat, ((double)frame * orbit_degrees) / (double)orbit_frames, origin)) != RAYRS_OK)
+                return fail("orbit", st);
+            if ((st = rayrs_camera_new(origin, up, def.cam_lookat, def.fov, def.width, def.height, def.ppi, &cam)) != RAYRS_OK)
+                return fail("camera", st);
+            if (cam.x_pixels != cam0.x_pixels || cam.y_pixels != cam0.y_pixels) return fail("camera", RAYRS_INVALID_ARG);
+            rayrs_film_params fprm;
+            std::memset(&fprm, 0, sizeof fprm);
+            fprm.sample_chunk = sample_chunk, fprm.max_bounces = max_bounces, fprm.seed = seed, fprm.fast_traversal = fast_traversal;
+            rayrs_film* film = nullptr;
+            if ((st = rayrs_film_create(scene, &cam, &fprm, &film)) != RAYRS_OK) return fail("film", st);
+            for (uint32_t done = 0; done < spp;) {
+                const uint32_t n = spp - done < pass ? spp - done : pass;
+                if ((st = rayrs_film_render(film, n, nullptr)) != RAYRS_OK) return fail("film pass", st);
+                done += n;
+            }
+            if ((st = rayrs_film_read(film, RAYRS_OUT_F32, rgb.data())) != RAYRS_OK) return fail("film read", st);
+            if (write_files(false) != RAYRS_OK) return 1;
+            if (temporal) {
+                if ((st = rayrs_history_push_film(history, film, FEATURE_SAMPLES, TEMPORAL_MAX_SAMPLES, TEMPORAL_DEPTH_TOL, TEMPORAL_NORMAL_TOL)) != RAYRS_OK)
+                    return fail("history push", st);
+                if ((st = rayrs_history_read(history, RAYRS_OUT_F32, extra.data(), nullptr, nullptr)) != RAYRS_OK) return fail("history read", st);
+                if ((st = write_extra("_temporal", 1. / 2.2, true)) != RAYRS_OK) return fail("temporal png", st);
+                if ((st = write_extra("_temporal", 1.0, false)) != RAYRS_OK) return fail("temporal hdr", st);
+            }
+            if (want_guided) {
+                st = temporal ? rayrs_history_denoise_guided(history, guided_levels, kn, ka, kz, kv, RAYRS_OUT_F32, extra.data(), nullptr)
+                              : rayrs_film_denoise_guided(film, FEATURE_SAMPLES, guided_levels, kn, ka, kz, kv, RAYRS_OUT_F32, extra.data(), nullptr);
+                if (st != RAYRS_OK) return fail("denoise guided", st);
+                if ((st = write_extra("_guided", 1. / 2.2, true)) != RAYRS_OK) return fail("guided png", st);
+                if ((st = write_extra("_guided", 1.0, false)) != RAYRS_OK) return fail("guided hdr", st);
+            }
+            rayrs_film_destroy(film);
+            std::printf("Frame %u of %u: %.6g degrees\n", frame + 1, orbit_frames, ((double)frame * orbit_degrees) / (double)orbit_frames);
+        }
+        rayrs_history_destroy(history);
+        for (rayrs_scene* sc : scenes) rayrs_scene_destroy(sc);
+        return 0;
+    }
     rayrs_render_stats stats;
     std::memset(&stats, 0, sizeof stats);
     const auto t0 = std::chrono::steady_clock::now();
