@@ -712,6 +712,61 @@ int rayrs_history_denoise_guided(rayrs_history* history, uint32_t levels, double
 /* ORBIT above. */
 int rayrs_camera_orbit(const double origin[3], const double up[3], const double lookat[3], double degrees, double out_origin[3]);
 
+/* ---- ray queries: the scene asked about rays of the caller's -- picking, probes, baking, visibility, shadow and
+ * ambient-occlusion rays -- in batches, on the host or on device-resident buffers on a stream.  Nothing here touches a path
+ * kernel, a film or a render's buffers: the kernels are a unit of their own (query.hip).
+ *
+ * RAY QUERIES, specified to the operation.  A ray is (o, d), three f64 each, USED AS GIVEN: Ray::direction is not normalised
+ * (lib.rs:31), so t is in units of |d|.  Any f64 is a legal component -- NaN, infinities, a zero direction: the walk treats
+ * them as the reference's arithmetic does.
+ *
+ * CLOSEST HIT (rayrs_scene_intersect).  The query is the render's: Bvh::intersect (bvh.rs:212-214, :391-415) with the scene's
+ * z_near, z_far.  fast_traversal = 0 takes the default walk of rayrs_render_params.fast_traversal, the reference's visit set
+ * by construction; fast_traversal = 1 takes the fast walk with both of its bets.  There is no camera here, so the camera rule
+ * does not apply: fast_traversal = 1 is taken AS ASKED, and the rule's caveat -- from far away the leaf-box bet fails for
+ * about one in-plane ray in 10^4 -- applies to the caller's rays, whose origins the library does not look at.  Per ray, on a
+ * hit of object obj at t:
+ *     t      = t (f64)
+ *     object = obj (u32), in insertion order as rayrs_scene_export_bvh's prim_object numbers them
+ *     normal = FEATURES' normal_s: obj.geom.normal(r.point(t)), what radiance hands to Material::evaluate (lib.rs:528-529),
+ *              NOT flipped towards the ray's origin; 3 f64; the buffer may be NULL = not wanted
+ * and on a miss t = +0, object = 0xFFFFFFFF, normal = (+0, +0, +0).
+ *
+ * OCCLUSION (rayrs_scene_occluded).  occluded_i = 1 iff the closest-hit query above finds a hit and t < t_max_i, else 0;
+ * one uint8_t per ray.  The condition is in its positive form, so a NaN, zero or negative t_max gives 0; t_max == NULL means
+ * +infinity for every ray.  t_max is never handed to a box test or to the accept rule: the visit set and the acceptance window
+ * stay (z_near, z_far), which keeps the verdict a function of the closest-hit answer alone.  The walk behind it is an ANY-HIT
+ * walk: it culls nothing, so which primitives a ray is tested of is decided by the boxes alone and the closest hit is among
+ * them; an accepted t < t_max anywhere in that set implies the closest is < t_max, in any visiting order -- so a ray stops at
+ * the first such hit instead of paying for its whole visit set.  fast_traversal = 0: the default walk's trees (the verdict is
+ * the reference's for every ray by construction).  fast_traversal = 1: the tree of single primitives behind their own boxes
+ * (rayrs_scene_export_wide) with NOTHING CULLED and the same early exit -- the leaf-box bet WITHOUT the culling bet; its
+ * verdict is "a hit with t < t_max over that tree's visit set".
+ *
+ * The first two entry points take HOST buffers and are synchronous.  The _launch forms take DEVICE pointers on the scene's
+ * device and a hipStream_t (NULL = the default stream), enqueue and return without a host wait: what the caller enqueues on
+ * the stream afterwards is ordered behind the query, as it is behind rayrs_render_launch.  A batch goes through launches of
+ * at most 2^20 rays each.  After the first call of a given walk a _launch call allocates nothing.
+ *
+ * Refusals, all decided before the device is touched, in this order: RAYRS_INVALID_ARG for a NULL scene or a NULL required
+ * buffer (origin, direction, t, object; origin, direction, occluded) -- with n == 0 too; RAYRS_INVALID_ARG for
+ * fast_traversal > 1; RAYRS_NO_DEVICE for a host-only scene.  n == 0 on a device scene is RAYRS_OK and launches nothing.
+ *
+ * The calls on one scene come from one thread at a time.  A query owns its scratch (a strip for the traversal stacks' overflow,
+ * which the scene keeps, and the host forms' staging buffers) and touches nothing of a render's: it is ordered against a
+ * render in flight only by the streams.  Queries on one scene whose trees need the strip follow one another on the device
+ * whichever streams they are given (the later one's stream waits for the earlier one; no host wait). */
+int rayrs_scene_intersect(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t fast_traversal,
+                          double* t, uint32_t* object, double* normal /* may be NULL */);
+int rayrs_scene_occluded(rayrs_scene* scene, const double* origin, const double* direction, const double* t_max /* may be NULL */,
+                         uint64_t n, uint32_t fast_traversal, uint8_t* occluded);
+int rayrs_scene_intersect_launch(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n,
+                                 uint32_t fast_traversal, double* t, uint32_t* object, double* normal /* may be NULL */,
+                                 void* hip_stream);
+int rayrs_scene_occluded_launch(rayrs_scene* scene, const double* origin, const double* direction,
+                                const double* t_max /* may be NULL */, uint64_t n, uint32_t fast_traversal, uint8_t* occluded,
+                                void* hip_stream);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -719,7 +774,8 @@ int rayrs_camera_orbit(const double origin[3], const double up[3], const double 
  * rayrs_film_status; no existing struct changed); still 7 with rayrs_film_render_adaptive and rayrs_film_tile_samples: entry points
  * were added, no struct or existing call changed; and with rayrs_render_features, rayrs_film_features, rayrs_film_denoise and
  * rayrs_image_denoise, for the same reason, and with rayrs_film_noise, rayrs_film_denoise_guided and
- * rayrs_image_denoise_guided, and with rayrs_history_* and rayrs_camera_orbit (TEMPORAL ACCUMULATION).  The layout table below begins with this
+ * rayrs_image_denoise_guided, and with rayrs_history_* and rayrs_camera_orbit (TEMPORAL ACCUMULATION), and with
+ * rayrs_scene_intersect, rayrs_scene_occluded and their _launch forms (RAY QUERIES).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

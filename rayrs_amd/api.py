@@ -210,6 +210,11 @@ def _d3(v):
     return (C.c_double * 3)(*v)
 
 
+def _is_torch(a) -> bool:
+    """A torch tensor, told without importing torch where nobody uses it."""
+    return type(a).__module__.split(".")[0] == "torch"
+
+
 def flatten_objects(objects) -> List[Object]:
     out = []
     for o in objects:
@@ -367,6 +372,81 @@ class Scene:
         _ffi.check(self._L.rayrs_scene_export_hot_tree(self._h, box.ctypes.data, ref.ctypes.data),
                    "rayrs_scene_export_hot_tree")
         return box[:i["hot_n_wide"]], ref[:i["hot_n_wide"]]
+
+    # ---- ray queries (include/rayrs_hip.h RAY QUERIES)
+
+    def _query_inputs(self, origins, directions, t_max=None):
+        """The rays of a query, checked before any library call: (torch module or None, origins, directions, t_max, n).
+        numpy inputs become contiguous f64 arrays; torch tensors are taken as they are and must be f64, contiguous and on the
+        scene's GPU, all of them."""
+        given = [a for a in (origins, directions, t_max) if a is not None]
+        if any(_is_torch(a) for a in given):
+            import torch
+            for a in given:
+                if not _is_torch(a) or a.dtype != torch.float64 or not a.is_cuda or a.device.index != self.device \
+                        or not a.is_contiguous():
+                    raise ValueError(f"a query on device tensors takes contiguous float64 tensors on cuda:{self.device}, all of them")
+        else:
+            torch = None
+            origins, directions = (np.ascontiguousarray(a, dtype=np.float64) for a in (origins, directions))
+            t_max = None if t_max is None else np.ascontiguousarray(t_max, dtype=np.float64)
+        for a in (origins, directions):
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("origins and directions must be (n, 3)")
+        n = int(origins.shape[0])
+        if int(directions.shape[0]) != n:
+            raise ValueError("origins and directions must have the same length")
+        if t_max is not None and tuple(t_max.shape) != (n,):
+            raise ValueError(f"t_max must be ({n},)")
+        return torch, origins, directions, t_max, n
+
+    def intersect(self, origins, directions, fast_traversal: bool = False, normals: bool = False):
+        """The closest hit of every ray (origins[i], directions[i]), the render's query: (t, object) or, with normals,
+        (t, object, normal) -- t (n,) f64, object (n,) uint32 in insertion order (0xFFFFFFFF: a miss, t and normal then 0),
+        normal (n, 3) f64, not flipped.  (n, 3) numpy arrays are answered through host buffers and return numpy; f64 torch
+        tensors on the scene's GPU are answered on torch's current stream and return tensors there, nothing copied to the
+        host and no wait.  (For the device path import torch before the library is first used -- before the first Scene or
+        Camera -- as bench.py does: torch brings its own copy of the HIP runtime, and only a library loaded after it shares
+        torch's; loaded first, the process has two runtimes and torch finds no device.)"""
+        torch, o, d, _, n = self._query_inputs(origins, directions)
+        m = max(n, 1)  # (an empty batch still hands the library buffers)
+        if torch is None:
+            t, obj = np.zeros(m), np.zeros(m, dtype=np.uint32)
+            nrm = np.zeros((m, 3)) if normals else None
+            o, d = (a if n else np.zeros((1, 3)) for a in (o, d))
+            _ffi.check(self._L.rayrs_scene_intersect(self._h, o.ctypes.data, d.ctypes.data, n, int(bool(fast_traversal)),
+                                                     t.ctypes.data, obj.ctypes.data, _ptr(nrm)), "rayrs_scene_intersect")
+        else:
+            dev = o.device
+            t = torch.empty(m, dtype=torch.float64, device=dev)
+            obj = torch.empty(m, dtype=torch.int32, device=dev).view(torch.uint32)
+            nrm = torch.empty((m, 3), dtype=torch.float64, device=dev) if normals else None
+            o, d = (a if n else torch.zeros((1, 3), dtype=torch.float64, device=dev) for a in (o, d))
+            _ffi.check(self._L.rayrs_scene_intersect_launch(self._h, o.data_ptr(), d.data_ptr(), n, int(bool(fast_traversal)),
+                                                            t.data_ptr(), obj.data_ptr(), None if nrm is None else nrm.data_ptr(),
+                                                            torch.cuda.current_stream(dev).cuda_stream),
+                       "rayrs_scene_intersect_launch")
+        return (t[:n], obj[:n], nrm[:n]) if normals else (t[:n], obj[:n])
+
+    def occluded(self, origins, directions, t_max=None, fast_traversal: bool = False):
+        """Whether the closest hit of every ray lies before t_max[i] (None: anywhere), as a bool array: an any-hit walk that
+        stops at the first accepted hit with t < t_max.  A NaN, zero or negative t_max gives False.  Inputs and where the
+        answer lives as intersect()."""
+        torch, o, d, tm, n = self._query_inputs(origins, directions, t_max)
+        m = max(n, 1)
+        if torch is None:
+            occ = np.zeros(m, dtype=np.uint8)
+            o, d = (a if n else np.zeros((1, 3)) for a in (o, d))
+            _ffi.check(self._L.rayrs_scene_occluded(self._h, o.ctypes.data, d.ctypes.data, _ptr(tm) if n else None, n,
+                                                    int(bool(fast_traversal)), occ.ctypes.data), "rayrs_scene_occluded")
+            return occ[:n].astype(bool)
+        dev = o.device
+        occ = torch.empty(m, dtype=torch.uint8, device=dev)
+        o, d = (a if n else torch.zeros((1, 3), dtype=torch.float64, device=dev) for a in (o, d))
+        _ffi.check(self._L.rayrs_scene_occluded_launch(self._h, o.data_ptr(), d.data_ptr(), tm.data_ptr() if tm is not None and n else None,
+                                                       n, int(bool(fast_traversal)), occ.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream), "rayrs_scene_occluded_launch")
+        return occ[:n].view(torch.bool)
 
     def close(self):
         if self._h is not None:

@@ -821,6 +821,43 @@ RR_DEV bool lane_query(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack, d
                     : bvh_intersect<COMPACT, false, false>(sc, o, d, stack, t_hit, prim_hit, wc);
 }
 
+// ---- the any-hit walk (query.hip query_occluded_kernel; include/rayrs_hip.h RAY QUERIES): "does the closest-hit query
+// find a hit with t < t_max?" without finding the closest hit.  It is bvh_intersect's walk with the cull margin at
+// +infinity in BOTH modes -- EXACT only says whether the scene's hot group is owed its test first -- so which primitives
+// the ray is tested of is decided by the boxes alone (the comment above the leaf queue makes the same point), and the
+// closest hit is one of them.  An accepted t < t_max anywhere in that set therefore implies that the closest is < t_max,
+// and no accepted t < t_max implies that the closest is not: the verdict is the closest-hit verdict in any visiting order
+// and with any early exit.  So a lane is finished as soon as it holds such a hit: after the hot group and after every leaf
+// group.  t_max meets only that comparison -- never a box test, never take_hit: the acceptance window stays (t0, t1) --
+// and the comparison is in its positive form, so a NaN t_max finds nothing.
+RR_DEV bool occluded_found(const Trav& tv, double t_max) { return tv.best_prim != 0xffffffffu && tv.best_t < t_max; }
+
+// STEPS (rayrs_lab.h rayrs_lab_query_steps, never a query of the boundary's): `steps` counts the lane's turns of the loop.
+template <bool COMPACT, bool EXACT, bool STEPS = false>
+RR_DEV bool bvh_occluded(const SceneDev& sc, V3 o, V3 d, double t_max, const LaneStack& stack, uint32_t* steps = nullptr) {
+    Trav tv;
+    trav_init(sc, o, d, tv);
+    const HotNodes hot{nullptr, 0u};
+    WorkCount wc{};
+    // (as in bvh_intersect: the wave-level calls inside need every live lane of the wave, so the branch is on the
+    // wave-uniform pointer only, and no lane leaves before it)
+    if (EXACT && sc.hot != nullptr) {
+        HotTally ht{};
+        hot_group_step<false>(sc, o, d, tv.cur != TRAV_DONE, tv, wc, ht);
+        if (occluded_found(tv, t_max)) tv.cur = TRAV_DONE;
+    }
+    while (tv.cur != TRAV_DONE) {
+        if (STEPS) (*steps)++;
+        if (trav_at_interior(tv)) {
+            trav_interior_step<COMPACT, false, true>(sc, o, stack, hot, tv, wc);
+        } else {
+            trav_leaf_step<COMPACT, false>(sc, o, d, stack, tv, wc);
+            if (occluded_found(tv, t_max)) tv.cur = TRAV_DONE;
+        }
+    }
+    return occluded_found(tv, t_max);
+}
+
 // ---------------------------------------------------------------- materials
 
 struct CtLayer {  // struct CookTorrance, material.rs:194-200

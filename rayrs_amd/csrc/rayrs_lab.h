@@ -61,6 +61,14 @@ int rayrs_lab_round_ms(rayrs_scene* scene, float* out, uint32_t cap_rounds);
  * ncclReduce (counted over all rounds) reports an error.  log: ';'-separated record.  Returns the first non-OK status. */
 int rayrs_lab_multi_rehearse(const int* rank_devices, uint32_t n, uint32_t rounds, int fail_reduce_at, char* log, uint32_t cap);
 
+/* rayrs_scene_occluded (include/rayrs_hip.h RAY QUERIES) on host buffers through an instance of its kernel that also counts:
+ * steps[i] = the turns of the any-hit walk's loop ray i took (records visited + leaf groups tested) before it finished.  With
+ * a NaN t_max no ray stops early: the count is then the closest-hit query's on the same tree.  For scripts/ubench/query_bench.py's
+ * measure of how much of a wave idles (64 consecutive rays share a wave, which runs as long as its slowest lane).  Refusals as
+ * rayrs_scene_occluded's; steps is required. */
+int rayrs_lab_query_steps(rayrs_scene* scene, const double* origin, const double* direction, const double* t_max, uint64_t n,
+                          uint32_t fast_traversal, uint8_t* occluded, uint32_t* steps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,19 @@ int scene_upload(rayrs_scene* s) {
     return RAYRS_OK;
 }
 
+// Only the ray queries map a depth-first slot to its object on the device (a render's host side does it after the
+// download), so the table goes up with the first of them and stays.
+int scene_prim_object(rayrs_scene* s, const uint32_t** out) {
+    rayrs_scene::Queries& q = s->queries;
+    if (!q.has_prim_object) {
+        const std::vector<uint32_t>& prim_object = s->flat.prim_object;
+        HIP_TRY(q.d_prim_object.upload(prim_object.data(), prim_object.size() * sizeof(uint32_t)));
+        q.has_prim_object = true;
+    }
+    *out = q.d_prim_object.as<uint32_t>();
+    return RAYRS_OK;
+}
+
 SceneDev make_scene_dev(const rayrs_scene* s, bool exact) {
     SceneDev sc;
     std::memset(&sc, 0, sizeof(sc));

@@ -94,6 +94,16 @@ struct rayrs_scene {
         hipError_t wait();
     };
     Frame frame;
+    // What the ray queries (query_abi.cpp) keep between calls; nothing of it is a render's.
+    struct Queries {
+        rayrs::DevBuf d_prim_object;   // flat.prim_object, uploaded by the first closest-hit query (scene_device.cpp)
+        bool has_prim_object = false;
+        rayrs::DevBuf d_stack_spill;   // the traversal stacks' overflow of one launch, reserved at its largest size
+        rayrs::Event ev_done;          // behind the last launch that used the strip: the next query's stream waits for it
+        bool has_event = false, strip_in_use = false;
+        rayrs::DevBuf d_origin, d_direction, d_t_max, d_t, d_object, d_normal, d_occluded;  // the host forms' staging
+    };
+    Queries queries;
     // Scenes whose walk tree is at most one record are rendered by local_pool.hip: every path resident in LDS.
     bool local_ok = false;
     rayrs::LocalScene local = {};
@@ -124,6 +134,9 @@ int scene_configure_traversal(rayrs_scene* s);
 // what a render hands its kernels, for the self tests too (scene_device.cpp)
 SceneDev make_scene_dev(const rayrs_scene* s, bool exact);
 CameraDev make_camera_dev(const rayrs_camera* c);
+// the device copy of flat.prim_object (depth-first slot -> object in insertion order), uploaded at the first call
+// (scene_device.cpp; the scene's device is current)
+int scene_prim_object(rayrs_scene* s, const uint32_t** out);
 // the route and the walk of a frame with these settings (frame_plan.hpp frame_route, camera_is_far)
 FrameWalk frame_walk(const rayrs_scene* s, const rayrs_camera* c, uint32_t fast_traversal);
 // the traversal kernel's settings on a pool of np slots of this scene (frame_plan.hpp plan_traversal)
