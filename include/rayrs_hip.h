@@ -767,6 +767,55 @@ int rayrs_scene_occluded_launch(rayrs_scene* scene, const double* origin, const 
                                 const double* t_max /* may be NULL */, uint64_t n, uint32_t fast_traversal, uint8_t* occluded,
                                 void* hip_stream);
 
+/* ---- ambient occlusion: the consumer of the occlusion query above that the library can make the rays of itself -- a cosine
+ * lobe of `samples` rays around each point's normal, counted.  Nothing here touches a path kernel, a film or a render's
+ * buffers: the kernels are a unit of their own (ao.hip).
+ *
+ * AMBIENT OCCLUSION, specified to the operation.  A point is (p, n), three f64 each, USED AS GIVEN: the library does not
+ * normalise or inspect them.  samples = S >= 1; t_max, bias: one f64 each for the call; seed, index_base: u64.  For point i
+ * of the call and sample s in 0 .. S-1:
+ *     key = rr_path_key(seed, index_base + i, s)                         (rayrs_numeric.h)
+ *     u = rr_uniform(key, 0), v = rr_uniform(key, 1)
+ *     (e1, e2) = onb(n_i)                                                (vecmath.rs:341-352)
+ *     phi = 2.0 * RR_PI * v;  su = sqrt(u)
+ *     l = (e1 * (cos(phi) * su) + e2 * (sin(phi) * su)) + n_i * sqrt(1.0 - u)
+ *     o = p_i + n_i * bias
+ *     occ = OCCLUSION(o, l, t_max)                                       (RAY QUERIES: the same rule and the same walks)
+ * every operation f64 and unfused, in the operand and operation order of the reference's Lambertian scatter direction
+ * (material.rs:259-281, :982-993): the directions are that material's, bit for bit, on two draws each.  Per point:
+ *     count_i      = the number of samples with occ (u32)
+ *     visibility_i = (double)(S - count_i) / (double)S, one true division (f64)
+ * Either output buffer may be NULL = not wanted, but not both.  index_base makes a call on points[a:b] with index_base = a
+ * return the slice of the whole call's answer.  A NaN, zero or negative t_max gives count 0, by OCCLUSION's positive form;
+ * +infinity means anywhere.  fast_traversal means what it means for rayrs_scene_occluded.  The count is an integer sum, so it
+ * is the same bits however the kernel schedules a point's samples.
+ *
+ * AMBIENT OCCLUSION PLANE (rayrs_render_ao).  For pixel (row, col) take sample 0's primary ray as FEATURES forms it --
+ * sample_key(seed, cam, row, col, 0) and sample_ray -- and its closest hit by the render's query (the walk a render with
+ * these settings takes).  On a miss count = 0 and visibility = 1.0, and no AO ray is traced.  On a hit at t: p = o + d * t;
+ * n = FEATURES' normal_s turned against the ray (if n . d > 0.0 then n = n * -1.0); then the operation above at (p, n) with
+ * index_base + i = row * W + col and seed ao_seed -- a parameter of its own: with the primary seed, sample 0's draws 0 and 1
+ * would be the pixel jitter's.  The result is the whole frame's (H, W) planes in image order; there are no tile shares.
+ *
+ * rayrs_scene_ambient_occlusion takes HOST buffers and is synchronous, as rayrs_render_ao.  The _launch form takes DEVICE
+ * pointers on the scene's device and a hipStream_t (NULL = the default stream), enqueues and returns without a host wait; after
+ * the first call of a given walk it allocates nothing.  A batch goes through launches of at most 2^20 threads each, which share
+ * RAY QUERIES' stack strip and its ordering rule.
+ *
+ * Refusals, all decided before the device is touched, in RAY QUERIES' order: RAYRS_INVALID_ARG for a NULL scene, a NULL
+ * position or normal, both outputs NULL, samples == 0 or fast_traversal > 1 -- with n == 0 too; then RAYRS_NO_DEVICE for a
+ * host-only scene.  n == 0 on a device scene is RAYRS_OK and launches nothing.  rayrs_render_ao refuses a NULL camera and the
+ * cameras rayrs_render_features refuses, likewise before RAYRS_NO_DEVICE. */
+int rayrs_scene_ambient_occlusion(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                  double t_max, double bias, uint64_t seed, uint64_t index_base, uint32_t fast_traversal,
+                                  uint32_t* count /* may be NULL */, double* visibility /* may be NULL */);
+int rayrs_scene_ambient_occlusion_launch(rayrs_scene* scene, const double* position, const double* normal, uint64_t n,
+                                         uint32_t samples, double t_max, double bias, uint64_t seed, uint64_t index_base,
+                                         uint32_t fast_traversal, uint32_t* count /* may be NULL */,
+                                         double* visibility /* may be NULL */, void* hip_stream);
+int rayrs_render_ao(rayrs_scene* scene, const rayrs_camera* camera, uint64_t seed, uint64_t ao_seed, uint32_t samples, double t_max,
+                    double bias, uint32_t fast_traversal, uint32_t* count /* may be NULL */, double* visibility /* may be NULL */);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -775,7 +824,8 @@ int rayrs_scene_occluded_launch(rayrs_scene* scene, const double* origin, const 
  * were added, no struct or existing call changed; and with rayrs_render_features, rayrs_film_features, rayrs_film_denoise and
  * rayrs_image_denoise, for the same reason, and with rayrs_film_noise, rayrs_film_denoise_guided and
  * rayrs_image_denoise_guided, and with rayrs_history_* and rayrs_camera_orbit (TEMPORAL ACCUMULATION), and with
- * rayrs_scene_intersect, rayrs_scene_occluded and their _launch forms (RAY QUERIES).  The layout table below begins with this
+ * rayrs_scene_intersect, rayrs_scene_occluded and their _launch forms (RAY QUERIES), and with
+ * rayrs_scene_ambient_occlusion, its _launch form and rayrs_render_ao (AMBIENT OCCLUSION).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

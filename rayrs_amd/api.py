@@ -448,6 +448,39 @@ class Scene:
                                                        torch.cuda.current_stream(dev).cuda_stream), "rayrs_scene_occluded_launch")
         return occ[:n].view(torch.bool)
 
+    # ---- ambient occlusion (include/rayrs_hip.h AMBIENT OCCLUSION)
+
+    def ambient_occlusion(self, points, normals, samples: int = 16, t_max=None, bias: float = 0.0, seed: int = 0x5EED,
+                          index_base: int = 0, fast_traversal: bool = False, counts: bool = False):
+        """The share of `samples` cosine-distributed rays around normals[i], leaving points[i] + normals[i] * bias, that
+        reach t_max (None: anywhere) unoccluded: visibility (n,) f64, and with counts also the occluded samples per point,
+        (n,) uint32.  Points and normals are used as given.  A call on points[a:b] with index_base=a returns the slice of the
+        whole call's answer.  Inputs and where the answers live as intersect()."""
+        torch, p, nrm, _, n = self._query_inputs(points, normals)
+        if int(samples) < 1:
+            raise ValueError("samples must be at least 1")
+        m = max(n, 1)
+        args = (n, int(samples), float("inf") if t_max is None else float(t_max), float(bias), int(seed), int(index_base),
+                int(bool(fast_traversal)))
+        if torch is None:
+            cnt, vis = np.zeros(m, dtype=np.uint32), np.zeros(m)
+            p, nrm = (a if n else np.zeros((1, 3)) for a in (p, nrm))
+            _ffi.check(self._L.rayrs_scene_ambient_occlusion(self._h, p.ctypes.data, nrm.ctypes.data, *args, cnt.ctypes.data,
+                                                             vis.ctypes.data), "rayrs_scene_ambient_occlusion")
+        else:
+            dev = p.device
+            cnt = torch.empty(m, dtype=torch.int32, device=dev).view(torch.uint32)
+            vis = torch.empty(m, dtype=torch.float64, device=dev)
+            p, nrm = (a if n else torch.zeros((1, 3), dtype=torch.float64, device=dev) for a in (p, nrm))
+            _ffi.check(self._L.rayrs_scene_ambient_occlusion_launch(self._h, p.data_ptr(), nrm.data_ptr(), *args, cnt.data_ptr(),
+                                                                    vis.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                       "rayrs_scene_ambient_occlusion_launch")
+        return (vis[:n], cnt[:n]) if counts else vis[:n]
+
+    def lab_ao_refill(self, refill_below: int = 0):
+        """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_ao_refill: for tests and scripts/ubench only; 0 = the default."""
+        _ffi.check(self._L.rayrs_lab_ao_refill(self._h, int(refill_below)), "rayrs_lab_ao_refill")
+
     def close(self):
         if self._h is not None:
             self._L.rayrs_scene_destroy(self._h)
@@ -579,6 +612,18 @@ def render_features(scene: Scene, camera: Camera, samples: int = 16, seed: int =
                                               out["albedo"].ctypes.data, out["depth"].ctypes.data, out["coverage"].ctypes.data,
                                               out["object"].ctypes.data), "rayrs_render_features")
     return out
+
+
+def render_ao(scene: Scene, camera: Camera, samples: int = 16, t_max=None, bias: float = 0.0, seed: int = 0x5EED,
+              ao_seed: int = 0xA0, fast_traversal: bool = False, counts: bool = False):
+    """The ambient-occlusion plane of the view (include/rayrs_hip.h AMBIENT OCCLUSION PLANE): (H, W) f64 visibility at the
+    first hit of every pixel's sample 0, exactly 1.0 where the primary ray misses; with counts also the (H, W) uint32 counts."""
+    H, W = camera.y_pixels(), camera.x_pixels()
+    vis, cnt = np.zeros((H, W)), np.zeros((H, W), dtype=np.uint32)
+    _ffi.check(scene._L.rayrs_render_ao(scene._h, C.byref(camera.desc), int(seed), int(ao_seed), int(samples),
+                                        float("inf") if t_max is None else float(t_max), float(bias), int(bool(fast_traversal)),
+                                        cnt.ctypes.data, vis.ctypes.data), "rayrs_render_ao")
+    return (vis, cnt) if counts else vis
 
 
 def _filter_inputs(color, planes, what, variance=False):

@@ -858,6 +858,32 @@ RR_DEV bool bvh_occluded(const SceneDev& sc, V3 o, V3 d, double t_max, const Lan
     return occluded_found(tv, t_max);
 }
 
+// ---- the same walk in pieces, for a wave whose lanes take new rays while others walk on (ao.hip ao_kernel): bvh_occluded's
+// three parts, each on a resumable Trav.  A lane is finished when tv.cur == TRAV_DONE; its verdict is occluded_found.
+// occluded_start is called by the WHOLE wave (the hot group's test votes across it) after the lanes with a new ray (`fresh`)
+// have run trav_init: only those owe the group its test, and only their state is touched.
+template <bool EXACT>
+RR_DEV void occluded_start(const SceneDev& sc, V3 o, V3 d, double t_max, bool fresh, Trav& tv) {
+    if (EXACT && sc.hot != nullptr) {
+        WorkCount wc{};
+        HotTally ht{};
+        hot_group_step<false>(sc, o, d, fresh && tv.cur != TRAV_DONE, tv, wc, ht);
+        if (fresh && occluded_found(tv, t_max)) tv.cur = TRAV_DONE;
+    }
+}
+template <bool COMPACT>
+RR_DEV void occluded_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack, Trav& tv) {
+    const HotNodes hot{nullptr, 0u};
+    WorkCount wc{};
+    trav_interior_step<COMPACT, false, true>(sc, o, stack, hot, tv, wc);
+}
+template <bool COMPACT>
+RR_DEV void occluded_leaf_step(const SceneDev& sc, V3 o, V3 d, double t_max, const LaneStack& stack, Trav& tv) {
+    WorkCount wc{};
+    trav_leaf_step<COMPACT, false>(sc, o, d, stack, tv, wc);
+    if (occluded_found(tv, t_max)) tv.cur = TRAV_DONE;
+}
+
 // ---------------------------------------------------------------- materials
 
 struct CtLayer {  // struct CookTorrance, material.rs:194-200

@@ -3,6 +3,12 @@
 //     rayrs hdri_path [spp] [--scene NAME] [--seed N] [--device N] [--max-bounces N] [--fast-traversal 0|1]
 //                           [--gpus N | --devices a,b,...] [--sample-chunk C] [--pass N] [--until-noise TAU]
 //                           [--denoise [LEVELS]] [--features] [--denoise-guided [LEVELS]] [--noise]
+//                           [--ao [S]] [--ao-radius R]
+//
+// --ao additionally writes <scene>_ao.png (no gamma) and <scene>_ao.hdr: the ambient-occlusion plane of include/rayrs_hip.h
+// (AMBIENT OCCLUSION PLANE) on three channels, S samples a pixel (default 16), ao_seed 0xA0, rays leaving the surface by a bias
+// of 1e-6 of the root box's diagonal and reaching --ao-radius R (default: anywhere).  <scene>.png and <scene>.hdr are the same
+// bytes with and without it.
 //
 // --denoise additionally writes <scene>_denoised.png and .hdr: the final frame (as f64) through the feature-guided a-trous
 // filter of include/rayrs_hip.h (DENOISER), LEVELS levels (default 5), with the normal, albedo and depth of 16 samples and
@@ -147,6 +153,11 @@ int main(int argc, char** argv) {
     uint32_t denoise_levels = 5;
     bool want_guided = false, want_noise = false;
     uint32_t guided_levels = 5;
+    bool want_ao = false;
+    uint32_t ao_samples = 16;
+    double ao_radius = INFINITY;
+    constexpr uint64_t AO_SEED = 0xA0;  // rayrs_amd/api.py render_ao's default
+    constexpr double AO_BIAS_FRACTION = 1e-6;
     uint32_t orbit_frames = 0;  // --orbit FRAMES DEGREES: frame i from the camera turned by i * DEGREES / FRAMES about its up through its lookat
     double orbit_degrees = 0.0;
     bool orbit_given = false, temporal = false;  // --temporal: every frame's film is pushed into one history
@@ -203,6 +214,14 @@ int main(int argc, char** argv) {
             else i--;
             continue;
         }
+        if (opt == "--ao") {  // the sample count is optional
+            want_ao = true;
+            char* end = nullptr;
+            const unsigned long v = i + 1 < argc ? std::strtoul(argv[i + 1], &end, 10) : 0ul;
+            if (i + 1 < argc && end != argv[i + 1] && *end == '\0') ao_samples = (uint32_t)v;
+            else i--;
+            continue;
+        }
         if (opt == "--denoise") {  // the level count is optional
             want_denoise = true;
             char* end = nullptr;
@@ -221,6 +240,7 @@ int main(int argc, char** argv) {
         else if (opt == "--sample-chunk") sample_chunk = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10), chunk_given = true;
         else if (opt == "--pass") pass = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10);
         else if (opt == "--until-noise") tau = std::strtod(argv[i + 1], nullptr), until_noise = true;
+        else if (opt == "--ao-radius") ao_radius = std::strtod(argv[i + 1], nullptr);
         else if (opt == "--gpus") {
             devices.clear();
             for (int d = 0; d < std::atoi(argv[i + 1]); d++) devices.push_back(d);
@@ -266,7 +286,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Usage: --orbit FRAMES DEGREES, FRAMES >= 1\n");
         return 2;
     }
-    if (orbit_given && (adaptive || until_noise || want_features || want_noise || want_denoise)) {
+    if (want_ao && ao_samples == 0) {
+        std::fprintf(stderr, "Usage: --ao [S], S >= 1\n");
+        return 2;
+    }
+    if (orbit_given && (adaptive || until_noise || want_features || want_noise || want_denoise || want_ao)) {
         std::fprintf(stderr, "Usage: --orbit writes each frame, with --temporal the history and with --denoise-guided the filtered one; it takes no other extra\n");
         return 2;
     }
@@ -333,7 +357,7 @@ int main(int argc, char** argv) {
     // --denoise filters the f64 frame: a plain render is then asked for f64 and converted here, which is the conversion
     // the f32 output format makes at its store -- the same <scene>.png and <scene>.hdr
     std::vector<double> rgb64(want_denoise && !use_film ? npix * 3 : 0);
-    std::vector<float> extra(want_denoise || want_features || want_guided || want_noise || temporal ? npix * 3 : 0);
+    std::vector<float> extra(want_denoise || want_features || want_guided || want_noise || temporal || want_ao ? npix * 3 : 0);
     auto write_extra = [&](const char* suffix, double gamma, bool png) -> int {
         const std::string name = scene_name + suffix + (png ? ".png" : ".hdr");
         if (!png) return rayrs_hdr_save(name.c_str(), extra.data(), cam.x_pixels, cam.y_pixels);
@@ -342,6 +366,7 @@ int main(int argc, char** argv) {
         return rayrs_png_save(name.c_str(), bytes.data(), cam.x_pixels, cam.y_pixels);
     };
     double kn = 1.0 / (SIGMA_NORMAL * SIGMA_NORMAL), ka = 1.0 / (SIGMA_ALBEDO * SIGMA_ALBEDO), kc = 1.0 / (SIGMA_COLOR * SIGMA_COLOR), kz = 0.0;
+    double ao_bias = 0.0;
     {
         rayrs_scene_info_t info;
         if ((st = rayrs_scene_info(scene, &info)) != RAYRS_OK) return fail("scene info", st);
@@ -351,6 +376,7 @@ int main(int argc, char** argv) {
         if (std::isfinite(diag) && diag > 0.0) {
             const double sigma = SIGMA_DEPTH_FRACTION * diag;
             kz = 1.0 / (sigma * sigma);
+            ao_bias = AO_BIAS_FRACTION * diag;
         }
     }
     // the feature files, from the planes of FEATURE_SAMPLES samples
@@ -553,6 +579,14 @@ int main(int argc, char** argv) {
             for (size_t k = 0; k < npix * 3; k++) extra[k] = (float)out64[k];
             if (write_denoised() != RAYRS_OK) return 1;
         }
+    }
+    if (want_ao) {
+        std::vector<double> vis(npix);
+        if ((st = rayrs_render_ao(scene, &cam, seed, AO_SEED, ao_samples, ao_radius, ao_bias, fast_traversal, nullptr, vis.data())) != RAYRS_OK)
+            return fail("ao", st);
+        for (size_t k = 0; k < npix; k++) extra[3 * k] = extra[3 * k + 1] = extra[3 * k + 2] = (float)vis[k];
+        if ((st = write_extra("_ao", 1.0, true)) != RAYRS_OK) return fail("ao png", st);
+        if ((st = write_extra("_ao", 1.0, false)) != RAYRS_OK) return fail("ao hdr", st);
     }
     for (rayrs_scene* sc : scenes) rayrs_scene_destroy(sc);
     return 0;

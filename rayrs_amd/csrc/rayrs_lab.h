@@ -69,6 +69,19 @@ int rayrs_lab_multi_rehearse(const int* rank_devices, uint32_t n, uint32_t round
 int rayrs_lab_query_steps(rayrs_scene* scene, const double* origin, const double* direction, const double* t_max, uint64_t n,
                           uint32_t fast_traversal, uint8_t* occluded, uint32_t* steps);
 
+/* Ambient occlusion (include/rayrs_hip.h AMBIENT OCCLUSION): a wave of ao.hip's kernel hands its idle lanes new (point, sample)
+ * items when fewer than refill_below lanes are walking, 1..64; 64 = whenever a lane is idle, 1 = only when none walks (no refill
+ * within a batch of 64).  0 restores the default.  The counts are the same for every setting.  Applies to the calls on this
+ * scene afterwards; RAYRS_INVALID_ARG above 64. */
+int rayrs_lab_ao_refill(rayrs_scene* scene, uint32_t refill_below);
+
+/* rayrs_scene_ambient_occlusion on host buffers through an instance of its kernel that also counts (never a timed one): turns[0]
+ * = 64 x the step turns the waves took, turns[1] = the lane-turns of them in which a lane advanced its walk -- their quotient is
+ * the share of lane-turns spent walking (scripts/ubench/ao_bench.py).  Refusals as rayrs_scene_ambient_occlusion's; count and
+ * turns are required. */
+int rayrs_lab_ao_turns(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples, double t_max,
+                       double bias, uint64_t seed, uint64_t index_base, uint32_t fast_traversal, uint32_t* count, uint64_t turns[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,14 @@ struct rayrs_scene {
         rayrs::DevBuf d_origin, d_direction, d_t_max, d_t, d_object, d_normal, d_occluded;  // the host forms' staging
     };
     Queries queries;
+    // What ambient occlusion (ao_abi.cpp) keeps between calls: the host forms' staging, which is also where the image form's
+    // first pass leaves its points; the traversal stacks' overflow is the queries' strip.
+    struct Ao {
+        rayrs::DevBuf d_position, d_normal, d_active, d_count, d_visibility;
+        rayrs::DevBuf d_turns;       // the lab's two turn counters (rayrs_lab_ao_turns)
+        uint32_t refill_below = 0;   // rayrs_lab_ao_refill; 0 = the default (ao_kernels.h AO_REFILL_BELOW)
+    };
+    Ao ao;
     // Scenes whose walk tree is at most one record are rendered by local_pool.hip: every path resident in LDS.
     bool local_ok = false;
     rayrs::LocalScene local = {};
