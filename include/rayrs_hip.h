@@ -816,6 +816,60 @@ int rayrs_scene_ambient_occlusion_launch(rayrs_scene* scene, const double* posit
 int rayrs_render_ao(rayrs_scene* scene, const rayrs_camera* camera, uint64_t seed, uint64_t ao_seed, uint32_t samples, double t_max,
                     double bias, uint32_t fast_traversal, uint32_t* count /* may be NULL */, double* visibility /* may be NULL */);
 
+/* ---- radiance queries: the light the render computes, along rays of the caller's and at points of the caller's -- an
+ * environment probe, a camera model of the caller's own, irradiance at lightmap texels or probe positions -- in batches, on the
+ * host or on device-resident buffers on a stream.  Nothing here touches a path kernel, a film or a render's buffers: the
+ * kernels are a unit of their own (radiance.hip).
+ *
+ * RADIANCE QUERY, specified to the operation.  A ray is (o, d), three f64 each, USED AS GIVEN, as in RAY QUERIES.  samples =
+ * S >= 1, max_bounces, sample_chunk = c: u32; seed, index_base: u64.  For ray i of the call and sample s in 0 .. S-1:
+ *     key      = rr_path_key(seed, index_base + i, s);  rng = (key, draw 0)   (rayrs_numeric.h)
+ *     L_{i,s}  = radiance(scene, Ray{o_i, d_i}, max_bounces)                  (lib.rs:521-560)
+ * with the draws taken in program order from rng, and the loop's query the render's: Bvh::intersect with the scene's z_near,
+ * z_far.  fast_traversal means what it means for rayrs_scene_intersect, and is taken AS ASKED: there is no camera for the
+ * camera rule to look at.  Then, with c' = S if c == 0 or c >= S, else c, and chunk k = the samples k*c' .. min((k+1)*c', S) - 1:
+ *     C_k        = Vec3::zeros(); C_k += L_{i,s} in sample order               (main.rs:67-69)
+ *     sum_i      = C_0 assigned, then += C_k in chunk order                    (rayrs_render_params.sample_chunk's rule)
+ *     radiance_i = sum_i * (1.0 / (double)S)                                   (main.rs:89; Div<f64> multiplies by the reciprocal)
+ *     queries_i  = the number of Bvh::intersect calls of the ray's S paths (u32)
+ * every operation f64 and unfused; radiance is 3 f64 per ray.  Either output buffer may be NULL = not wanted, but not both.
+ * index_base makes a call on rays[a:b] with index_base = a return the slice of the whole call's answer.  max_bounces == 0 is
+ * legal: the loop runs no turn, radiance is +0 and queries is 0.  No f64 sum depends on how the kernel schedules its lanes: a
+ * chunk's sum is made in one lane in sample order, the rest by a resolve in chunk order.
+ *
+ * IRRADIANCE.  A point is (p, n), three f64 each, USED AS GIVEN, as in AMBIENT OCCLUSION; bias: one f64 for the call.  For point
+ * i and sample s: key as above; draws 0 and 1 make l exactly as AMBIENT OCCLUSION does; o = p_i + n_i * bias; and
+ *     L_{i,s} = radiance(scene, Ray{o, l}, max_bounces)    with the path's rng continuing at draw 2
+ * which is what Material::evaluate of a Lambertian surface at (p, n) followed by the loop does with one rng.  The sums and the
+ * outputs are the RADIANCE QUERY's.  The value is the cosine-weighted mean of the incoming radiance, E / pi: for the irradiance
+ * E multiply by pi; a Lambertian texel of albedo rho radiates rho times the value.
+ *
+ * rayrs_scene_radiance and rayrs_scene_irradiance take HOST buffers and are synchronous.  The _launch forms take DEVICE
+ * pointers on the scene's device and a hipStream_t (NULL = the default stream), enqueue and return without a host wait; after the
+ * first call of a given walk a _launch call allocates nothing.  An item is (ray, chunk); a batch goes through launches of whole
+ * rays, at most 2^20 items each, which share RAY QUERIES' stack strip and its ordering rule (and a scratch of the scene's under
+ * the same rule).
+ *
+ * Refusals, all decided before the device is touched, in RAY QUERIES' order: RAYRS_INVALID_ARG for a NULL scene, a NULL
+ * origin / direction (position / normal), both outputs NULL, samples == 0 or fast_traversal > 1 -- with n == 0 too; then
+ * RAYRS_UNSUPPORTED for samples or max_bounces beyond the limits rayrs_render_params puts on spp and max_bounces (2^30 - 1;
+ * 8000), for (uint64)samples * max_bounces >= 2^32 (queries_i could wrap), and for more than 2^20 chunks per ray (a launch
+ * takes whole rays); then RAYRS_NO_DEVICE for a host-only scene.  n == 0 on a device scene is RAYRS_OK and launches nothing. */
+int rayrs_scene_radiance(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                         uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base, uint32_t fast_traversal,
+                         double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */);
+int rayrs_scene_radiance_launch(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                                uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base,
+                                uint32_t fast_traversal, double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */,
+                                void* hip_stream);
+int rayrs_scene_irradiance(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                           uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                           uint32_t fast_traversal, double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */);
+int rayrs_scene_irradiance_launch(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                  uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                                  uint32_t fast_traversal, double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */,
+                                  void* hip_stream);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -825,7 +879,8 @@ int rayrs_render_ao(rayrs_scene* scene, const rayrs_camera* camera, uint64_t see
  * rayrs_image_denoise, for the same reason, and with rayrs_film_noise, rayrs_film_denoise_guided and
  * rayrs_image_denoise_guided, and with rayrs_history_* and rayrs_camera_orbit (TEMPORAL ACCUMULATION), and with
  * rayrs_scene_intersect, rayrs_scene_occluded and their _launch forms (RAY QUERIES), and with
- * rayrs_scene_ambient_occlusion, its _launch form and rayrs_render_ao (AMBIENT OCCLUSION).  The layout table below begins with this
+ * rayrs_scene_ambient_occlusion, its _launch form and rayrs_render_ao (AMBIENT OCCLUSION), and with rayrs_scene_radiance,
+ * rayrs_scene_irradiance and their _launch forms (RADIANCE QUERY, IRRADIANCE).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

@@ -31,6 +31,7 @@ SYMBOLS = [
     "rayrs_history_push_times", "rayrs_history_read", "rayrs_history_denoise_guided", "rayrs_camera_orbit",
     "rayrs_scene_intersect", "rayrs_scene_occluded", "rayrs_scene_intersect_launch", "rayrs_scene_occluded_launch",
     "rayrs_scene_ambient_occlusion", "rayrs_scene_ambient_occlusion_launch", "rayrs_render_ao",
+    "rayrs_scene_radiance", "rayrs_scene_radiance_launch", "rayrs_scene_irradiance", "rayrs_scene_irradiance_launch",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -40,7 +41,7 @@ SYMBOLS = [
 # rayrs_amd/csrc/rayrs_selftest.h and rayrs_lab.h: private hooks of the library (tests/ and scripts/ only)
 PRIVATE_SYMBOLS = ["rayrs_test_math", "rayrs_test_rng", "rayrs_test_intersect", "rayrs_test_trace", "rayrs_test_path_trace", "rayrs_test_material", "rayrs_test_background",
                    "rayrs_lab_set", "rayrs_lab_round_ms", "rayrs_lab_multi_rehearse", "rayrs_lab_query_steps",
-                   "rayrs_lab_ao_refill", "rayrs_lab_ao_turns"]
+                   "rayrs_lab_ao_refill", "rayrs_lab_ao_turns", "rayrs_lab_radiance_tuning", "rayrs_lab_radiance_turns"]
 
 
 class MaterialDesc(C.Structure):
@@ -238,7 +239,15 @@ def lib():
                        ("rayrs_scene_ambient_occlusion_launch", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_double, C.c_double,
                                                                  C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp]),
                        ("rayrs_render_ao", [vp, C.POINTER(CameraDesc), C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_double,
-                                            C.c_uint32, vp, vp])):
+                                            C.c_uint32, vp, vp]),
+                       ("rayrs_scene_radiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                 C.c_uint32, vp, vp]),
+                       ("rayrs_scene_radiance_launch", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                        C.c_uint64, C.c_uint32, vp, vp, vp]),
+                       ("rayrs_scene_irradiance", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64,
+                                                   C.c_uint64, C.c_uint32, vp, vp]),
+                       ("rayrs_scene_irradiance_launch", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
+                                                          C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):
@@ -249,6 +258,10 @@ def lib():
         L.rayrs_lab_ao_refill.argtypes = [vp, C.c_uint32]
         L.rayrs_lab_ao_turns.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_uint64,
                                          C.c_uint32, vp, vp]
+    if hasattr(L, "rayrs_lab_radiance_tuning"):
+        L.rayrs_lab_radiance_tuning.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.rayrs_lab_radiance_turns.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
+                                               C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]
     L.rayrs_test_math.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
     L.rayrs_test_rng.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
     L.rayrs_test_intersect.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp]

@@ -481,6 +481,51 @@ class Scene:
         """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_ao_refill: for tests and scripts/ubench only; 0 = the default."""
         _ffi.check(self._L.rayrs_lab_ao_refill(self._h, int(refill_below)), "rayrs_lab_ao_refill")
 
+    # ---- radiance queries (include/rayrs_hip.h RADIANCE QUERY, IRRADIANCE)
+
+    def _radiance(self, name, a, b, samples, max_bounces, sample_chunk, bias, seed, index_base, fast_traversal, queries):
+        torch, a, b, _, n = self._query_inputs(a, b)
+        if int(samples) < 1:
+            raise ValueError("samples must be at least 1")
+        m = max(n, 1)
+        args = (n, int(samples), int(max_bounces), int(sample_chunk)) + (() if bias is None else (float(bias),)) + \
+               (int(seed), int(index_base), int(bool(fast_traversal)))
+        if torch is None:
+            rad, cnt = np.zeros((m, 3)), np.zeros(m, dtype=np.uint32)
+            a, b = (x if n else np.zeros((1, 3)) for x in (a, b))
+            _ffi.check(getattr(self._L, name)(self._h, a.ctypes.data, b.ctypes.data, *args, rad.ctypes.data, cnt.ctypes.data), name)
+        else:
+            dev = a.device
+            rad = torch.empty((m, 3), dtype=torch.float64, device=dev)
+            cnt = torch.empty(m, dtype=torch.int32, device=dev).view(torch.uint32)
+            a, b = (x if n else torch.zeros((1, 3), dtype=torch.float64, device=dev) for x in (a, b))
+            _ffi.check(getattr(self._L, name + "_launch")(self._h, a.data_ptr(), b.data_ptr(), *args, rad.data_ptr(), cnt.data_ptr(),
+                                                          torch.cuda.current_stream(dev).cuda_stream), name + "_launch")
+        return (rad[:n], cnt[:n]) if queries else rad[:n]
+
+    def radiance(self, origins, directions, samples: int = 1, max_bounces: int = 50, seed: int = 0x5EED, index_base: int = 0,
+                 sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False):
+        """The path-traced light arriving along every ray (origins[i], directions[i]), the mean of `samples` paths of the
+        render's radiance loop: radiance (n, 3) f64, and with queries also the number of closest-hit queries the ray's paths
+        made, (n,) uint32.  Rays are used as given.  Sample s of ray i draws from the key of (seed, index_base + i, s), so a
+        call on rays[a:b] with index_base=a returns the slice of the whole call's answer; sample_chunk is
+        rayrs_render_params.sample_chunk's rule for the order of the sum.  Inputs and where the answers live as intersect()."""
+        return self._radiance("rayrs_scene_radiance", origins, directions, samples, max_bounces, sample_chunk, None, seed, index_base,
+                              fast_traversal, queries)
+
+    def irradiance(self, points, normals, samples: int = 64, bias: float = 0.0, max_bounces: int = 50, seed: int = 0x5EED,
+                   index_base: int = 0, sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False):
+        """The cosine-weighted mean of the light arriving at points[i] around normals[i], E / pi, from `samples` paths that
+        leave points[i] + normals[i] * bias in ambient_occlusion()'s directions: (n, 3) f64 (multiply by pi for the
+        irradiance; a Lambertian texel of albedo rho radiates rho times the value).  Points and normals are used as given.
+        The other arguments, inputs and answers as radiance()."""
+        return self._radiance("rayrs_scene_irradiance", points, normals, samples, max_bounces, sample_chunk, bias, seed, index_base,
+                              fast_traversal, queries)
+
+    def lab_radiance_tuning(self, refill_below: int = 0, shade_at: int = 0, leaf_min: int = 0):
+        """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_radiance_tuning: for tests and scripts/ubench only; 0 = the default."""
+        _ffi.check(self._L.rayrs_lab_radiance_tuning(self._h, int(refill_below), int(shade_at), int(leaf_min)), "rayrs_lab_radiance_tuning")
+
     def close(self):
         if self._h is not None:
             self._L.rayrs_scene_destroy(self._h)

@@ -884,6 +884,32 @@ RR_DEV void occluded_leaf_step(const SceneDev& sc, V3 o, V3 d, double t_max, con
     if (occluded_found(tv, t_max)) tv.cur = TRAV_DONE;
 }
 
+// ---- the closest-hit walk in pieces, for a wave whose lanes shade, take new rays or walk on side by side (radiance.hip
+// radiance_kernel): bvh_intersect's three parts, each on a resumable Trav, for both walks -- EXACT: nothing culled, the hot
+// group first; else the fast walk with its two bets.  A lane is finished when tv.cur == TRAV_DONE; its answer is tv.best_prim
+// (0xffffffff: a miss) at tv.best_t.  A lane's walk visits what bvh_intersect visits for its ray, in the same order: what
+// the other lanes of the wave do in between does not enter it.  closest_start is called by the WHOLE wave, as
+// occluded_start is, after the lanes with a new ray (`fresh`) have run trav_init.
+template <bool EXACT>
+RR_DEV void closest_start(const SceneDev& sc, V3 o, V3 d, bool fresh, Trav& tv) {
+    if (EXACT && sc.hot != nullptr) {
+        WorkCount wc{};
+        HotTally ht{};
+        hot_group_step<false>(sc, o, d, fresh && tv.cur != TRAV_DONE, tv, wc, ht);
+    }
+}
+template <bool COMPACT, bool EXACT>
+RR_DEV void closest_interior_step(const SceneDev& sc, V3 o, const LaneStack& stack, Trav& tv) {
+    const HotNodes hot{nullptr, 0u};
+    WorkCount wc{};
+    trav_interior_step<COMPACT, false, EXACT>(sc, o, stack, hot, tv, wc);
+}
+template <bool COMPACT>
+RR_DEV void closest_leaf_step(const SceneDev& sc, V3 o, V3 d, const LaneStack& stack, Trav& tv) {
+    WorkCount wc{};
+    trav_leaf_step<COMPACT, false>(sc, o, d, stack, tv, wc);
+}
+
 // ---------------------------------------------------------------- materials
 
 struct CtLayer {  // struct CookTorrance, material.rs:194-200

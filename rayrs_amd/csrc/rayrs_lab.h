@@ -82,6 +82,23 @@ int rayrs_lab_ao_refill(rayrs_scene* scene, uint32_t refill_below);
 int rayrs_lab_ao_turns(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples, double t_max,
                        double bias, uint64_t seed, uint64_t index_base, uint32_t fast_traversal, uint32_t* count, uint64_t turns[2]);
 
+/* Radiance queries (include/rayrs_hip.h RADIANCE QUERY, IRRADIANCE): the thresholds of a wave of radiance.hip's kernel, 1..64
+ * each.  refill_below: idle lanes take new (ray, chunk) items when fewer than this many lanes are walking (64 = whenever a lane is
+ * idle, 1 = only when none walks).  shade_at: finished lanes are shaded once there are this many (1 = at once, 64 = only when no
+ * lane walks; they always are when none walks).  leaf_min: a leaf phase runs once this many lanes stand on a leaf group.  0
+ * restores a default (1, 64, 1: radiance_kernels.h, chosen by scripts/ubench/radiance_bench.py's sweep, profiles/radiance_rates.txt).
+ * Every answer is the same bits under every setting: a chunk's sum is made in one lane in sample order, the rest by the resolve
+ * in chunk order.  Applies to the calls on this scene afterwards; RAYRS_INVALID_ARG above 64. */
+int rayrs_lab_radiance_tuning(rayrs_scene* scene, uint32_t refill_below, uint32_t shade_at, uint32_t leaf_min);
+
+/* rayrs_scene_radiance (irradiance = 0: a = origins, b = directions; bias unused) or rayrs_scene_irradiance (irradiance = 1: a =
+ * points, b = normals) on host buffers through an instance of the kernel that also counts (never a timed one): turns[0] = 64 x the
+ * turns the waves took, turns[1] = the lane-turns in which a lane advanced its walk, turns[2] = those in which a lane was
+ * shaded (scripts/ubench/radiance_bench.py).  Refusals as the entry points'; queries and turns are required. */
+int rayrs_lab_radiance_turns(rayrs_scene* scene, uint32_t irradiance, const double* a, const double* b, uint64_t n, uint32_t samples,
+                             uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                             uint32_t fast_traversal, uint32_t* queries, uint64_t turns[3]);
+
 #ifdef __cplusplus
 }
 #endif

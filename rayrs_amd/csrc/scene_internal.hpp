@@ -112,6 +112,16 @@ struct rayrs_scene {
         uint32_t refill_below = 0;   // rayrs_lab_ao_refill; 0 = the default (ao_kernels.h AO_REFILL_BELOW)
     };
     Ao ao;
+    // What the radiance queries (radiance_abi.cpp) keep between calls: a launch's scratch (radiance_kernels.h
+    // RADIANCE_SCRATCH_BYTES: the item cursor, the items' sums and query counts), ordered between streams with the queries'
+    // strip and by its event; the host forms' staging; the lab's knobs.
+    struct Radiance {
+        rayrs::DevBuf d_scratch;
+        rayrs::DevBuf d_a, d_b, d_radiance, d_queries;
+        rayrs::DevBuf d_turns;       // the lab's three turn counters (rayrs_lab_radiance_turns)
+        uint32_t refill_below = 0, shade_at = 0, leaf_min = 0;  // rayrs_lab_radiance_tuning; 0 = the default (radiance_kernels.h)
+    };
+    Radiance radiance;
     // Scenes whose walk tree is at most one record are rendered by local_pool.hip: every path resident in LDS.
     bool local_ok = false;
     rayrs::LocalScene local = {};
