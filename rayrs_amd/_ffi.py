@@ -40,7 +40,7 @@ SYMBOLS = [
 
 # rayrs_amd/csrc/rayrs_selftest.h and rayrs_lab.h: private hooks of the library (tests/ and scripts/ only)
 PRIVATE_SYMBOLS = ["rayrs_test_math", "rayrs_test_rng", "rayrs_test_intersect", "rayrs_test_trace", "rayrs_test_path_trace", "rayrs_test_material", "rayrs_test_background",
-                   "rayrs_lab_set", "rayrs_lab_round_ms", "rayrs_lab_multi_rehearse", "rayrs_lab_query_steps",
+                   "rayrs_lab_set", "rayrs_lab_stack_need", "rayrs_lab_round_ms", "rayrs_lab_multi_rehearse", "rayrs_lab_query_steps",
                    "rayrs_lab_ao_refill", "rayrs_lab_ao_turns", "rayrs_lab_radiance_tuning", "rayrs_lab_radiance_turns"]
 
 
@@ -182,6 +182,8 @@ def lib():
     L.rayrs_scene_set_tuning.argtypes = [vp, C.POINTER(Tuning)]
     L.rayrs_lab_set.argtypes = [vp, C.POINTER(LabTuning)]  # private: rayrs_amd/csrc/rayrs_lab.h
     L.rayrs_lab_set.restype = C.c_int
+    if hasattr(L, "rayrs_lab_stack_need"):  # (an older build behind RAYRS_HIP_LIB has none)
+        L.rayrs_lab_stack_need.argtypes = [vp, C.c_uint32]
     L.rayrs_lab_multi_rehearse.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_uint32]
     L.rayrs_lab_multi_rehearse.restype = C.c_int
     L.rayrs_frame_sample_chunk.argtypes = [C.c_uint32] * 4

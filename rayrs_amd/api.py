@@ -327,6 +327,14 @@ class Scene:
             setattr(t, k, int(v))
         _ffi.check(self._L.rayrs_lab_set(self._h, C.byref(t)), "rayrs_lab_set")
 
+    def lab_stack_need(self, which: int) -> int:
+        """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_stack_need: the entries of a lane's stack on tree 0 (fast walk), 1 (gate), 2 (gate
+        without the hot group); for tests only."""
+        n = self._L.rayrs_lab_stack_need(self._h, int(which))
+        if n < 0:
+            _ffi.check(n, "rayrs_lab_stack_need")
+        return int(n)
+
     def info(self) -> dict:
         i = _ffi.SceneInfo()
         _ffi.check(self._L.rayrs_scene_info(self._h, C.byref(i)), "rayrs_scene_info")

@@ -189,11 +189,11 @@ int rayrs_scene_new(const rayrs_objects* objs, double z_near, double z_far, int 
     *out = nullptr;
     std::unique_ptr<rayrs_scene> s(new rayrs_scene());
     RAYRS_TRY(build_flat_scene(objs->list, z_near, z_far, heuristic, splits, hdri_w, hdri_h, hdri_rgb, &s->flat));
-    // Every traversal lane gets a stack of WalkTree::depth entries (12 in LDS, the rest in HBM: 1.3 MB per entry on a
+    // Every traversal lane gets a stack of WalkTree::stack_need entries (12 in LDS, the rest in HBM: 1.3 MB per entry on a
     // 256-CU device).  The reference recurses as deep as its tree; a tree that needs more than 4096 pending
     // entries (a chain of thousands of nested objects) is refused instead of allocating gigabytes for it.
-    if (std::max(s->flat.walk.depth, s->flat.gate.depth) > 4096u) {
-        g_last_error = "walk tree needs " + std::to_string(std::max(s->flat.walk.depth, s->flat.gate.depth)) + " stack entries (limit 4096)";
+    if (std::max(s->flat.walk.stack_need, s->flat.gate.stack_need) > 4096u) {
+        g_last_error = "walk tree needs " + std::to_string(std::max(s->flat.walk.stack_need, s->flat.gate.stack_need)) + " stack entries (limit 4096)";
         return RAYRS_UNSUPPORTED;
     }
     s->surfaces = objs->list.surfaces;
@@ -325,6 +325,11 @@ int rayrs_lab_set(rayrs_scene* scene, const rayrs_lab_tuning* lab) {
     scene->lab = *lab;
     if (scene->device >= 0) return scene_configure_traversal(scene);
     return RAYRS_OK;
+}
+
+int rayrs_lab_stack_need(rayrs_scene* scene, uint32_t which) {
+    if (!scene || which > 2u || (which == 2u && !scene->flat.has_hot)) return RAYRS_INVALID_ARG;
+    return (int)scene->stack_depth((int)which);
 }
 
 uint32_t rayrs_frame_sample_chunk(uint32_t x_pixels, uint32_t y_pixels, uint32_t spp, uint32_t requested) {

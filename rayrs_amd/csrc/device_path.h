@@ -399,7 +399,9 @@ struct RecordTest {
 };
 
 // The record test of both walks: the record tv.cur, fetched from its LDS copy or from HBM, and its four boxes tested.
-// Unused slots need no special case: they carry the inverted box (scene_host.cpp), for which the slab test says "missed".
+// Unused slots need no special case: they carry the inverted box (scene_host.cpp), for which the slab test says "missed" --
+// to every ray but one all of whose slabs are NaN, which enters every box of the tree and is then tested of primitive 0 once
+// more (REF_UNUSED reads as that one-primitive group); the trees' stack need covers that walk (scene_host.cpp emit_wide).
 template <bool COMPACT, bool COUNT>
 RR_DEV RecordTest trav_record_test(const SceneDev& sc, V3 o, const HotNodes& hot, const Trav& tv, WorkCount& wc) {
     const double tmin = sc.t0, tmax = sc.t1;

@@ -44,7 +44,7 @@ RR_LAYOUT_FN constexpr uint32_t record_ref(uint32_t rec) { return (REF_INTERIOR 
 RR_LAYOUT_FN constexpr uint32_t group_ref(uint32_t first, uint32_t count, uint32_t kind = REF_RANGE) {
     return (kind << 30) | (first << 2) | (count - 1u);
 }
-constexpr uint32_t REF_UNUSED = REF_NONE << 30;    // what an unused slot carries
+constexpr uint32_t REF_UNUSED = REF_NONE << 30;    // what an unused slot carries; to a walk it reads as the group of primitive 0 alone
 constexpr uint32_t REF_LEAF_BASE = REF_RANGE << 30;  // a reference a ray can enter (never REF_NONE: the inverted box) at or above this is a leaf group
 
 // primitive tag: kind | axis << 2 | surface << 8

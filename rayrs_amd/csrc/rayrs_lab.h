@@ -49,6 +49,12 @@ typedef struct {
 /* Applies to the renders launched on this scene afterwards.  Waits for a render in flight. */
 int rayrs_lab_set(rayrs_scene* scene, const rayrs_lab_tuning* lab);
 
+/* The entries of a lane's traversal stack on the scene's tree `which` (0: the fast walk's, 1: the gate tree, 2: the gate tree
+ * without the hot group), what the overflow strips are sized by: rayrs_scene_info_t's depth of that tree, or what the walk of a
+ * ray that enters every slot of every record -- an all-NaN ray -- needs if that is more (scene_host.cpp emit_wide).  Needs no
+ * device.  Negative: rayrs_status (no scene, no such tree). */
+int rayrs_lab_stack_need(rayrs_scene* scene, uint32_t which);
+
 /* HIP-event times (ms) of the last finished render's path rounds, three per round: traversal, hit, miss kernel (the
  * local-pool route: its launch, 0, 0).  Returns the number of rounds (negative: rayrs_status); writes min(rounds,
  * cap_rounds) * 3 floats. */

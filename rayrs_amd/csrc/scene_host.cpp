@@ -570,8 +570,18 @@ struct WideCollapse {
 };
 
 // One record per call: the slots the collapse gives node n's two subtrees.  Returns the record's reference;
-// *stack_need is the number of stack entries a traversal below it can have pending.
-uint32_t emit_wide(WalkTree& f, const WideCollapse& wc, int32_t n, uint32_t* stack_need) {
+// *stack_need and *every_need are the numbers of stack entries two kinds of traversal below it can have pending; a lane's
+// stack holds the larger (WalkTree::stack_need).
+//   A ray visits the slots it enters in any order (nearest first): the other used slots wait, ns - 1 of them, above
+// whatever the deepest subtree needs (*stack_need: WalkTree::depth).
+//   A ray all of whose slabs are NaN -- a NaN direction or origin, an infinite direction on every axis: any f64 is a legal
+// ray component -- enters every box, because the slab test ignores a NaN slab (f64::max / f64::min), and so it enters the
+// inverted box of an UNUSED slot as well.  Every entry parameter is then t0, so it walks in slot order with all four slots
+// of every record entered: 3 - i entries wait while it is below slot i (*every_need).  An unused slot's reference
+// reads as the one-primitive group at primitive 0, which such a ray is tested of anyway (it enters every gating box),
+// and the accept rule takes the same hit twice to no effect.  On a record with fewer than four used slots this walk
+// needs more entries than the first; a stack sized for the first alone was overrun by such a ray.
+uint32_t emit_wide(WalkTree& f, const WideCollapse& wc, int32_t n, uint32_t* stack_need, uint32_t* every_need) {
     const std::vector<WalkNode>& nodes = wc.nodes;
     const uint32_t rec = f.n();
     f.ref.resize(f.ref.size() + 4, REF_UNUSED);
@@ -581,18 +591,20 @@ uint32_t emit_wide(WalkTree& f, const WideCollapse& wc, int32_t n, uint32_t* sta
     const int k = wc.argk[(size_t)n * 4];
     wc.expand(nodes[n].left, k, slots, ns);
     wc.expand(nodes[n].right, 4 - k, slots, ns);
-    uint32_t below = 0;
+    uint32_t below = 0, every = 3;
     for (int i = 0; i < ns; i++) {
         const WalkNode& c = nodes[slots[i]];
         uint32_t ref = c.ref;
         if (c.left >= 0) {
-            uint32_t need = 0;
-            ref = emit_wide(f, wc, slots[i], &need);
+            uint32_t need = 0, need_every = 0;
+            ref = emit_wide(f, wc, slots[i], &need, &need_every);
             if (need > below) below = need;
+            if ((uint32_t)(3 - i) + need_every > every) every = (uint32_t)(3 - i) + need_every;
         }
         f.ref[(size_t)rec * 4 + i] = ref;
         for (int q = 0; q < 6; q++) f.box[((size_t)rec * 4 + i) * 6 + q] = c.box[q];
     }
+    *every_need = every;
     *stack_need = (uint32_t)(ns - 1) + below;
     return record_ref(rec);
 }
@@ -648,7 +660,9 @@ void build_tree_over(const std::vector<WalkGroup>& leaves, WalkTree& t) {
     t.box.reserve(leaves.size() * 12);
     t.ref.reserve(leaves.size() * 2);
     const WideCollapse wc(b.nodes);
-    t.root_ref = emit_wide(t, wc, 0, &t.depth);
+    uint32_t every_need = 0;
+    t.root_ref = emit_wide(t, wc, 0, &t.depth, &every_need);
+    t.stack_need = std::max(t.depth, every_need);
     front_largest(t);
 }
 

@@ -49,7 +49,8 @@ struct WalkTree {
     std::vector<double> box;    // n * 24
     std::vector<uint32_t> ref;  // n * 4
     uint32_t root_ref = 0;
-    uint32_t depth = 0;         // stack entries the traversal can need
+    uint32_t depth = 0;         // stack entries the traversal of a ray with a number in some slab can need
+    uint32_t stack_need = 0;    // entries of a lane's stack: depth, or what an all-NaN ray's walk needs if that is more (emit_wide)
     std::vector<uint8_t> node_bytes;  // the records as the kernels read them (Node4F32 / Node4F64)
     uint32_t n() const { return (uint32_t)(ref.size() / 4); }
 };

@@ -56,7 +56,7 @@ struct rayrs_scene {
     // [2] FlatScene::gate_hot (the default walk on a scene with a hot group: layout.h HotGroupDev).
     Walk trav[3];
     const rayrs::WalkTree& tree(int which) const { return which == 2 ? flat.gate_hot : which == 1 ? flat.gate : flat.walk; }
-    uint32_t stack_depth(int which) const { return tree(which).depth ? tree(which).depth : 1; }  // entries of a lane's stack
+    uint32_t stack_depth(int which) const { return tree(which).stack_need ? tree(which).stack_need : 1; }  // entries of a lane's stack
     rayrs::DevBuf d_hot;  // one HotGroupDev
     int walk_index(bool exact) const { return rayrs::walk_index(exact, flat.has_hot, lab); }  // which of the three a frame walks
     uint64_t device_bytes = 0;

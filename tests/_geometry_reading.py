@@ -520,7 +520,8 @@ def ties_rays(prims, seed, n):
 
 def extreme(prims, seed, n):
     """At the point, the segment and the tiny sphere of degenerate_objects(), around the scene, and with subnormal
-    coordinates: origins and direction components of 1e-310 and 5e-324."""
+    coordinates: origins and direction components of 1e-310 and 5e-324.  (A direction that comes out all zero is replaced:
+    zero, NaN, infinite and far-scaled rays are tests/_nonfinite_rays.py's.)"""
     r = np.random.default_rng(seed)
     o, d = _around(prims, r, n)
     q = n // 4

@@ -97,7 +97,7 @@ def test_rays_aimed_at_the_groups_primitives_return_the_recursions_hits():
         gd = r.uniform(lo, hi, (500, 3)) - g
         os_.append(g - 3.0 * gd), ds_.append(gd)
     o, d = np.concatenate(os_), np.concatenate(ds_)
-    d[(d == 0).all(axis=1)] = (0.0, -1.0, 0.0)
+    d[(d == 0).all(axis=1)] = (0.0, -1.0, 0.0)      # (a zero direction, NaN, infinities, 2^+-500: tests/_nonfinite_rays.py)
     rt, robj = osc.intersect_many(o, d, 1e-6, 1e6, traversal=0)
     t, obj = gpu_intersect(scene, o, d)
     hot_objs = {int(pp[info["hot_first"] + k]) for k in range(info["hot_count"])}
