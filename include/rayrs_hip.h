@@ -870,6 +870,99 @@ int rayrs_scene_irradiance_launch(rayrs_scene* scene, const double* position, co
                                   uint32_t fast_traversal, double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */,
                                   void* hip_stream);
 
+/* ---- radiance queries with light sampling: the queries above with the reference's Some(pdf) in place of None, and the same
+ * loop over a camera's pixels.  The reference designed the mix (Material::evaluate takes an Option<Pdf>, material.rs:91-97;
+ * LambertianDiffuse::scatter mixes it with its cosine lobe, :259-281; Plastic hands it to its diffuse arm, :588; the seven
+ * other scatters ignore it) and its radiance() passes None (lib.rs:532): here the caller names the lights.  The kernels are a
+ * unit of their own (radiance_lit.hip); nothing above changes, rayrs_render and the film know nothing of it.
+ *
+ * LIGHT SAMPLING, specified to the operation.  A LIGHT LIST is K <= RAYRS_MAX_LIGHTS object indices, in the numbering
+ * rayrs_scene_intersect returns as `object` (insertion order, a mesh one index per triangle).  Each index must name a sphere or
+ * a plane object; it need not emit (a portal is a legitimate target); duplicates are legal and mean what the density below
+ * says.  K = 0 is pdf = None: every lit entry point then returns, bit for bit and count for count, what its unlit counterpart
+ * returns.  With K >= 1, Material::evaluate of a LambertianDiffuse surface, and of Plastic's diffuse arm after Plastic's own
+ * Fresnel draw, at (position, normal) with the surface's colour `albedo` is, the draws taken from the path's rng in this order:
+ *     a = rng.next()
+ *     if a < 0.5:                                   (Pdf::Mix::generate, material.rs:1028-1034, MixKind::Constant(0.5))
+ *         b = rng.next();  k = min((uint32)(b * (double)K), K - 1)
+ *         u1 = rng.next();  u2 = rng.next()
+ *         q = light k's Hittable::sample:
+ *             plane  (geometry.rs:288-299): u = u1 * (umax - umin) + umin;  v = u2 * (vmax - vmin) + vmin;
+ *                    q = (pos, u, v) | (u, pos, v) | (u, v, pos) for an X | Y | Z axis
+ *             sphere (geometry.rs:142-152): phi = 2.0 * RR_PI * u2;  r = sqrt(u1 * (1.0 - u1));
+ *                    x = cos(phi) * 2.0 * r;  y = sin(phi) * 2.0 * r;  z = 1.0 - 2.0 * u1;
+ *                    q = (x, y, z) * sqrt(radius2) + origin
+ *         l = (q - position).unit()                 (material.rs:1027)
+ *     else:
+ *         l = Pdf::Cosine.generate                  (two draws: exactly the unlit Lambertian's direction, AMBIENT OCCLUSION's l)
+ *     ndl = normal . l
+ *     pdf = +inf if ndl < 0.0                       (material.rs:952-954)
+ *           else 0.5 * p_L + 0.5 * (ndl * RR_FRAC_1_PI),
+ *           p_L = (p_0 assigned, then += p_k in list order) / (double)K, one true division
+ *     color = ((albedo * RR_FRAC_1_PI) * ndl) / pdf     (material.rs:273-274; Div<f64> multiplies by the reciprocal)
+ *     Scatter { color, Ray(position, l) }
+ * The light arm takes four draws and the cosine arm three; the loop's roulette draw follows as it does without lights.  The
+ * other seven materials and Plastic's Cook-Torrance arm are unchanged, as in the reference.
+ *
+ * p_k(l) is the TRUE solid-angle density, at `position`, of the directions that light k's arm generates.  This is the one
+ * place where the operation deliberately leaves the reference (Pdf::Hittable's value, material.rs:943-950): the estimator is
+ * unbiased only if the density it divides by is the density it draws from, and the reference's is that in two cases out of
+ * many -- it divides by the SHADING normal's n . l where the area's projection is the LIGHT's |n_k . l|, and of a sphere it
+ * prices the near crossing only where uniform sampling of the sphere's area reaches its far side too.  With ray = Ray{position, l}:
+ *     plane:  Plane::intersect(ray) (geometry.rs:229-271); if it is Some(t) and t > 0.0:
+ *                 p_k = (position - ray.point(t)).mag2() / (|n_k . l| * area),  area = (umax - umin) * (vmax - vmin),
+ *                 n_k = Plane::normal (geometry.rs:273-282), the dot product written out in full (three products, two sums);
+ *             else p_k = 0.0
+ *     sphere: odiff, a, b, c, desc of Sphere::intersect (geometry.rs:107-113); p_k = 0.0; if desc > 0.0:
+ *                 t1 = (-b - sqrt(desc)) / (2.0 * a);  t2 = (-b + sqrt(desc)) / (2.0 * a)
+ *                 if t1 > 0.0: p_k = p_k + X(t1);  if t2 > 0.0: p_k = p_k + X(t2)
+ *                 X(t) = (position - ray.point(t)).mag2() / (|Sphere::normal(ray.point(t)) . l| * area),
+ *                 area = (4.0 * RR_PI) * radius2
+ * Everything is f64 and unfused; ray.point(t) = position + l * t; a zero or non-finite intermediate takes whatever IEEE gives
+ * (q == position, a grazing |n_k . l| = 0, a point inside a sphere light).  Where pdf = +inf the densities are not evaluated.
+ *
+ * RADIANCE, LIT (rayrs_scene_radiance_lit): RADIANCE QUERY with the operation above in place of evaluate(.., None).
+ * IRRADIANCE, LIT (rayrs_scene_irradiance_lit): with K >= 1 the sample's first direction comes from the same operation at
+ * position = p_i + n_i * bias, normal n_i, albedo (1, 1, 1), on the path's rng from draw 0; then
+ *     L_{i,s} = color * radiance(scene, Ray{position, l}, max_bounces)   componentwise, the path's rng continuing;
+ * the path is traced whatever color is.  With K = 0 it is IRRADIANCE, with no multiplication.
+ * IMAGE FORM (rayrs_render_lit): pixel (row, col) is ray i = row * W + col of an H * W batch; key = sample_key(seed, cam, row,
+ * col, s) (= rr_path_key(seed, i, s)), the primary ray is the render's sample_ray on draws 0 and 1, the loop goes on at draw 2,
+ * and the sums are RADIANCE QUERY's.  With K = 0 the frame is rayrs_render's with out_format = RAYRS_OUT_F64 and the same
+ * sample_chunk, bit for bit: rayrs_render sums by the same rule and does nothing beyond it to an f64 frame (its NaN and
+ * negative-pixel counters only count).  There are no tile shares.  fast_traversal is treated as rayrs_render_ao treats it: the
+ * walk is the one a render with these settings takes (the camera rule of rayrs_render_params.fast_traversal included), for the
+ * whole path; in the other four entry points it is taken as asked.
+ *
+ * `lights` is a HOST pointer in every form, the _launch forms included: the list is resolved on the host into a table of a
+ * kind and seven f64 per light and passed by value in the kernel arguments, so a _launch call still allocates nothing (after
+ * the first call of a given walk) and orders no copy.  Buffers, streams, launches and the stack strip are RADIANCE QUERY's.
+ *
+ * Refusals, all decided before the device is touched and with n == 0 too, in RADIANCE QUERY's order: to its RAYRS_INVALID_ARG
+ * group add lights == NULL with n_lights > 0 and an index >= the scene's object count (rayrs_render_lit: a NULL camera or
+ * out_rgb, and the cameras rayrs_render_features refuses as arguments); to its RAYRS_UNSUPPORTED group add n_lights >
+ * RAYRS_MAX_LIGHTS and an index that names a triangle (rayrs_render_lit: an image side above 65535); RAYRS_NO_DEVICE last. */
+#define RAYRS_MAX_LIGHTS 8
+int rayrs_scene_radiance_lit(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                             uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base, uint32_t fast_traversal,
+                             const uint32_t* lights, uint32_t n_lights, double* radiance /* may be NULL */,
+                             uint32_t* queries /* may be NULL */);
+int rayrs_scene_radiance_lit_launch(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                                    uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base,
+                                    uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                    double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_scene_irradiance_lit(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                               uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                               uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                               double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */);
+int rayrs_scene_irradiance_lit_launch(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                      uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                                      uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                      double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_render_lit(rayrs_scene* scene, const rayrs_camera* camera, uint64_t seed, uint32_t samples, uint32_t max_bounces,
+                     uint32_t sample_chunk, uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                     double* out_rgb /* H*W*3 */, uint32_t* queries /* H*W, may be NULL */);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -880,7 +973,8 @@ int rayrs_scene_irradiance_launch(rayrs_scene* scene, const double* position, co
  * rayrs_image_denoise_guided, and with rayrs_history_* and rayrs_camera_orbit (TEMPORAL ACCUMULATION), and with
  * rayrs_scene_intersect, rayrs_scene_occluded and their _launch forms (RAY QUERIES), and with
  * rayrs_scene_ambient_occlusion, its _launch form and rayrs_render_ao (AMBIENT OCCLUSION), and with rayrs_scene_radiance,
- * rayrs_scene_irradiance and their _launch forms (RADIANCE QUERY, IRRADIANCE).  The layout table below begins with this
+ * rayrs_scene_irradiance and their _launch forms (RADIANCE QUERY, IRRADIANCE), and with rayrs_scene_radiance_lit,
+ * rayrs_scene_irradiance_lit, their _launch forms and rayrs_render_lit (LIGHT SAMPLING).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

@@ -491,13 +491,17 @@ class Scene:
 
     # ---- radiance queries (include/rayrs_hip.h RADIANCE QUERY, IRRADIANCE)
 
-    def _radiance(self, name, a, b, samples, max_bounces, sample_chunk, bias, seed, index_base, fast_traversal, queries):
+    def _radiance(self, name, a, b, samples, max_bounces, sample_chunk, bias, seed, index_base, fast_traversal, queries, lights=None):
         torch, a, b, _, n = self._query_inputs(a, b)
         if int(samples) < 1:
             raise ValueError("samples must be at least 1")
         m = max(n, 1)
         args = (n, int(samples), int(max_bounces), int(sample_chunk)) + (() if bias is None else (float(bias),)) + \
                (int(seed), int(index_base), int(bool(fast_traversal)))
+        if lights is not None:  # (a host array in every form: include/rayrs_hip.h LIGHT SAMPLING)
+            lights = _light_list(lights)
+            name += "_lit"
+            args += (lights.ctypes.data if len(lights) else None, len(lights))
         if torch is None:
             rad, cnt = np.zeros((m, 3)), np.zeros(m, dtype=np.uint32)
             a, b = (x if n else np.zeros((1, 3)) for x in (a, b))
@@ -512,23 +516,26 @@ class Scene:
         return (rad[:n], cnt[:n]) if queries else rad[:n]
 
     def radiance(self, origins, directions, samples: int = 1, max_bounces: int = 50, seed: int = 0x5EED, index_base: int = 0,
-                 sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False):
+                 sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None):
         """The path-traced light arriving along every ray (origins[i], directions[i]), the mean of `samples` paths of the
         render's radiance loop: radiance (n, 3) f64, and with queries also the number of closest-hit queries the ray's paths
         made, (n,) uint32.  Rays are used as given.  Sample s of ray i draws from the key of (seed, index_base + i, s), so a
         call on rays[a:b] with index_base=a returns the slice of the whole call's answer; sample_chunk is
-        rayrs_render_params.sample_chunk's rule for the order of the sum.  Inputs and where the answers live as intersect()."""
+        rayrs_render_params.sample_chunk's rule for the order of the sum.  lights: None, or up to 8 object indices (emitters())
+        that diffuse surfaces sample half of the time (include/rayrs_hip.h LIGHT SAMPLING; an empty list computes what None
+        computes).  Inputs and where the answers live as intersect()."""
         return self._radiance("rayrs_scene_radiance", origins, directions, samples, max_bounces, sample_chunk, None, seed, index_base,
-                              fast_traversal, queries)
+                              fast_traversal, queries, lights)
 
     def irradiance(self, points, normals, samples: int = 64, bias: float = 0.0, max_bounces: int = 50, seed: int = 0x5EED,
-                   index_base: int = 0, sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False):
+                   index_base: int = 0, sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None):
         """The cosine-weighted mean of the light arriving at points[i] around normals[i], E / pi, from `samples` paths that
         leave points[i] + normals[i] * bias in ambient_occlusion()'s directions: (n, 3) f64 (multiply by pi for the
         irradiance; a Lambertian texel of albedo rho radiates rho times the value).  Points and normals are used as given.
-        The other arguments, inputs and answers as radiance()."""
+        With lights the first direction too is drawn from the mix of the lights and the cosine lobe, and the sample is weighted
+        for it: the same mean, with less noise under a small lamp.  The other arguments, inputs and answers as radiance()."""
         return self._radiance("rayrs_scene_irradiance", points, normals, samples, max_bounces, sample_chunk, bias, seed, index_base,
-                              fast_traversal, queries)
+                              fast_traversal, queries, lights)
 
     def lab_radiance_tuning(self, refill_below: int = 0, shade_at: int = 0, leaf_min: int = 0):
         """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_radiance_tuning: for tests and scripts/ubench only; 0 = the default."""
@@ -677,6 +684,42 @@ def render_ao(scene: Scene, camera: Camera, samples: int = 16, t_max=None, bias:
                                         float("inf") if t_max is None else float(t_max), float(bias), int(bool(fast_traversal)),
                                         cnt.ctypes.data, vis.ctypes.data), "rayrs_render_ao")
     return (vis, cnt) if counts else vis
+
+
+def _light_list(lights):
+    """A light list as the contiguous uint32 host array the library reads."""
+    lights = np.ascontiguousarray(lights, dtype=np.int64).reshape(-1)
+    if len(lights) and (lights.min() < 0 or lights.max() > 0xFFFFFFFF):
+        raise ValueError("a light is an object index, 0 .. 2^32 - 1")
+    return lights.astype(np.uint32)
+
+
+def emitters(objects) -> List[int]:
+    """The indices, in the scene's numbering (Scene.intersect's `object`: insertion order, a mesh one index per triangle), of
+    the emissive sphere and plane objects of an object list: what radiance(), irradiance() and render_lit() take as lights."""
+    out, index = [], 0
+    for o in flatten_objects(objects):
+        if o.kind == "mesh":
+            index += int(o.idx.shape[0])
+            continue
+        if o.kind in ("sphere", "plane") and o.emission.emissive:
+            out.append(index)
+        index += 1
+    return out
+
+
+def render_lit(scene: Scene, camera: Camera, samples: int, lights, max_bounces: int = 50, seed: int = 0x5EED, sample_chunk: int = 0,
+               fast_traversal: bool = False, queries: bool = False):
+    """The view's radiance with light sampling (include/rayrs_hip.h LIGHT SAMPLING, the image form): (H, W, 3) f64, the mean of
+    `samples` paths per pixel whose diffuse surfaces sample `lights` half of the time; with queries also the (H, W) uint32
+    closest-hit queries per pixel.  With an empty list the frame is render(..., out_f64=True)'s, bit for bit."""
+    H, W = camera.y_pixels(), camera.x_pixels()
+    lights = _light_list(lights)
+    out, cnt = np.zeros((H, W, 3)), np.zeros((H, W), dtype=np.uint32)
+    _ffi.check(scene._L.rayrs_render_lit(scene._h, C.byref(camera.desc), int(seed), int(samples), int(max_bounces), int(sample_chunk),
+                                         int(bool(fast_traversal)), lights.ctypes.data if len(lights) else None, len(lights),
+                                         out.ctypes.data, cnt.ctypes.data), "rayrs_render_lit")
+    return (out, cnt) if queries else out
 
 
 def _filter_inputs(color, planes, what, variance=False):

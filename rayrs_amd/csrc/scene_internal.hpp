@@ -122,6 +122,12 @@ struct rayrs_scene {
         uint32_t refill_below = 0, shade_at = 0, leaf_min = 0;  // rayrs_lab_radiance_tuning; 0 = the default (radiance_kernels.h)
     };
     Radiance radiance;
+    // What the lit radiance queries (radiance_lit_abi.cpp) keep beside the radiance queries' scratch and staging, which they
+    // share: the inverse of flat.prim_object (object in insertion order -> depth-first slot), made by the first call with lights.
+    struct Lit {
+        std::vector<uint32_t> object_prim;
+    };
+    Lit lit;
     // Scenes whose walk tree is at most one record are rendered by local_pool.hip: every path resident in LDS.
     bool local_ok = false;
     rayrs::LocalScene local = {};
