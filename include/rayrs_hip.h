@@ -963,6 +963,98 @@ int rayrs_render_lit(rayrs_scene* scene, const rayrs_camera* camera, uint64_t se
                      uint32_t sample_chunk, uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
                      double* out_rgb /* H*W*3 */, uint32_t* queries /* H*W, may be NULL */);
 
+/* ---- radiance queries with direct lighting: a third strategy beside the unlit queries and LIGHT SAMPLING, in the same three
+ * forms.  A diffuse bounce keeps the direction the surface itself samples and sends a second, cheap ray towards a sampled point
+ * of a light (next-event estimation); the two are weighted against each other by the balance heuristic (multiple importance
+ * sampling).  Where the lamps matter little the light sample adds little and everything else keeps weight 1; where a lamp
+ * dominates, every bounce finds it; and no quotient can be 0 / 0.  The kernels are a unit of their own (radiance_direct.hip);
+ * nothing above changes.
+ *
+ * DIRECT LIGHTING, specified to the operation.  The light list is LIGHT SAMPLING's: K <= RAYRS_MAX_LIGHTS object indices,
+ * spheres and planes, duplicates legal.  Everything is f64 and unfused; the draws are taken from the path's rng in program
+ * order; p_k, p_L = (p_0 assigned, then += p_k in list order) / (double)K, light k's Hittable::sample and the list's numbering
+ * are LIGHT SAMPLING's, unchanged.  "obj is in the list" is set membership: obj's index equals some entry's.
+ *
+ * State.  A path carries one extra scalar w, the weight of the emission of a LISTED object met by the current ray: w = 1.0 at a
+ * path's start, and w = 1.0 after every bounce that is not a diffuse bounce.
+ *
+ * One turn of radiance()'s loop at a hit obj (lib.rs:526-551), K >= 1:
+ *     ev = Material::evaluate(position, normal, view, None)       exactly the unlit call, its draws unchanged
+ *     if NoScatter: return light
+ *     e = obj.emission.emit();  if obj is in the list: e = e * w
+ *     light = light + throughput * e
+ *     diffuse = obj.mat is LambertianDiffuse, or Plastic whose Fresnel draw chose the diffuse arm (material.rs:587-588)
+ *     if diffuse:                                                 (albedo = the material's colour)
+ *         b = rng.next();  u1 = rng.next();  u2 = rng.next()      always three draws, after evaluate's own
+ *         k = min((uint32)(b * (double)K), K - 1);  q = light k's Hittable::sample(u1, u2);  l_s = (q - position).unit()
+ *         ndl_s = normal . l_s
+ *         if ndl_s > 0.0:
+ *             den = p_L(position, l_s) + ndl_s * RR_FRAC_1_PI
+ *             if den < +inf:                                      (false for NaN as well)
+ *                 C = ((albedo * RR_FRAC_1_PI) * ndl_s) / den     (Div<f64> multiplies by the reciprocal)
+ *                 hit_s = Bvh::intersect(Ray{position, l_s}, z_near, z_far)       one query, counted
+ *                 if hit_s is Hit and its object is in the list:
+ *                     light = light + (throughput * C) * hit_s.obj.emission.emit()
+ *         l = ev.ray.direction;  ndl = normal . l;  pc = ndl * RR_FRAC_1_PI;  pl = p_L(position, l)
+ *         w_next = pc / (pc + pl) if pl > 0.0 else 1.0            (a NaN pl: 1.0)
+ *     else: w_next = 1.0
+ *     throughput = throughput * ev.color;  the roulette and DivAssign as in the reference (one draw);  w = w_next;  r = ev.ray
+ * The shadow sample is credited BEFORE the roulette: it is traced even if the roulette then ends the path, and at the last
+ * bounce max_bounces allows.  The shadow query does not count against max_bounces; it does count in queries_i, which can
+ * therefore reach S * (2 * max_bounces + 1).  A miss, and a listed object met by the first ray, are as in RADIANCE QUERY: w is 1
+ * there.  The shadow query is the closest-hit query, whole; there is no any-hit shortcut.
+ *
+ * Why it is unbiased.  Seen from a diffuse point, a direction l has density p_L(l) under the light arm and pc(l) under the
+ * cosine arm.  Light that a LISTED object sends along l is collected twice: by the shadow sample when the light arm draws l,
+ * with weight p_L / (p_L + pc) -- C is brdf * cosine / p_L times that weight --, and by the continuation when the cosine arm
+ * draws l and the next hit is listed, with weight w = pc / (p_L + pc).  The two weights sum to 1 wherever a listed object is the
+ * first thing seen along l (where it is not, the shadow sample is blocked and p_L prices a light the continuation does not
+ * meet: both sides collect nothing of it).  Objects outside the list keep their full weight and are found by BSDF sampling
+ * alone, as is the environment.  A bounce that is not diffuse has no light arm, so what it meets next has weight 1.
+ *
+ * Which materials a listed emitter may have.  The reference adds a hit's emission only inside Scatter (lib.rs:530-550): an
+ * emitter whose material can answer NoScatter radiates less than emit(), and the shadow sample, which credits emit() whole,
+ * would over-credit it.  So a listed object with emission.emit() != 0 must have a material whose scatter has no NoScatter
+ * path: LambertianDiffuse, Reflect or Glass (material.rs: Refract answers NoScatter at total internal reflection, the three
+ * Cook-Torrance materials and Plastic's specular arm where a sampled direction is rejected or worth zero, NoReflect always).
+ * Any other material on a listed emitter is RAYRS_UNSUPPORTED.  A dark listed object (a portal) may have any material.
+ *
+ * K = 0: every entry point below returns, bit for bit and count for count, what its unlit counterpart returns; no extra draw
+ * is taken.
+ *
+ * RADIANCE, DIRECT (rayrs_scene_radiance_direct): RADIANCE QUERY with the turn above.
+ * IRRADIANCE, DIRECT (rayrs_scene_irradiance_direct): with K >= 1 the point is a virtual Lambertian bounce of albedo (1, 1, 1)
+ * at position = p_i + n_i * bias, normal n_i.  Draws 0 and 1 make IRRADIANCE's cosine ray l, exactly as in the unlit form; draws
+ * 2, 3 and 4 are b, u1, u2; the shadow sample's credit is C * emit (throughput is 1); w for the first ray is w_next as above;
+ * there is no roulette at the virtual bounce; and
+ *     L_{i,s} = credit + radiance(scene, Ray{position, l}, max_bounces)     the path going on at draw 5.
+ * max_bounces == 0: +0, 0 queries, no shadow query.
+ * IMAGE FORM (rayrs_render_direct): pixels, keys, the primary ray, the sums and the fast_traversal treatment are
+ * rayrs_render_lit's.  The sums, sample_chunk, index_base and seed are RADIANCE QUERY's throughout.
+ *
+ * `lights` is a HOST pointer in every form, as in LIGHT SAMPLING.  Refusals: LIGHT SAMPLING's, in its order, with the material
+ * rule above in the RAYRS_UNSUPPORTED group (after the triangle check), and the overflow guard
+ * (uint64)samples * (2 * max_bounces + 1) >= 2^32 in place of RADIANCE QUERY's. */
+int rayrs_scene_radiance_direct(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                                uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base, uint32_t fast_traversal,
+                                const uint32_t* lights, uint32_t n_lights, double* radiance /* may be NULL */,
+                                uint32_t* queries /* may be NULL */);
+int rayrs_scene_radiance_direct_launch(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                                       uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base,
+                                       uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                       double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_scene_irradiance_direct(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                  uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                                  uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                  double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */);
+int rayrs_scene_irradiance_direct_launch(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                         uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                                         uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                         double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_render_direct(rayrs_scene* scene, const rayrs_camera* camera, uint64_t seed, uint32_t samples, uint32_t max_bounces,
+                        uint32_t sample_chunk, uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                        double* out_rgb /* H*W*3 */, uint32_t* queries /* H*W, may be NULL */);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -974,7 +1066,8 @@ int rayrs_render_lit(rayrs_scene* scene, const rayrs_camera* camera, uint64_t se
  * rayrs_scene_intersect, rayrs_scene_occluded and their _launch forms (RAY QUERIES), and with
  * rayrs_scene_ambient_occlusion, its _launch form and rayrs_render_ao (AMBIENT OCCLUSION), and with rayrs_scene_radiance,
  * rayrs_scene_irradiance and their _launch forms (RADIANCE QUERY, IRRADIANCE), and with rayrs_scene_radiance_lit,
- * rayrs_scene_irradiance_lit, their _launch forms and rayrs_render_lit (LIGHT SAMPLING).  The layout table below begins with this
+ * rayrs_scene_irradiance_lit, their _launch forms and rayrs_render_lit (LIGHT SAMPLING), and with rayrs_scene_radiance_direct,
+ * rayrs_scene_irradiance_direct, their _launch forms and rayrs_render_direct (DIRECT LIGHTING).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

@@ -491,7 +491,10 @@ class Scene:
 
     # ---- radiance queries (include/rayrs_hip.h RADIANCE QUERY, IRRADIANCE)
 
-    def _radiance(self, name, a, b, samples, max_bounces, sample_chunk, bias, seed, index_base, fast_traversal, queries, lights=None):
+    def _radiance(self, name, a, b, samples, max_bounces, sample_chunk, bias, seed, index_base, fast_traversal, queries, lights=None,
+                  direct=False):
+        if direct and lights is None:
+            raise ValueError("direct=True needs a light list (lights=[...])")
         torch, a, b, _, n = self._query_inputs(a, b)
         if int(samples) < 1:
             raise ValueError("samples must be at least 1")
@@ -500,7 +503,7 @@ class Scene:
                (int(seed), int(index_base), int(bool(fast_traversal)))
         if lights is not None:  # (a host array in every form: include/rayrs_hip.h LIGHT SAMPLING)
             lights = _light_list(lights)
-            name += "_lit"
+            name += "_direct" if direct else "_lit"
             args += (lights.ctypes.data if len(lights) else None, len(lights))
         if torch is None:
             rad, cnt = np.zeros((m, 3)), np.zeros(m, dtype=np.uint32)
@@ -516,26 +519,31 @@ class Scene:
         return (rad[:n], cnt[:n]) if queries else rad[:n]
 
     def radiance(self, origins, directions, samples: int = 1, max_bounces: int = 50, seed: int = 0x5EED, index_base: int = 0,
-                 sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None):
+                 sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None, direct: bool = False):
         """The path-traced light arriving along every ray (origins[i], directions[i]), the mean of `samples` paths of the
         render's radiance loop: radiance (n, 3) f64, and with queries also the number of closest-hit queries the ray's paths
         made, (n,) uint32.  Rays are used as given.  Sample s of ray i draws from the key of (seed, index_base + i, s), so a
         call on rays[a:b] with index_base=a returns the slice of the whole call's answer; sample_chunk is
         rayrs_render_params.sample_chunk's rule for the order of the sum.  lights: None, or up to 8 object indices (emitters())
         that diffuse surfaces sample half of the time (include/rayrs_hip.h LIGHT SAMPLING; an empty list computes what None
-        computes).  Inputs and where the answers live as intersect()."""
+        computes).  direct=True (with lights): every diffuse bounce keeps its own direction and sends one more ray towards a
+        sampled point of a light, the two weighted by the balance heuristic (include/rayrs_hip.h DIRECT LIGHTING).  Inputs and
+        where the answers live as intersect()."""
         return self._radiance("rayrs_scene_radiance", origins, directions, samples, max_bounces, sample_chunk, None, seed, index_base,
-                              fast_traversal, queries, lights)
+                              fast_traversal, queries, lights, direct)
 
     def irradiance(self, points, normals, samples: int = 64, bias: float = 0.0, max_bounces: int = 50, seed: int = 0x5EED,
-                   index_base: int = 0, sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None):
+                   index_base: int = 0, sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None,
+                   direct: bool = False):
         """The cosine-weighted mean of the light arriving at points[i] around normals[i], E / pi, from `samples` paths that
         leave points[i] + normals[i] * bias in ambient_occlusion()'s directions: (n, 3) f64 (multiply by pi for the
         irradiance; a Lambertian texel of albedo rho radiates rho times the value).  Points and normals are used as given.
         With lights the first direction too is drawn from the mix of the lights and the cosine lobe, and the sample is weighted
-        for it: the same mean, with less noise under a small lamp.  The other arguments, inputs and answers as radiance()."""
+        for it: the same mean, with less noise under a small lamp.  With direct=True the first direction stays the cosine lobe's
+        and the point sends a shadow ray of its own, as a diffuse bounce does.  The other arguments, inputs and answers as
+        radiance()."""
         return self._radiance("rayrs_scene_irradiance", points, normals, samples, max_bounces, sample_chunk, bias, seed, index_base,
-                              fast_traversal, queries, lights)
+                              fast_traversal, queries, lights, direct)
 
     def lab_radiance_tuning(self, refill_below: int = 0, shade_at: int = 0, leaf_min: int = 0):
         """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_radiance_tuning: for tests and scripts/ubench only; 0 = the default."""
@@ -709,16 +717,20 @@ def emitters(objects) -> List[int]:
 
 
 def render_lit(scene: Scene, camera: Camera, samples: int, lights, max_bounces: int = 50, seed: int = 0x5EED, sample_chunk: int = 0,
-               fast_traversal: bool = False, queries: bool = False):
+               fast_traversal: bool = False, queries: bool = False, direct: bool = False):
     """The view's radiance with light sampling (include/rayrs_hip.h LIGHT SAMPLING, the image form): (H, W, 3) f64, the mean of
     `samples` paths per pixel whose diffuse surfaces sample `lights` half of the time; with queries also the (H, W) uint32
-    closest-hit queries per pixel.  With an empty list the frame is render(..., out_f64=True)'s, bit for bit."""
+    closest-hit queries per pixel.  With an empty list the frame is render(..., out_f64=True)'s, bit for bit.  direct=True:
+    DIRECT LIGHTING's image form instead, a shadow ray per diffuse bounce beside the surface's own direction."""
+    if direct and lights is None:
+        raise ValueError("direct=True needs a light list (lights=[...])")
     H, W = camera.y_pixels(), camera.x_pixels()
     lights = _light_list(lights)
     out, cnt = np.zeros((H, W, 3)), np.zeros((H, W), dtype=np.uint32)
-    _ffi.check(scene._L.rayrs_render_lit(scene._h, C.byref(camera.desc), int(seed), int(samples), int(max_bounces), int(sample_chunk),
-                                         int(bool(fast_traversal)), lights.ctypes.data if len(lights) else None, len(lights),
-                                         out.ctypes.data, cnt.ctypes.data), "rayrs_render_lit")
+    name = "rayrs_render_direct" if direct else "rayrs_render_lit"
+    _ffi.check(getattr(scene._L, name)(scene._h, C.byref(camera.desc), int(seed), int(samples), int(max_bounces), int(sample_chunk),
+                                       int(bool(fast_traversal)), lights.ctypes.data if len(lights) else None, len(lights),
+                                       out.ctypes.data, cnt.ctypes.data), name)
     return (out, cnt) if queries else out
 
 

@@ -9,26 +9,16 @@
 
 #include "../../include/rayrs_hip.h"
 #include "../../include/rayrs_numeric.h"
+#include "radiance_direct_kernels.h"
+#include "radiance_lit_host.hpp"
 #include "radiance_lit_kernels.h"
 #include "scene_internal.hpp"
 
-using namespace rayrs;
-
+namespace rayrs {
 namespace {
 
-// What a call asks for, beside its buffers.
-struct LitCall {
-    int start;  // LIT_START_*
-    uint32_t samples, max_bounces, sample_chunk;
-    double bias;
-    uint64_t seed, index_base;
-    uint32_t fast_traversal;
-    const uint32_t* lights;
-    uint32_t n_lights;
-};
-
 // The depth-first slot of every object (the inverse of flat.prim_object), made once.
-const std::vector<uint32_t>& object_prim(rayrs_scene* scene) {
+const std::vector<uint32_t>& lit_object_prim(rayrs_scene* scene) {
     std::vector<uint32_t>& map = scene->lit.object_prim;
     const std::vector<uint32_t>& po = scene->flat.prim_object;
     if (map.size() != po.size()) {
@@ -42,12 +32,37 @@ const uint32_t* prim_record(const rayrs_scene* scene, uint32_t p) {
     const uint32_t dw = scene->flat.compact ? PRIM_DWORDS_COMPACT : PRIM_DWORDS_FULL;
     return reinterpret_cast<const uint32_t*>(scene->flat.prim_bytes.data()) + (size_t)p * dw;
 }
-uint32_t prim_tag(const rayrs_scene* scene, uint32_t p) {
+uint32_t lit_prim_tag(const rayrs_scene* scene, uint32_t p) {
     return prim_record(scene, p)[(scene->flat.compact ? PRIM_DWORDS_COMPACT : PRIM_DWORDS_FULL) - 1u];
 }
 
+// DIRECT LIGHTING's material rule on a list whose indices are checked (true: refuse).  A listed object that emits must have a
+// material whose scatter has no NoScatter path -- LambertianDiffuse, Reflect, Glass (material.rs: Refract and the Cook-Torrance
+// family, Plastic's arm among them, can answer NoScatter, NoReflect always does): radiance() adds a hit's emission inside Scatter
+// only (lib.rs:530-550), and the shadow sample credits emit() whole.
+bool direct_list_unsupported(rayrs_scene* scene, const LitCall& c) {
+    const std::vector<uint32_t>& map = lit_object_prim(scene);
+    for (uint32_t k = 0; k < c.n_lights; k++) {
+        const SurfaceDev& s = scene->surfaces[lit_prim_tag(scene, map[c.lights[k]]) >> 8];
+        const bool dark = s.emit[0] == 0.0 && s.emit[1] == 0.0 && s.emit[2] == 0.0;
+        const bool always_scatters = s.kind == RAYRS_MAT_LAMBERTIAN || s.kind == RAYRS_MAT_REFLECT || s.kind == RAYRS_MAT_GLASS;
+        if (!dark && !always_scatters) return true;
+    }
+    return false;
+}
+
+// The list as the depth-first slots a walk answers with (radiance_direct_kernels.h LightSlotsDev).
+LightSlotsDev direct_slots(rayrs_scene* scene, const LitCall& c) {
+    LightSlotsDev out;
+    std::memset(&out, 0, sizeof(out));
+    const std::vector<uint32_t>& map = lit_object_prim(scene);
+    for (uint32_t k = 0; k < c.n_lights; k++) out.prim[k] = map[c.lights[k]];
+    return out;
+}
+
 // The refusals that need no device, in the header's order: RADIANCE QUERY's with the list's among them.  `extra_invalid` and
-// `extra_unsupported` are what the image form adds to the two groups (the camera's).
+// `extra_unsupported` are what the image form adds to the two groups (the camera's).  A direct call can make 2 * max_bounces + 1
+// queries per path, and has its material rule.
 int lit_check(rayrs_scene* scene, const void* a, const void* b, const void* radiance, const void* queries, const LitCall& c,
               bool extra_invalid = false, bool extra_unsupported = false) {
     if (!scene || !a || !b || (!radiance && !queries)) return RAYRS_INVALID_ARG;
@@ -57,13 +72,15 @@ int lit_check(rayrs_scene* scene, const void* a, const void* b, const void* radi
     for (uint32_t k = 0; k < c.n_lights; k++)
         if (c.lights[k] >= n_objects) return RAYRS_INVALID_ARG;
     if (c.samples > SLOT_SAMPLE_MASK || c.max_bounces > 8000u || extra_unsupported) return RAYRS_UNSUPPORTED;
-    if ((uint64_t)c.samples * c.max_bounces >= (1ull << 32)) return RAYRS_UNSUPPORTED;
+    const uint64_t path_queries = c.direct ? 2ull * c.max_bounces + 1u : c.max_bounces;
+    if ((uint64_t)c.samples * path_queries >= (1ull << 32)) return RAYRS_UNSUPPORTED;
     if (radiance_chunks(c.samples, c.sample_chunk) > RADIANCE_LAUNCH_ITEMS) return RAYRS_UNSUPPORTED;
     if (c.n_lights > RAYRS_MAX_LIGHTS) return RAYRS_UNSUPPORTED;
     if (c.n_lights > 0u) {
-        const std::vector<uint32_t>& map = object_prim(scene);
+        const std::vector<uint32_t>& map = lit_object_prim(scene);
         for (uint32_t k = 0; k < c.n_lights; k++)
-            if ((prim_tag(scene, map[c.lights[k]]) & 3u) == PRIM_TRIANGLE) return RAYRS_UNSUPPORTED;
+            if ((lit_prim_tag(scene, map[c.lights[k]]) & 3u) == PRIM_TRIANGLE) return RAYRS_UNSUPPORTED;
+        if (c.direct && direct_list_unsupported(scene, c)) return RAYRS_UNSUPPORTED;
     }
     if (scene->device < 0) return RAYRS_NO_DEVICE;
     return RAYRS_OK;
@@ -76,10 +93,10 @@ LightsDev lights_resolve(rayrs_scene* scene, const LitCall& c) {
     std::memset(&out, 0, sizeof(out));
     out.n = c.n_lights;
     if (c.n_lights == 0u) return out;
-    const std::vector<uint32_t>& map = object_prim(scene);
+    const std::vector<uint32_t>& map = lit_object_prim(scene);
     for (uint32_t k = 0; k < c.n_lights; k++) {
         const uint32_t p = map[c.lights[k]];
-        const uint32_t tag = prim_tag(scene, p);
+        const uint32_t tag = lit_prim_tag(scene, p);
         double v[5] = {0, 0, 0, 0, 0};
         std::memcpy(v, prim_record(scene, p), ((tag & 3u) == PRIM_SPHERE ? 4u : 5u) * sizeof(double));
         LightDev& L = out.light[k];
@@ -116,6 +133,9 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
     }
     if (strip.strip_in_use) HIP_TRY(hipStreamWaitEvent(stream, strip.ev_done, 0));
 
+    LightSlotsDev slots;
+    std::memset(&slots, 0, sizeof(slots));
+    if (c.direct) slots = direct_slots(scene, c);
     RadianceDev rd;
     std::memset(&rd, 0, sizeof(rd));
     rd.samples = c.samples, rd.max_bounces = c.max_bounces, rd.irradiance = c.start == LIT_START_POINT ? 1u : 0u;
@@ -137,7 +157,8 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
         rd.radiance = radiance ? radiance + base * 3u : nullptr;
         rd.queries = queries ? queries + base : nullptr;
         HIP_TRY(hipMemsetAsync(rd.cursor, 0, sizeof(unsigned long long), stream));
-        HIP_TRY(launch_radiance_lit(scene->flat.compact, sc, rd, lights, cam, c.start, scene->cu_count, stream));
+        if (c.direct) HIP_TRY(launch_radiance_direct(scene->flat.compact, sc, rd, lights, slots, cam, c.start, scene->cu_count, stream));
+        else HIP_TRY(launch_radiance_lit(scene->flat.compact, sc, rd, lights, cam, c.start, scene->cu_count, stream));
     }
     HIP_TRY(hipEventRecord(strip.ev_done, stream));
     strip.strip_in_use = true;
@@ -160,6 +181,8 @@ int lit_host(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const Lig
     return RAYRS_OK;
 }
 
+}  // namespace
+
 int lit_entry(rayrs_scene* scene, const LitCall& c, const double* a, const double* b, uint64_t n, double* radiance, uint32_t* queries,
               bool launch, void* hip_stream) {
     RAYRS_TRY(lit_check(scene, a, b, radiance, queries, c));
@@ -173,7 +196,23 @@ int lit_entry(rayrs_scene* scene, const LitCall& c, const double* a, const doubl
     return lit_enqueue(scene, c, sc, lights, cam, a, b, n, radiance, queries, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
-}  // namespace
+int lit_render(rayrs_scene* scene, const rayrs_camera* camera, const LitCall& c, double* out_rgb, uint32_t* queries) {
+    // (the camera's refusals are FEATURES', as rayrs_render_ao's: an empty image with the arguments, a side above 65535 with the sizes)
+    const bool no_image = camera && (camera->x_pixels == 0u || camera->y_pixels == 0u);
+    const bool too_wide = camera && (camera->x_pixels > 65535u || camera->y_pixels > 65535u);
+    RAYRS_TRY(lit_check(scene, camera, out_rgb, out_rgb, queries, c, no_image, too_wide));
+    RAYRS_TRY(scene_settle(scene));
+    const LightsDev table = lights_resolve(scene, c);
+    const FrameWalk walk = frame_walk(scene, camera, c.fast_traversal);  // the walk a render with these settings takes
+    const SceneDev sc = make_scene_dev(scene, walk.exact || walk.use_local);
+    const CameraDev cam = make_camera_dev(camera);
+    const uint64_t npix = (uint64_t)camera->x_pixels * camera->y_pixels;
+    return lit_host(scene, c, sc, table, cam, nullptr, nullptr, npix, out_rgb, queries);
+}
+
+}  // namespace rayrs
+
+using namespace rayrs;
 
 extern "C" {
 
@@ -219,18 +258,8 @@ int rayrs_render_lit(rayrs_scene* scene, const rayrs_camera* camera, uint64_t se
                      uint32_t sample_chunk, uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights, double* out_rgb,
                      uint32_t* queries) {
     RAYRS_GUARDED({
-    const LitCall c{LIT_START_PIXEL, samples, max_bounces, sample_chunk, 0.0, seed, 0u, fast_traversal, lights, n_lights};
-    // (the camera's refusals are FEATURES', as rayrs_render_ao's: an empty image with the arguments, a side above 65535 with the sizes)
-    const bool no_image = camera && (camera->x_pixels == 0u || camera->y_pixels == 0u);
-    const bool too_wide = camera && (camera->x_pixels > 65535u || camera->y_pixels > 65535u);
-    RAYRS_TRY(lit_check(scene, camera, out_rgb, out_rgb, queries, c, no_image, too_wide));
-    RAYRS_TRY(scene_settle(scene));
-    const LightsDev table = lights_resolve(scene, c);
-    const FrameWalk walk = frame_walk(scene, camera, fast_traversal);  // the walk a render with these settings takes
-    const SceneDev sc = make_scene_dev(scene, walk.exact || walk.use_local);
-    const CameraDev cam = make_camera_dev(camera);
-    const uint64_t npix = (uint64_t)camera->x_pixels * camera->y_pixels;
-    return lit_host(scene, c, sc, table, cam, nullptr, nullptr, npix, out_rgb, queries);
+    return lit_render(scene, camera, LitCall{LIT_START_PIXEL, samples, max_bounces, sample_chunk, 0.0, seed, 0u, fast_traversal, lights, n_lights},
+                      out_rgb, queries);
     })
 }
 
