@@ -1055,6 +1055,102 @@ int rayrs_render_direct(rayrs_scene* scene, const rayrs_camera* camera, uint64_t
                         uint32_t sample_chunk, uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
                         double* out_rgb /* H*W*3 */, uint32_t* queries /* H*W, may be NULL */);
 
+/* ---- radiance queries with the sky among the lights: DIRECT LIGHTING above leaves the environment to BSDF sampling alone.  Here
+ * the HDRI is one more light of it: directions are drawn from the map in proportion to its brightness, the same one shadow ray
+ * per diffuse bounce may go to the sky, and the sky a continuation ray escapes to is weighted by the same balance heuristic.  A
+ * map that is dark but for a window or a sun disc is to the environment what a small lamp is to the scene.  The reference clips
+ * its map to [0, 3] (main.rs:42-43), so a texel is at most 3 and the gain is bounded by how uneven a clipped map can be.  The
+ * kernels are a unit of their own (radiance_sky.hip); nothing above changes.
+ *
+ * SKY SAMPLING, specified to the operation.  Everything is f64 and unfused; the elementary functions are rayrs_numeric.h's.  w, h
+ * are the HDRI's sizes; texel(i, j) is the clipped texel (row i, column j), widened to f64, that Scene::background reads.
+ *
+ * The table.  Built once per scene on the host from the host scene's HDRI (a scene made with device = -1 has one), lazily at the
+ * first sky call, and uploaded once per device.  Its cells are the bilinear cells of background(): (i, j), i in 0..h-2, j in 0..w-2.
+ *     L(i, j) = (r + g) + b of texel(i, j)
+ *     s_i = rr_sin(((double)i + 0.5) * RR_PI / (double)(h - 1))
+ *     A[i][j] = s_i * (((L(i,j) + L(i+1,j)) + L(i,j+1)) + L(i+1,j+1))
+ *     C[i][j] = the inclusive prefix of A[i][.] in j order: the first assigned, then one add per cell
+ *     R_i = C[i][w-2]
+ *     M[i] = the inclusive prefix of R_. in i order, likewise
+ *     T = M[h-2]
+ * T not > 0.0, or not finite, is RAYRS_UNSUPPORTED: there is nothing to sample.  Additions of non-negative f64 are monotone, so
+ * the prefixes are non-decreasing, and "the first index whose prefix exceeds the target" is the same index for any search.
+ *
+ * sky_sample(u1, u2):
+ *     ty = u1 * T;  i = the first index with M[i] > ty, or h-2 if there is none
+ *     below = i > 0 ? M[i-1] : 0.0;  y = (double)i + (ty - below) / R_i
+ *     tx = u2 * R_i;  j = the first index with C[i][j] > tx, or w-2 if there is none
+ *     below = j > 0 ? C[i][j-1] : 0.0;  x = (double)j + (tx - below) / A[i][j]
+ *     theta = y / (double)(h - 1) * RR_PI;  phi = x / (double)(w - 1) * (2.0 * RR_PI);  psi = phi - RR_PI
+ *     (st, ct) = rr_sincos(theta);  (sp, cp) = rr_sincos(psi);  l_s = (cp * st, ct, sp * st)
+ * the inverse of background()'s mapping (lib.rs:254-285).  A 0 / 0 (a fall-through onto an empty row or cell) takes what IEEE
+ * gives: the NaN direction then fails ndl_s > 0.0 and the sample is skipped.
+ *
+ * p_env(l):
+ *     dir = l.unit();  phi, theta, x, y exactly Scene::background's (lib.rs:254-263)
+ *     i = min(usize(floor(y)), h - 2);  j = min(usize(floor(x)), w - 2)
+ *     sn = rr_sqrt(1.0 - dir.y * dir.y)
+ *     p_env = ((A[i][j] / T) * ((double)(w - 1) * (double)(h - 1))) / (((2.0 * RR_PI) * RR_PI) * sn)
+ * the solid-angle density of sky_sample's directions: A[i][j] / T of the draws fall in a cell, uniformly in (x, y), and a cell
+ * spans 2 pi / (w - 1) of phi and pi / (h - 1) of theta.  At a pole sn = 0 and p_env = +inf: a shadow sample there is skipped
+ * by den < +inf, and a continuation exactly along the axis gets weight 0 -- a set of measure zero.
+ *
+ * The turn is DIRECT LIGHTING's with M = K + 1 lights: K <= RAYRS_MAX_LIGHTS listed lamps, possibly none, and the sky, which is
+ * index K.  What changes in it:
+ *     b = rng.next();  u1 = rng.next();  u2 = rng.next()          the draws unchanged, always three
+ *     k = min((uint32)(b * (double)M), M - 1);  l_s = sky_sample(u1, u2) if k == K, else light k's sample as in DIRECT LIGHTING
+ *     p_M(position, l) = (p_0 assigned, then += p_k in list order, then += p_env(l) last; with K = 0, p_env assigned) / (double)M
+ *         stands wherever DIRECT LIGHTING writes p_L(position, l): in den and in pm = p_M(position, ev.ray.direction)
+ *     after hit_s = Bvh::intersect(Ray{position, l_s}, z_near, z_far), whichever k was drawn:
+ *         if hit_s is Hit and its object is in the list:  light = light + (throughput * C) * hit_s.obj.emission.emit()
+ *         if hit_s is Miss:  light = light + (throughput * C) * background(l_s)
+ *     w_next = pc / (pc + pm) if pm > 0.0 else 1.0
+ *     at a Miss of the path's own ray:  return light + throughput * (background(dir) * w)
+ * w is 1.0 for a first ray and after a bounce that is not diffuse, so the background's bits are then the unlit ones.  Unlisted
+ * objects keep weight 1.  The material rule for listed emitters, the overflow guard, queries_i (shadow rays counted),
+ * IRRADIANCE's virtual bounce (draws 2, 3 and 4, the path going on at draw 5 -- here with K = 0 too, there is always the sky;
+ * a virtual bounce's shadow ray that misses credits C * background(l_s)) and the image form are DIRECT LIGHTING's.
+ *
+ * Why it is unbiased.  Seen from a diffuse point, a direction l has density p_M(l) under the light arm and pc(l) under the cosine
+ * arm.  Light arriving along l from the sky or from a listed object is collected by the shadow sample with weight
+ * p_M / (p_M + pc) and by the continuation with weight pc / (p_M + pc): the two sum to 1 wherever the sky or a listed object is
+ * the first thing seen along l.  Where p_M is 0 -- a black cell with no lamp behind it -- the light arm never draws l and the
+ * continuation keeps weight 1.  Where an unlisted object is the first thing seen, the shadow sample is blocked and the
+ * continuation meets an object of weight 1: both sides collect nothing of the light p_M prices.
+ *
+ * rayrs_scene_radiance_sky, rayrs_scene_irradiance_sky, their _launch forms and rayrs_render_sky take exactly the arguments of
+ * their _direct counterparts: lights, n_lights name the lamps, the sky is always on, and n_lights == 0 is legal, the sky alone.
+ * Every entry point above keeps its behaviour; the _direct calls still refuse the index 0xffffffff as an argument.  Refusals:
+ * DIRECT LIGHTING's, in its order, with the empty table in the RAYRS_UNSUPPORTED group after the material rule.  The light
+ * table stays in the kernel arguments and the sky's table is one device pointer beside it, so a _launch form allocates and
+ * copies nothing after a scene's first sky call on a given walk.
+ *
+ * Three calls on the host, which need no device: the table's cells A in row order ((h-1)*(w-1) f64, may be NULL) and T;
+ * sky_sample of n pairs (u1, u2); p_env of n directions.  The last two refuse an empty table as RAYRS_UNSUPPORTED. */
+int rayrs_scene_radiance_sky(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                             uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base, uint32_t fast_traversal,
+                             const uint32_t* lights, uint32_t n_lights, double* radiance /* may be NULL */,
+                             uint32_t* queries /* may be NULL */);
+int rayrs_scene_radiance_sky_launch(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                                    uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base,
+                                    uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                    double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_scene_irradiance_sky(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                               uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                               uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                               double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */);
+int rayrs_scene_irradiance_sky_launch(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                      uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                                      uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                      double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_render_sky(rayrs_scene* scene, const rayrs_camera* camera, uint64_t seed, uint32_t samples, uint32_t max_bounces,
+                     uint32_t sample_chunk, uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                     double* out_rgb /* H*W*3 */, uint32_t* queries /* H*W, may be NULL */);
+int rayrs_scene_sky_table(rayrs_scene* scene, double* cells /* (h-1)*(w-1), may be NULL */, double* total);
+int rayrs_scene_sky_sample(rayrs_scene* scene, const double* u /* n*2 */, uint64_t n, double* dir /* n*3 */);
+int rayrs_scene_sky_density(rayrs_scene* scene, const double* dir /* n*3 */, uint64_t n, double* p);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -1067,7 +1163,9 @@ int rayrs_render_direct(rayrs_scene* scene, const rayrs_camera* camera, uint64_t
  * rayrs_scene_ambient_occlusion, its _launch form and rayrs_render_ao (AMBIENT OCCLUSION), and with rayrs_scene_radiance,
  * rayrs_scene_irradiance and their _launch forms (RADIANCE QUERY, IRRADIANCE), and with rayrs_scene_radiance_lit,
  * rayrs_scene_irradiance_lit, their _launch forms and rayrs_render_lit (LIGHT SAMPLING), and with rayrs_scene_radiance_direct,
- * rayrs_scene_irradiance_direct, their _launch forms and rayrs_render_direct (DIRECT LIGHTING).  The layout table below begins with this
+ * rayrs_scene_irradiance_direct, their _launch forms and rayrs_render_direct (DIRECT LIGHTING), and with rayrs_scene_radiance_sky,
+ * rayrs_scene_irradiance_sky, their _launch forms, rayrs_render_sky, rayrs_scene_sky_table, rayrs_scene_sky_sample and
+ * rayrs_scene_sky_density (SKY SAMPLING).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

@@ -292,6 +292,7 @@ class Scene:
             _ffi.check(st, "rayrs_scene_new")
             self._h = h
             self.device = int(device)
+            self._hdri_size = (int(hdri.shape[1]), int(hdri.shape[0]))
         finally:
             L.rayrs_objects_destroy(objs)
 
@@ -306,7 +307,9 @@ class Scene:
         (one per GPU for render_multi)."""
         h = C.c_void_p()
         _ffi.check(self._L.rayrs_scene_clone_to_device(self._h, int(device), C.byref(h)), "rayrs_scene_clone_to_device")
-        return Scene._from_handle(self._L, h, device)
+        clone = Scene._from_handle(self._L, h, device)
+        clone._hdri_size = self._hdri_size
+        return clone
 
     def set_tuning(self, **kw):
         """The two scheduling choices of include/rayrs_hip.h rayrs_tuning (pool_slots, local_pool); 0 = default.
@@ -503,7 +506,10 @@ class Scene:
                (int(seed), int(index_base), int(bool(fast_traversal)))
         if lights is not None:  # (a host array in every form: include/rayrs_hip.h LIGHT SAMPLING)
             lights = _light_list(lights)
-            name += "_direct" if direct else "_lit"
+            sky = bool(direct) and bool((lights == SKY).any())   # (SKY SAMPLING: the sky beside the lamps, named once or often)
+            if sky:
+                lights = lights[lights != SKY]
+            name += "_sky" if sky else "_direct" if direct else "_lit"
             args += (lights.ctypes.data if len(lights) else None, len(lights))
         if torch is None:
             rad, cnt = np.zeros((m, 3)), np.zeros(m, dtype=np.uint32)
@@ -527,8 +533,9 @@ class Scene:
         rayrs_render_params.sample_chunk's rule for the order of the sum.  lights: None, or up to 8 object indices (emitters())
         that diffuse surfaces sample half of the time (include/rayrs_hip.h LIGHT SAMPLING; an empty list computes what None
         computes).  direct=True (with lights): every diffuse bounce keeps its own direction and sends one more ray towards a
-        sampled point of a light, the two weighted by the balance heuristic (include/rayrs_hip.h DIRECT LIGHTING).  Inputs and
-        where the answers live as intersect()."""
+        sampled point of a light, the two weighted by the balance heuristic (include/rayrs_hip.h DIRECT LIGHTING); with SKY in
+        the list the environment map is one more of those lights, its directions drawn in proportion to its brightness
+        (include/rayrs_hip.h SKY SAMPLING; lights=[SKY] is the sky alone).  Inputs and where the answers live as intersect()."""
         return self._radiance("rayrs_scene_radiance", origins, directions, samples, max_bounces, sample_chunk, None, seed, index_base,
                               fast_traversal, queries, lights, direct)
 
@@ -544,6 +551,35 @@ class Scene:
         radiance()."""
         return self._radiance("rayrs_scene_irradiance", points, normals, samples, max_bounces, sample_chunk, bias, seed, index_base,
                               fast_traversal, queries, lights, direct)
+
+    # ---- the sky as a light (include/rayrs_hip.h SKY SAMPLING): host only, a scene without a device has them too
+
+    def sky_table(self):
+        """The sky's table: (cells (h - 1, w - 1) f64 -- A[i][j], the weight of bilinear cell (i, j) of the HDRI --, their total T)."""
+        w, h = self._hdri_size
+        cells, total = np.zeros((h - 1, w - 1)), C.c_double()
+        _ffi.check(self._L.rayrs_scene_sky_table(self._h, cells.ctypes.data, C.addressof(total)), "rayrs_scene_sky_table")
+        return cells, total.value
+
+    def sky_sample(self, u):
+        """sky_sample(u1, u2) of every row of u (n, 2): directions (n, 3) f64, distributed in proportion to the HDRI's brightness."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.ndim != 2 or u.shape[1] != 2:
+            raise ValueError("u must be (n, 2)")
+        out = np.zeros((max(len(u), 1), 3))
+        _ffi.check(self._L.rayrs_scene_sky_sample(self._h, u.ctypes.data if len(u) else out.ctypes.data, len(u), out.ctypes.data),
+                   "rayrs_scene_sky_sample")
+        return out[:len(u)]
+
+    def sky_density(self, directions):
+        """p_env of every direction (n, 3): the solid-angle density of sky_sample's directions, (n,) f64."""
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError("directions must be (n, 3)")
+        out = np.zeros(max(len(d), 1))
+        _ffi.check(self._L.rayrs_scene_sky_density(self._h, d.ctypes.data if len(d) else out.ctypes.data, len(d), out.ctypes.data),
+                   "rayrs_scene_sky_density")
+        return out[:len(d)]
 
     def lab_radiance_tuning(self, refill_below: int = 0, shade_at: int = 0, leaf_min: int = 0):
         """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_radiance_tuning: for tests and scripts/ubench only; 0 = the default."""
@@ -694,6 +730,10 @@ def render_ao(scene: Scene, camera: Camera, samples: int = 16, t_max=None, bias:
     return (vis, cnt) if counts else vis
 
 
+# The sky in a light list: the number Scene.intersect returns as `object` for a miss (include/rayrs_hip.h SKY SAMPLING).
+SKY = 0xFFFFFFFF
+
+
 def _light_list(lights):
     """A light list as the contiguous uint32 host array the library reads."""
     lights = np.ascontiguousarray(lights, dtype=np.int64).reshape(-1)
@@ -721,13 +761,17 @@ def render_lit(scene: Scene, camera: Camera, samples: int, lights, max_bounces: 
     """The view's radiance with light sampling (include/rayrs_hip.h LIGHT SAMPLING, the image form): (H, W, 3) f64, the mean of
     `samples` paths per pixel whose diffuse surfaces sample `lights` half of the time; with queries also the (H, W) uint32
     closest-hit queries per pixel.  With an empty list the frame is render(..., out_f64=True)'s, bit for bit.  direct=True:
-    DIRECT LIGHTING's image form instead, a shadow ray per diffuse bounce beside the surface's own direction."""
+    DIRECT LIGHTING's image form instead, a shadow ray per diffuse bounce beside the surface's own direction; with SKY in the
+    list, SKY SAMPLING's: the environment map is one more of the lights."""
     if direct and lights is None:
         raise ValueError("direct=True needs a light list (lights=[...])")
     H, W = camera.y_pixels(), camera.x_pixels()
     lights = _light_list(lights)
+    sky = bool(direct) and bool((lights == SKY).any())
+    if sky:
+        lights = lights[lights != SKY]
     out, cnt = np.zeros((H, W, 3)), np.zeros((H, W), dtype=np.uint32)
-    name = "rayrs_render_direct" if direct else "rayrs_render_lit"
+    name = "rayrs_render_sky" if sky else "rayrs_render_direct" if direct else "rayrs_render_lit"
     _ffi.check(getattr(scene._L, name)(scene._h, C.byref(camera.desc), int(seed), int(samples), int(max_bounces), int(sample_chunk),
                                        int(bool(fast_traversal)), lights.ctypes.data if len(lights) else None, len(lights),
                                        out.ctypes.data, cnt.ctypes.data), name)

@@ -12,6 +12,7 @@
 #include "radiance_direct_kernels.h"
 #include "radiance_lit_host.hpp"
 #include "radiance_lit_kernels.h"
+#include "radiance_sky_kernels.h"
 #include "scene_internal.hpp"
 
 namespace rayrs {
@@ -82,6 +83,7 @@ int lit_check(rayrs_scene* scene, const void* a, const void* b, const void* radi
             if ((lit_prim_tag(scene, map[c.lights[k]]) & 3u) == PRIM_TRIANGLE) return RAYRS_UNSUPPORTED;
         if (c.direct && direct_list_unsupported(scene, c)) return RAYRS_UNSUPPORTED;
     }
+    if (c.sky && !sky_table_usable(scene)) return RAYRS_UNSUPPORTED;  // SKY SAMPLING: an empty table, nothing to sample
     if (scene->device < 0) return RAYRS_NO_DEVICE;
     return RAYRS_OK;
 }
@@ -118,6 +120,9 @@ LightsDev lights_resolve(rayrs_scene* scene, const LitCall& c) {
 // rays are the camera's pixels index_base + i.
 int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const LightsDev& lights, const CameraDev& cam, const double* a,
                 const double* b, uint64_t n, double* radiance, uint32_t* queries, hipStream_t stream) {
+    SkyDev sky;
+    std::memset(&sky, 0, sizeof(sky));
+    if (c.sky) RAYRS_TRY(sky_device_table(scene, &sky));  // (uploaded by the scene's first sky call, then kept)
     if (c.max_bounces == 0u) {  // the loop runs no turn: +0 and no query, whatever the scene
         if (radiance) HIP_TRY(hipMemsetAsync(radiance, 0, n * 3u * sizeof(double), stream));
         if (queries) HIP_TRY(hipMemsetAsync(queries, 0, n * sizeof(uint32_t), stream));
@@ -157,7 +162,8 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
         rd.radiance = radiance ? radiance + base * 3u : nullptr;
         rd.queries = queries ? queries + base : nullptr;
         HIP_TRY(hipMemsetAsync(rd.cursor, 0, sizeof(unsigned long long), stream));
-        if (c.direct) HIP_TRY(launch_radiance_direct(scene->flat.compact, sc, rd, lights, slots, cam, c.start, scene->cu_count, stream));
+        if (c.sky) HIP_TRY(launch_radiance_sky(scene->flat.compact, sc, rd, lights, slots, sky, cam, c.start, scene->cu_count, stream));
+        else if (c.direct) HIP_TRY(launch_radiance_direct(scene->flat.compact, sc, rd, lights, slots, cam, c.start, scene->cu_count, stream));
         else HIP_TRY(launch_radiance_lit(scene->flat.compact, sc, rd, lights, cam, c.start, scene->cu_count, stream));
     }
     HIP_TRY(hipEventRecord(strip.ev_done, stream));

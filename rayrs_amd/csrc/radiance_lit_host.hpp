@@ -1,9 +1,10 @@
-// radiance_lit_host.hpp -- what the two units of entry points that take a light list share (radiance_lit_abi.cpp: LIGHT SAMPLING,
-// radiance_direct_abi.cpp: DIRECT LIGHTING): a call's description and its way from the refusals through the launches, all in
-// radiance_lit_abi.cpp.  A call differs between the two in `direct` alone.
+// radiance_lit_host.hpp -- what the three units of entry points that take a light list share (radiance_lit_abi.cpp: LIGHT SAMPLING,
+// radiance_direct_abi.cpp: DIRECT LIGHTING, radiance_sky_abi.cpp: SKY SAMPLING): a call's description and its way from the refusals
+// through the launches, all in radiance_lit_abi.cpp.  A call differs between the three in `direct` and `sky` alone.
 #pragma once
 #include "../../include/rayrs_hip.h"
 #include "radiance_lit_kernels.h"
+#include "radiance_sky_table.h"
 #include "scene_internal.hpp"
 
 namespace rayrs {
@@ -18,11 +19,19 @@ struct LitCall {
     const uint32_t* lights;
     uint32_t n_lights;
     bool direct;  // DIRECT LIGHTING: radiance_direct.hip's kernels, its overflow guard and its material rule
+    bool sky;     // SKY SAMPLING (with direct): radiance_sky.hip's kernels, the sky one more light; an empty table is refused
 };
 
 // the four ray and point entry points, and the image form, of either unit
 int lit_entry(rayrs_scene* scene, const LitCall& c, const double* a, const double* b, uint64_t n, double* radiance, uint32_t* queries,
               bool launch, void* hip_stream);
 int lit_render(rayrs_scene* scene, const rayrs_camera* camera, const LitCall& c, double* out_rgb, uint32_t* queries);
+
+// The sky's table of the host scene's HDRI, built at the first call (radiance_sky_abi.cpp); `table` is a host pointer.
+SkyDev sky_host_table(rayrs_scene* scene);
+// T > 0.0 and finite: there is something to sample.
+bool sky_table_usable(rayrs_scene* scene);
+// The same with the device copy, uploaded at the first call (the scene's device is current).
+int sky_device_table(rayrs_scene* scene, SkyDev* out);
 
 }  // namespace rayrs

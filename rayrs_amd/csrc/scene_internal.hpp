@@ -128,6 +128,16 @@ struct rayrs_scene {
         std::vector<uint32_t> object_prim;
     };
     Lit lit;
+    // What the sky queries (radiance_sky_abi.cpp, include/rayrs_hip.h SKY SAMPLING) keep: the table of the host scene's HDRI
+    // (radiance_sky_table.h: M, C, A), built by the first sky call of any kind -- a host-only scene has one --, its total T, and
+    // the device copy, uploaded by the first call that launches.
+    struct Sky {
+        std::vector<double> table;
+        double total = 0.0;
+        bool built = false, uploaded = false;
+        rayrs::DevBuf d_table;
+    };
+    Sky sky;
     // Scenes whose walk tree is at most one record are rendered by local_pool.hip: every path resident in LDS.
     bool local_ok = false;
     rayrs::LocalScene local = {};

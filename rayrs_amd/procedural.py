@@ -47,6 +47,22 @@ def make_hdri(width: int = 1024, height: int = 512) -> np.ndarray:
     return np.clip(img, 0.0, 3.0).astype(np.float32)
 
 
+def make_studio_hdri(width: int = 1024, height: int = 512) -> np.ndarray:
+    """A dark studio: a black map with two bright rectangles in its upper half -- a window above the clip value 3 (the reference
+    clips its HDRI to [0, 3], rayrs/src/main.rs:43; the library clips it again) and a dimmer, warmer softbox on the other side
+    -- and nothing at all from three fifths of the way down, so that at least the bottom row of bilinear cells is empty.  The
+    environment-light counterpart of a small lamp: what BSDF sampling finds rarely and sky sampling finds at every bounce.
+    width >= 9 and height >= 5."""
+    if width < 9 or height < 5:
+        raise ValueError("the studio map is at least 9 x 5")
+    img = np.zeros((height, width, 3), dtype=np.float32)
+    r0, c0 = height // 5, width // 9
+    img[r0:max(r0 + 1, 2 * height // 5), c0:max(c0 + 1, 3 * width // 9)] = (8.0, 8.0, 6.0)
+    r1, c1 = 2 * height // 5, 5 * width // 9
+    img[r1:max(r1 + 1, 3 * height // 5), c1:max(c1 + 1, 7 * width // 9)] = (1.5, 1.25, 0.875)
+    return img
+
+
 def _icosahedron():
     t = (1.0 + np.sqrt(5.0)) / 2.0
     v = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
