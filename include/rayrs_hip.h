@@ -1151,6 +1151,45 @@ int rayrs_scene_sky_table(rayrs_scene* scene, double* cells /* (h-1)*(w-1), may 
 int rayrs_scene_sky_sample(rayrs_scene* scene, const double* u /* n*2 */, uint64_t n, double* dir /* n*3 */);
 int rayrs_scene_sky_density(rayrs_scene* scene, const double* dir /* n*3 */, uint64_t n, double* p);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * DIRECT-LIT FILMS.  A film whose passes are direct-lit: rayrs_film_create_direct makes a film of DIRECT LIGHTING's paths,
+ * rayrs_film_create_sky one of SKY SAMPLING's (lights, n_lights name the lamps, the sky is always on, n_lights == 0 is legal: the
+ * sky alone).  lights is a HOST array, copied at creation and fixed for the film's life.  The film is a rayrs_film like any
+ * other: every rayrs_film_* call and rayrs_history_push_film takes it.
+ *
+ * THE CONTRACT and THE CONTRACT PER TILE of the progressive film hold word for word with rayrs_render_direct (rayrs_render_sky)
+ * in rayrs_render's place, called with the same seed, max_bounces, sample_chunk = c, list, and the walk a render with the film's
+ * settings takes: after passes adding up to N_t samples in tile t, rayrs_film_read(RAYRS_OUT_F64) returns, bit for bit, that
+ * entry point's pixels for samples = N_t; RAYRS_OUT_F32 is that value converted; a film with tile_ranks > 1 holds its share's
+ * pixels and the rest read +0.  No arithmetic differs: the first chunk sum is assigned, later ones are added in chunk order, then
+ * sum * (1.0 / N), in the image form's resolve as in the film's records.  A film with an empty list (rayrs_film_create_direct,
+ * n_lights == 0) holds a plain film's records.  NOISE, ADAPTIVE PASSES, NOISE PLANE, FEATURES, DENOISER, GUIDED FILTER and
+ * TEMPORAL ACCUMULATION apply unchanged: they read the records and the first-hit features only.
+ *
+ * rayrs_film_status.rays is the closest-hit queries the film's paths made, shadow rays included: the sum over the share's
+ * in-image pixels of the `queries` plane rayrs_render_direct (rayrs_render_sky) returns at N_t; paths is the in-image pixels of
+ * the sampled tiles times n, summed over the passes.  pass_stats carries the pass's rays and paths, exact_walk as chosen, and
+ * one HIP-event time of all the pass's kernels in kernel_ms and total_ms; every field that describes the path pool, its rounds
+ * or the work counters is 0.
+ *
+ * Refusals at creation, before the device is touched.  RAYRS_INVALID_ARG: rayrs_film_create's of that group; lights == NULL with
+ * n_lights > 0; an index >= the scene's object count.  Then RAYRS_UNSUPPORTED: rayrs_film_create's of that group;
+ * n_lights > RAYRS_MAX_LIGHTS; an index naming a triangle; DIRECT LIGHTING's material rule; for rayrs_film_create_sky the empty
+ * table; c * (2 * max_bounces + 1) >= 2^32 (an item's query counter is 32 bits).  Then RAYRS_NO_DEVICE.
+ *
+ * A pass: a tile's items of one pass fit one launch of the waves, ceil(n / c) * 64 <= 2^20, that is n / c up to 16384; a longer
+ * pass is RAYRS_UNSUPPORTED and leaves the film unchanged.  The other pass rules are the progressive film's (n = 0, a closed
+ * film, the 2^30 sample cursor, an adaptive pass's n % c).
+ *
+ * The checkpoint image is the progressive film's, byte for byte the same format: the light list is NOT recorded in it, just as
+ * the scene and the camera are not.  Continuing a direct-lit film's image on a film with another list, or on a plain film (or a
+ * plain film's image on a direct-lit film), is the caller's error: rayrs_film_state_set cannot tell, and the result is the mean
+ * of samples of different estimators. */
+int rayrs_film_create_direct(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params,
+                             const uint32_t* lights /* HOST */, uint32_t n_lights, rayrs_film** out);
+int rayrs_film_create_sky(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params,
+                          const uint32_t* lights /* HOST */, uint32_t n_lights, rayrs_film** out);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -1165,7 +1204,8 @@ int rayrs_scene_sky_density(rayrs_scene* scene, const double* dir /* n*3 */, uin
  * rayrs_scene_irradiance_lit, their _launch forms and rayrs_render_lit (LIGHT SAMPLING), and with rayrs_scene_radiance_direct,
  * rayrs_scene_irradiance_direct, their _launch forms and rayrs_render_direct (DIRECT LIGHTING), and with rayrs_scene_radiance_sky,
  * rayrs_scene_irradiance_sky, their _launch forms, rayrs_render_sky, rayrs_scene_sky_table, rayrs_scene_sky_sample and
- * rayrs_scene_sky_density (SKY SAMPLING).  The layout table below begins with this
+ * rayrs_scene_sky_density (SKY SAMPLING), and with rayrs_film_create_direct and rayrs_film_create_sky (DIRECT-LIT FILMS).  The
+ * layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

@@ -38,6 +38,7 @@ SYMBOLS = [
     "rayrs_scene_irradiance_direct_launch", "rayrs_render_direct",
     "rayrs_scene_radiance_sky", "rayrs_scene_radiance_sky_launch", "rayrs_scene_irradiance_sky", "rayrs_scene_irradiance_sky_launch",
     "rayrs_render_sky", "rayrs_scene_sky_table", "rayrs_scene_sky_sample", "rayrs_scene_sky_density",
+    "rayrs_film_create_direct", "rayrs_film_create_sky",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -288,7 +289,9 @@ def lib():
                                              C.c_uint32, vp, vp]),
                        ("rayrs_scene_sky_table", [vp, vp, vp]),
                        ("rayrs_scene_sky_sample", [vp, vp, C.c_uint64, vp]),
-                       ("rayrs_scene_sky_density", [vp, vp, C.c_uint64, vp])):
+                       ("rayrs_scene_sky_density", [vp, vp, C.c_uint64, vp]),
+                       ("rayrs_film_create_direct", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, C.POINTER(vp)]),
+                       ("rayrs_film_create_sky", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, C.POINTER(vp)])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):

@@ -836,19 +836,36 @@ def denoise_guided(color, variance, normal=None, albedo=None, depth=None, levels
 class Film:
     """A progressive film (include/rayrs_hip.h rayrs_film_*): samples are added to it pass by pass, and after passes
     that add up to N samples image() is, bit for bit, render(scene, camera, N, sample_chunk=sample_chunk) with the same
-    seed, bounces, tile share and walk.  The scene must outlive the film."""
+    seed, bounces, tile share and walk.  The scene must outlive the film.
+
+    With lights=[...] and direct=True the film is direct-lit (DIRECT-LIT FILMS): its passes take a shadow sample per diffuse
+    bounce towards the list's lamps, and towards the sky too if SKY is in the list, and image() is
+    render_lit(scene, camera, N, lights, direct=True, sample_chunk=sample_chunk), bit for bit.  The list is fixed for the
+    film's life (film.lights); everything else a film does works on such a film unchanged."""
 
     def __init__(self, scene: Scene, camera: Camera, sample_chunk: int = 4, max_bounces: int = 50, seed: int = 0x5EED,
-                 tile_rank: int = 0, tile_ranks: int = 1, fast_traversal: bool = False):
+                 tile_rank: int = 0, tile_ranks: int = 1, fast_traversal: bool = False, lights=None, direct: bool = False):
+        if direct and lights is None:
+            raise ValueError("direct=True needs a light list (lights=[...])")
+        if lights is not None and not direct:
+            raise ValueError("a film with a light list is direct-lit: pass direct=True (the one-sample mix has no film)")
         self._L, self._h = scene._L, None
         self.scene, self.camera = scene, camera
+        self.lights = None if lights is None else [int(v) for v in _light_list(lights)]
         p = _ffi.FilmParams()
         p.sample_chunk, p.max_bounces, p.seed = int(sample_chunk), int(max_bounces), int(seed)
         p.tile_rank, p.tile_ranks, p.fast_traversal = int(tile_rank), int(tile_ranks), 1 if fast_traversal else 0
         self.sample_chunk = int(sample_chunk) or 4
         self.tile_rank, self.tile_ranks = int(tile_rank), int(tile_ranks) or 1
         h = C.c_void_p()
-        _ffi.check(self._L.rayrs_film_create(scene._h, C.byref(camera.desc), C.byref(p), C.byref(h)), "rayrs_film_create")
+        if lights is None:
+            _ffi.check(self._L.rayrs_film_create(scene._h, C.byref(camera.desc), C.byref(p), C.byref(h)), "rayrs_film_create")
+        else:  # (the rule render_lit chooses its entry point by: SKY in the list is the sky, the rest the lamps)
+            lamps = _light_list(lights)
+            name = "rayrs_film_create_sky" if (lamps == SKY).any() else "rayrs_film_create_direct"
+            lamps = lamps[lamps != SKY]
+            _ffi.check(getattr(self._L, name)(scene._h, C.byref(camera.desc), C.byref(p), lamps.ctypes.data if len(lamps) else None,
+                                              len(lamps), C.byref(h)), name)
         self._h = h
 
     def render(self, n: int) -> dict:

@@ -1,6 +1,7 @@
 // film_abi.cpp -- the progressive film of include/rayrs_hip.h (rayrs_film_*): a film's lifetime, a pass as a render of a
 // sample window whose chunk sums go to the film's records (render.cpp render_enqueue, film.hip), the frame and the status
-// read from the records, and the checkpoint image.
+// read from the records, and the checkpoint image.  A direct-lit film (DIRECT-LIT FILMS) differs in who makes a pass's chunk
+// sums: film_direct.hip's kernels on the scene's radiance scratch, launch by launch (film_pass_lit).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,7 +14,9 @@
 #include "denoise_host.hpp"
 #include "features_host.hpp"
 #include "film.h"
+#include "film_direct_kernels.h"
 #include "film_host.hpp"
+#include "radiance_lit_host.hpp"
 #include "scene_internal.hpp"
 
 using namespace rayrs;
@@ -63,6 +66,18 @@ struct rayrs_film {
     uint32_t feat_samples = 0;  // 0 = none yet
     DevBuf d_var;               // the noise plane (rayrs_film_noise, rayrs_film_denoise_guided), grown on demand
     DenoiseBufs filter;         // what either filter works in
+    // DIRECT-LIT FILMS: the film's passes are direct-lit (rayrs_film_create_direct), with the sky among the lights
+    // (rayrs_film_create_sky); the list as given, fixed for the film's life.  Not part of the checkpoint image.
+    bool lit = false, sky = false;
+    std::vector<uint32_t> lights;
+    DevBuf d_lit_counts;  // one FilmDirectCounts, read once per pass
+    Event lit_ev[2];      // around a pass's launches
+    LitCall lit_call(uint32_t n) const {
+        return LitCall{LIT_START_PIXEL, n, prm.max_bounces, prm.sample_chunk, 0.0, prm.seed, 0u, prm.fast_traversal, lights.data(),
+                       (uint32_t)lights.size(), true, sky};
+    }
+    // a lit pass of n samples is too long: a tile's items of one pass do not fit one launch
+    bool lit_pass_too_long(uint32_t n) const { return lit && ((uint64_t)n + prm.sample_chunk - 1u) / prm.sample_chunk * 64u > RADIANCE_LAUNCH_ITEMS; }
     size_t record_bytes() const { return n_tiles() * FILM_TILE_DOUBLES * sizeof(double); }
     size_t n_tiles() const { return (size_t)share.tiles_x * share.tiles_y; }
     size_t count_bytes() const { return n_tiles() * sizeof(uint32_t); }
@@ -103,7 +118,9 @@ static int film_select(rayrs_film* f, uint32_t n, uint32_t cap, double tau, bool
 
 // One pass of n samples: over the list film_select has just made (n_list tiles, each from its own N_t), or, n_list == 0,
 // over the whole share of a uniform film from `samples`.
+static int film_pass_lit(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_render_stats* st);
 static int film_pass(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_render_stats* st) {
+    if (film->lit) return film_pass_lit(film, n, n_list, st);
     const uint32_t c = film->prm.sample_chunk;
     rayrs_render_params p;
     std::memset(&p, 0, sizeof(p));
@@ -129,6 +146,84 @@ static int film_pass(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_render
     return RAYRS_OK;
 }
 
+// The same pass of a direct-lit film.  Whole tiles, as many as fit RADIANCE_LAUNCH_ITEMS items, per launch of the direct or the
+// sky wave on the scene's radiance scratch (the queries' ordering rule, radiance_lit_abi.cpp lit_scratch_begin); behind each
+// launch, on the same stream, its counts and film_accumulate_kernel over its tile range, as behind a segment of a plain pass.
+// The host waits once, for the pass's two counters.
+static int film_pass_lit(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_render_stats* st) {
+    rayrs_scene* scene = film->scene;
+    const uint32_t c = film->prm.sample_chunk;
+    const LitCall call = film->lit_call(n);
+    const LightsDev lights = lights_resolve(scene, call);
+    const LightSlotsDev slots = direct_slots(scene, call);
+    SkyDev sky;
+    std::memset(&sky, 0, sizeof(sky));
+    if (film->sky) RAYRS_TRY(sky_device_table(scene, &sky));
+    const FrameWalk walk = frame_walk(scene, &film->camera, film->prm.fast_traversal);  // the walk a render with these settings takes
+    const SceneDev sc = make_scene_dev(scene, walk.exact || walk.use_local);
+    const CameraDev cam = make_camera_dev(&film->camera);
+    const hipStream_t stream = nullptr;
+    RadianceDev rd;
+    std::memset(&rd, 0, sizeof(rd));
+    RAYRS_TRY(lit_scratch_begin(scene, sc, stream, &rd));
+    rd.samples = n, rd.max_bounces = film->prm.max_bounces, rd.seed = film->prm.seed;
+    rd.chunk = c, rd.chunks = (n + c - 1u) / c;  // (n and c are below 2^30)
+    const uint32_t n_tiles = n_list ? n_list : film->share.n_local_tiles;
+    FilmStartDev fs;
+    std::memset(&fs, 0, sizeof(fs));
+    fs.share = film->share, fs.share.n_local_tiles = n_tiles;
+    fs.tile_list = n_list ? film->d_list.as<TileRef>() : nullptr;
+    fs.sample0 = n_list ? 0u : (uint32_t)film->samples, fs.spp = n;
+    RenderDev rp;  // what film_accumulate_kernel reads of it
+    std::memset(&rp, 0, sizeof(rp));
+    rp.spp = n, rp.sample0 = fs.sample0, rp.max_bounces = rd.max_bounces, rp.seed = rd.seed;
+    rp.chunk = c, rp.nchunks = rd.chunks;
+    rp.tile_rank = fs.share.tile_rank, rp.tile_ranks = fs.share.tile_ranks;
+    rp.tiles_x = fs.share.tiles_x, rp.tiles_y = fs.share.tiles_y, rp.n_local_tiles = n_tiles;
+    rp.total_items = (uint64_t)n_tiles * rp.nchunks * 64u;
+    rp.inv_nchunks = 1.0 / (double)rp.nchunks, rp.inv_tiles_x = 1.0 / (double)rp.tiles_x;
+    rp.out_format = RAYRS_OUT_F64;
+    rp.partial = rd.partial;
+    rp.tile_list = fs.tile_list;
+    FilmPassDev fp;
+    std::memset(&fp, 0, sizeof(fp));
+    fp.rec = film->d_rec.as<double>();
+    fp.first = film->samples == 0 ? 1u : 0u;
+    fp.full_chunks = n / c;
+    fp.tile_n = film->d_tile_n.as<uint32_t>();
+    fp.list = fs.tile_list, fp.n_list = n_list;
+    FilmDirectCounts* counts = film->d_lit_counts.as<FilmDirectCounts>();
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(FilmDirectCounts), stream));
+    HIP_TRY(hipEventRecord(film->lit_ev[0], stream));
+    const uint32_t per_launch = (uint32_t)(RADIANCE_LAUNCH_ITEMS / (64u * (uint64_t)rd.chunks));  // (>= 1: lit_pass_too_long)
+    for (uint32_t lt0 = 0; lt0 < n_tiles; lt0 += per_launch) {
+        const uint32_t n_lt = n_tiles - lt0 < per_launch ? n_tiles - lt0 : per_launch;
+        rd.n = n_lt * 64u;
+        fs.lt0 = lt0;
+        rp.partial_item0 = (uint64_t)lt0 * rp.nchunks * 64u;
+        if (rd.max_bounces == 0u) {  // the loop runs no turn: +0 and no query, whatever the scene
+            HIP_TRY(hipMemsetAsync(rd.partial, 0, (size_t)rd.n * rd.chunks * 3u * sizeof(double), stream));
+        } else {
+            HIP_TRY(hipMemsetAsync(rd.cursor, 0, sizeof(unsigned long long), stream));
+            HIP_TRY(launch_film_direct(scene->flat.compact, sc, rd, fs, lights, slots, film->sky ? &sky : nullptr, cam, scene->cu_count, stream));
+        }
+        HIP_TRY(launch_film_direct_count(rd, fs, cam, rd.max_bounces != 0u ? 1u : 0u, counts, stream));
+        HIP_TRY(launch_film_accumulate(cam, rp, fp, lt0, n_lt, stream));
+    }
+    HIP_TRY(hipEventRecord(film->lit_ev[1], stream));
+    RAYRS_TRY(lit_scratch_end(scene, stream));
+    FilmDirectCounts got;
+    HIP_TRY(film->d_lit_counts.download(&got, sizeof(got)));  // (the pass's one wait)
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, film->lit_ev[0], film->lit_ev[1]));
+    std::memset(st, 0, sizeof(*st));
+    st->rays = got.queries, st->paths = got.pixels * n;
+    st->exact_walk = sc.exact;
+    st->kernel_ms = ms, st->total_ms = ms;  // the waves' launches, and all of the pass's kernels: one HIP-event interval
+    film->rays += st->rays, film->paths += st->paths;
+    return RAYRS_OK;
+}
+
 static int film_stage(rayrs_film* f) {
     if (!f->has_stage) {
         HIP_TRY(f->h_stage.alloc(STAGE_BYTES));
@@ -137,10 +232,8 @@ static int film_stage(rayrs_film* f) {
     return RAYRS_OK;
 }
 
-extern "C" {
-
-int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, rayrs_film** out) {
-    RAYRS_GUARDED({
+// rayrs_film_create (lit == nullptr), or a direct-lit film of lit's list: its refusals join the plain film's, group by group.
+static int film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, const LitCall* lit, rayrs_film** out) {
     if (!scene || !camera || !params || !out) return RAYRS_INVALID_ARG;
     *out = nullptr;
     rayrs_film_params prm = *params;
@@ -148,9 +241,15 @@ int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayr
     if (prm.tile_ranks == 0 && prm.tile_rank == 0) prm.tile_ranks = 1;
     if (camera->x_pixels == 0 || camera->y_pixels == 0) return RAYRS_INVALID_ARG;
     if (prm.tile_ranks == 0 || prm.tile_rank >= prm.tile_ranks || prm.fast_traversal > 1u || prm.pad != 0u) return RAYRS_INVALID_ARG;
+    if (lit) RAYRS_TRY(lit_list_invalid(scene, *lit));
     if (camera->x_pixels > 65535u || camera->y_pixels > 65535u) return RAYRS_UNSUPPORTED;
     if (prm.max_bounces > 8000u) return RAYRS_UNSUPPORTED;
     if (prm.sample_chunk > SLOT_SAMPLE_MASK) return RAYRS_UNSUPPORTED;  // not one full chunk fits the 30-bit sample cursor
+    if (lit) {
+        RAYRS_TRY(lit_list_unsupported(scene, *lit));
+        // (an item is one chunk of at most 2 * max_bounces + 1 queries a sample, counted in 32 bits)
+        if ((uint64_t)prm.sample_chunk * (2ull * prm.max_bounces + 1u) >= (1ull << 32)) return RAYRS_UNSUPPORTED;
+    }
     if (scene->device < 0) return RAYRS_NO_DEVICE;
     std::unique_ptr<rayrs_film> f(new rayrs_film());
     f->scene = scene;
@@ -165,8 +264,41 @@ int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayr
     HIP_TRY(f->d_select.reserve(sizeof(FilmSelect)));
     HIP_TRY(f->h_word.alloc(sizeof(uint32_t)));
     HIP_TRY(f->d_counts.reserve(sizeof(FilmCounts)));
+    if (lit) {
+        f->lit = true, f->sky = lit->sky;
+        f->lights.assign(lit->lights, lit->lights + lit->n_lights);
+        HIP_TRY(f->d_lit_counts.reserve(sizeof(FilmDirectCounts)));
+        HIP_TRY(f->lit_ev[0].create());
+        HIP_TRY(f->lit_ev[1].create());
+    }
     *out = f.release();
     return RAYRS_OK;
+}
+
+// the list of a direct-lit film's creation as the light-list entry points describe a call (the film's own settings join it later)
+static LitCall film_list(const uint32_t* lights, uint32_t n_lights, bool sky) {
+    return LitCall{LIT_START_PIXEL, 0u, 0u, 0u, 0.0, 0u, 0u, 0u, lights, n_lights, true, sky};
+}
+
+extern "C" {
+
+int rayrs_film_create(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, rayrs_film** out) {
+    RAYRS_GUARDED({ return film_create(scene, camera, params, nullptr, out); })
+}
+
+int rayrs_film_create_direct(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, const uint32_t* lights,
+                             uint32_t n_lights, rayrs_film** out) {
+    RAYRS_GUARDED({
+    const LitCall lit = film_list(lights, n_lights, false);
+    return film_create(scene, camera, params, &lit, out);
+    })
+}
+
+int rayrs_film_create_sky(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, const uint32_t* lights,
+                          uint32_t n_lights, rayrs_film** out) {
+    RAYRS_GUARDED({
+    const LitCall lit = film_list(lights, n_lights, true);
+    return film_create(scene, camera, params, &lit, out);
     })
 }
 
@@ -181,7 +313,7 @@ int rayrs_film_render(rayrs_film* film, uint32_t n, rayrs_render_stats* pass_sta
     RAYRS_GUARDED({
     if (!film || n == 0 || film->closed) return RAYRS_INVALID_ARG;
     const uint32_t c = film->prm.sample_chunk;
-    if (n > SLOT_SAMPLE_MASK) return RAYRS_UNSUPPORTED;
+    if (n > SLOT_SAMPLE_MASK || film->lit_pass_too_long(n)) return RAYRS_UNSUPPORTED;
     if (film->uniform && (film->samples > SLOT_SAMPLE_MASK || n > SLOT_SAMPLE_MASK - (uint32_t)film->samples)) return RAYRS_UNSUPPORTED;
     RAYRS_TRY(film_enter(film));
     uint32_t n_list = 0;
@@ -206,6 +338,7 @@ int rayrs_film_render_adaptive(rayrs_film* film, uint32_t n, double tau, uint32_
     RAYRS_GUARDED({
     if (!film || n == 0 || film->closed || !(tau >= 0.0) || !std::isfinite(tau)) return RAYRS_INVALID_ARG;
     if (n % film->prm.sample_chunk != 0u) return RAYRS_INVALID_ARG;
+    if (film->lit_pass_too_long(n)) return RAYRS_UNSUPPORTED;
     RAYRS_TRY(film_enter(film));
     const uint32_t cap = max_tile_samples != 0u && max_tile_samples < SLOT_SAMPLE_MASK ? max_tile_samples : SLOT_SAMPLE_MASK;
     uint32_t active = 0;

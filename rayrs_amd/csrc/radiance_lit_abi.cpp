@@ -52,6 +52,8 @@ bool direct_list_unsupported(rayrs_scene* scene, const LitCall& c) {
     return false;
 }
 
+}  // namespace
+
 // The list as the depth-first slots a walk answers with (radiance_direct_kernels.h LightSlotsDev).
 LightSlotsDev direct_slots(rayrs_scene* scene, const LitCall& c) {
     LightSlotsDev out;
@@ -61,21 +63,18 @@ LightSlotsDev direct_slots(rayrs_scene* scene, const LitCall& c) {
     return out;
 }
 
-// The refusals that need no device, in the header's order: RADIANCE QUERY's with the list's among them.  `extra_invalid` and
-// `extra_unsupported` are what the image form adds to the two groups (the camera's).  A direct call can make 2 * max_bounces + 1
-// queries per path, and has its material rule.
-int lit_check(rayrs_scene* scene, const void* a, const void* b, const void* radiance, const void* queries, const LitCall& c,
-              bool extra_invalid = false, bool extra_unsupported = false) {
-    if (!scene || !a || !b || (!radiance && !queries)) return RAYRS_INVALID_ARG;
-    if (c.samples == 0u || c.fast_traversal > 1u || extra_invalid) return RAYRS_INVALID_ARG;
+// lit_check's two pieces about the list, which the direct-lit films' creation takes as they are (film_abi.cpp): what of it is
+// RAYRS_INVALID_ARG ...
+int lit_list_invalid(rayrs_scene* scene, const LitCall& c) {
     if (c.n_lights > 0u && !c.lights) return RAYRS_INVALID_ARG;
     const size_t n_objects = scene->flat.prim_object.size();
     for (uint32_t k = 0; k < c.n_lights; k++)
         if (c.lights[k] >= n_objects) return RAYRS_INVALID_ARG;
-    if (c.samples > SLOT_SAMPLE_MASK || c.max_bounces > 8000u || extra_unsupported) return RAYRS_UNSUPPORTED;
-    const uint64_t path_queries = c.direct ? 2ull * c.max_bounces + 1u : c.max_bounces;
-    if ((uint64_t)c.samples * path_queries >= (1ull << 32)) return RAYRS_UNSUPPORTED;
-    if (radiance_chunks(c.samples, c.sample_chunk) > RADIANCE_LAUNCH_ITEMS) return RAYRS_UNSUPPORTED;
+    return RAYRS_OK;
+}
+// ... and, of a list that is not, what is RAYRS_UNSUPPORTED: too many lights, a triangle, DIRECT LIGHTING's material rule, and
+// SKY SAMPLING's empty table (nothing to sample).
+int lit_list_unsupported(rayrs_scene* scene, const LitCall& c) {
     if (c.n_lights > RAYRS_MAX_LIGHTS) return RAYRS_UNSUPPORTED;
     if (c.n_lights > 0u) {
         const std::vector<uint32_t>& map = lit_object_prim(scene);
@@ -83,10 +82,30 @@ int lit_check(rayrs_scene* scene, const void* a, const void* b, const void* radi
             if ((lit_prim_tag(scene, map[c.lights[k]]) & 3u) == PRIM_TRIANGLE) return RAYRS_UNSUPPORTED;
         if (c.direct && direct_list_unsupported(scene, c)) return RAYRS_UNSUPPORTED;
     }
-    if (c.sky && !sky_table_usable(scene)) return RAYRS_UNSUPPORTED;  // SKY SAMPLING: an empty table, nothing to sample
+    if (c.sky && !sky_table_usable(scene)) return RAYRS_UNSUPPORTED;
+    return RAYRS_OK;
+}
+
+namespace {
+
+// The refusals that need no device, in the header's order: RADIANCE QUERY's with the list's among them.  `extra_invalid` and
+// `extra_unsupported` are what the image form adds to the two groups (the camera's).  A direct call can make 2 * max_bounces + 1
+// queries per path, and has its material rule.
+int lit_check(rayrs_scene* scene, const void* a, const void* b, const void* radiance, const void* queries, const LitCall& c,
+              bool extra_invalid = false, bool extra_unsupported = false) {
+    if (!scene || !a || !b || (!radiance && !queries)) return RAYRS_INVALID_ARG;
+    if (c.samples == 0u || c.fast_traversal > 1u || extra_invalid) return RAYRS_INVALID_ARG;
+    RAYRS_TRY(lit_list_invalid(scene, c));
+    if (c.samples > SLOT_SAMPLE_MASK || c.max_bounces > 8000u || extra_unsupported) return RAYRS_UNSUPPORTED;
+    const uint64_t path_queries = c.direct ? 2ull * c.max_bounces + 1u : c.max_bounces;
+    if ((uint64_t)c.samples * path_queries >= (1ull << 32)) return RAYRS_UNSUPPORTED;
+    if (radiance_chunks(c.samples, c.sample_chunk) > RADIANCE_LAUNCH_ITEMS) return RAYRS_UNSUPPORTED;
+    RAYRS_TRY(lit_list_unsupported(scene, c));
     if (scene->device < 0) return RAYRS_NO_DEVICE;
     return RAYRS_OK;
 }
+
+}  // namespace
 
 // The table of a checked list (radiance_lit_kernels.h LightDev): the primitive record's f64 values as they are, and the two
 // values a light's sample and density read on top, each one correctly rounded operation of the header's.
@@ -115,6 +134,37 @@ LightsDev lights_resolve(rayrs_scene* scene, const LitCall& c) {
     return out;
 }
 
+// What every launch on the scene's radiance scratch begins with: the scratch and the stack strip reserved, `stream` made to wait
+// for the last launch that used them (the queries' ordering rule), and rd's thresholds, cursor, item sums, item query counts and
+// spill strip filled in.  lit_scratch_end, behind the last launch, records the event the next user waits for.
+int lit_scratch_begin(rayrs_scene* scene, const SceneDev& sc, hipStream_t stream, RadianceDev* rd) {
+    rayrs_scene::Queries& strip = scene->queries;
+    rayrs_scene::Radiance& own = scene->radiance;
+    if (sc.stack_depth > sc.stack_lds) HIP_TRY(strip.d_stack_spill.reserve(stack_spill_words(sc, QUERY_LAUNCH_RAYS) * sizeof(uint32_t)));
+    HIP_TRY(own.d_scratch.reserve(RADIANCE_SCRATCH_BYTES));
+    if (!strip.has_event) {
+        HIP_TRY(strip.ev_done.create());
+        strip.has_event = true;
+    }
+    if (strip.strip_in_use) HIP_TRY(hipStreamWaitEvent(stream, strip.ev_done, 0));
+    rd->refill_below = own.refill_below ? own.refill_below : RADIANCE_REFILL_BELOW;
+    rd->shade_at = own.shade_at ? own.shade_at : RADIANCE_SHADE_AT;
+    rd->leaf_min = own.leaf_min ? own.leaf_min : RADIANCE_LEAF_MIN;
+    char* scratch = own.d_scratch.as<char>();
+    rd->cursor = reinterpret_cast<unsigned long long*>(scratch);
+    rd->partial = reinterpret_cast<double*>(scratch + RADIANCE_CURSOR_BYTES);
+    rd->partial_queries = reinterpret_cast<uint32_t*>(scratch + RADIANCE_CURSOR_BYTES + RADIANCE_LAUNCH_ITEMS * 24u);
+    rd->spill = strip.d_stack_spill.as<uint32_t>();
+    return RAYRS_OK;
+}
+int lit_scratch_end(rayrs_scene* scene, hipStream_t stream) {
+    HIP_TRY(hipEventRecord(scene->queries.ev_done, stream));
+    scene->queries.strip_in_use = true;
+    return RAYRS_OK;
+}
+
+namespace {
+
 // The batch, whole rays of at most RADIANCE_LAUNCH_ITEMS items per launch, all on `stream`, as radiance_abi.cpp's
 // radiance_enqueue: the same scratch, the same strip and the same ordering rule.  LIT_START_PIXEL: a and b are null and the
 // rays are the camera's pixels index_base + i.
@@ -128,32 +178,15 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
         if (queries) HIP_TRY(hipMemsetAsync(queries, 0, n * sizeof(uint32_t), stream));
         return RAYRS_OK;
     }
-    rayrs_scene::Queries& strip = scene->queries;
-    rayrs_scene::Radiance& own = scene->radiance;
-    if (sc.stack_depth > sc.stack_lds) HIP_TRY(strip.d_stack_spill.reserve(stack_spill_words(sc, QUERY_LAUNCH_RAYS) * sizeof(uint32_t)));
-    HIP_TRY(own.d_scratch.reserve(RADIANCE_SCRATCH_BYTES));
-    if (!strip.has_event) {
-        HIP_TRY(strip.ev_done.create());
-        strip.has_event = true;
-    }
-    if (strip.strip_in_use) HIP_TRY(hipStreamWaitEvent(stream, strip.ev_done, 0));
-
     LightSlotsDev slots;
     std::memset(&slots, 0, sizeof(slots));
     if (c.direct) slots = direct_slots(scene, c);
     RadianceDev rd;
     std::memset(&rd, 0, sizeof(rd));
+    RAYRS_TRY(lit_scratch_begin(scene, sc, stream, &rd));
     rd.samples = c.samples, rd.max_bounces = c.max_bounces, rd.irradiance = c.start == LIT_START_POINT ? 1u : 0u;
     rd.chunk = radiance_chunk(c.samples, c.sample_chunk), rd.chunks = radiance_chunks(c.samples, c.sample_chunk);
-    rd.refill_below = own.refill_below ? own.refill_below : RADIANCE_REFILL_BELOW;
-    rd.shade_at = own.shade_at ? own.shade_at : RADIANCE_SHADE_AT;
-    rd.leaf_min = own.leaf_min ? own.leaf_min : RADIANCE_LEAF_MIN;
     rd.seed = c.seed, rd.bias = c.bias;
-    char* scratch = own.d_scratch.as<char>();
-    rd.cursor = reinterpret_cast<unsigned long long*>(scratch);
-    rd.partial = reinterpret_cast<double*>(scratch + RADIANCE_CURSOR_BYTES);
-    rd.partial_queries = reinterpret_cast<uint32_t*>(scratch + RADIANCE_CURSOR_BYTES + RADIANCE_LAUNCH_ITEMS * 24u);
-    rd.spill = strip.d_stack_spill.as<uint32_t>();
     const uint64_t per_launch = RADIANCE_LAUNCH_ITEMS / rd.chunks;  // (>= 1: lit_check)
     for (uint64_t base = 0; base < n; base += per_launch) {
         rd.n = (uint32_t)(n - base < per_launch ? n - base : per_launch);
@@ -166,9 +199,7 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
         else if (c.direct) HIP_TRY(launch_radiance_direct(scene->flat.compact, sc, rd, lights, slots, cam, c.start, scene->cu_count, stream));
         else HIP_TRY(launch_radiance_lit(scene->flat.compact, sc, rd, lights, cam, c.start, scene->cu_count, stream));
     }
-    HIP_TRY(hipEventRecord(strip.ev_done, stream));
-    strip.strip_in_use = true;
-    return RAYRS_OK;
+    return lit_scratch_end(scene, stream);
 }
 
 // The host form: upload (rays and points), launch on the null stream, wait, download.

@@ -1,227 +1,21 @@
 // radiance_sky.hip -- the radiance queries with the sky among the lights of direct lighting (include/rayrs_hip.h SKY SAMPLING).
-// A unit of its own beside radiance_direct.hip, whose wave it restates: one path per lane from its first ray to its last, in
-// registers, fused with the closest-hit walk in its resumable pieces; finished lanes are shaded, idle lanes refilled from one
-// device-wide cursor, one record or one leaf group per step; a lane walks TWO rays per diffuse bounce, one after the other, the
-// shadow ray and then the continuation, and keeps between them the continuation's direction, the shadow sample's worth and the
-// roulette's word.  What differs: the shadow ray's direction may come from the sky's table (radiance_sky_table.h), a shadow ray
-// that misses is credited the background, every diffuse bounce has a shadow sample (the list may be empty, the sky is always
-// there), and the background a path's own ray escapes to is weighted by w.  p_env of the continuation is evaluated at the
-// bounce, so the state a lane carries is the direct kernel's.
+// A unit of its own beside radiance_direct.hip: the kernels of the queries' three starts, the resolve and the launch.  The wave
+// itself, and what sets it apart from the direct wave, is radiance_sky_wave.h's, which the sky-lit film's kernels
+// (film_direct.hip) run with a start of their own.
 #include <hip/hip_runtime.h>
 
 #include "device_path.h"
 #include "launch_dispatch.h"
-#include "radiance_sky_device.h"
 #include "radiance_sky_kernels.h"
+#include "radiance_sky_wave.h"
 
 namespace rayrs {
 
-// The start of sample s of ray (point, pixel) `ray`: its RNG and its first ray.  LIT_START_POINT is IRRADIANCE, DIRECT's virtual
-// bounce, whatever K is: `first` is its shadow sample and the weight of what the first ray meets (a listed object, or the sky).
-struct SkyStart {
-    Rng rng;
-    V3 o, d;
-    DirectBounce first;
-};
-template <int START>
-RR_DEV SkyStart sky_path_start(const RadianceDev& rd, const LightsDev& lights, const SkyDev& sky, const CameraDev& cam, uint32_t ray,
-                               uint32_t s) {
-    Rng rng;
-    V3 o, d;
-    DirectBounce first;
-    first.shadow = false, first.l_s = mk(0.0, 0.0, 1.0), first.credit = mk(0.0, 0.0, 0.0), first.w_next = 1.0;
-    if (START == LIT_START_PIXEL) {
-        const uint32_t pix = (uint32_t)rd.index_base + ray;  // (the image's pixels: below 2^32)
-        const uint32_t row = pix / cam.W, col = pix - row * cam.W;
-        rng = Rng{sample_key(rd.seed, cam, row, col, s), 0};
-        sample_ray(cam, row, col, rng, o, d);
-        return SkyStart{rng, o, d, first};
-    }
-    const double* pa = rd.a + (size_t)ray * 3u;
-    const double* pb = rd.b + (size_t)ray * 3u;
-    const V3 a = mk(pa[0], pa[1], pa[2]), b = mk(pb[0], pb[1], pb[2]);
-    rng = Rng{rr_path_key(rd.seed, rd.index_base + ray, (uint64_t)s), 0};
-    if (START == LIT_START_POINT) {  // IRRADIANCE's ray (radiance.hip radiance_sample_start)
-        o = v_add(a, v_scale(b, rd.bias));
-        V3 e1, e2;
-        v_onb(b, e1, e2);
-        const double u = rng.next();
-        const double phi = 2.0 * RR_PI * rng.next();
-        const double su = rr_sqrt(u);
-        const rr_sincos_t sc_phi = rr_sincos(phi);
-        const double x = sc_phi.c * su;
-        const double y = sc_phi.s * su;
-        const double z = rr_sqrt(1.0 - u);
-        d = v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(b, z));
-        first = sky_bounce(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), o, b, d, rng, lights, sky);
-    } else {
-        o = a, d = b;
-    }
-    return SkyStart{rng, o, d, first};
-}
-
-// radiance_direct.hip radiance_direct_kernel's wave and its termination argument, turn for turn: a lane that holds a path either
-// walks (its path's ray or a shadow ray) or waits to be shaded, every shade turn ends a ray, and a path has at most
-// 2 * max_bounces + 1 of them.  A chunk's sum is made in this one lane in sample order and stored once, so no f64 sum depends on
-// which lanes did what when.  The sky's table is read inside sky_bounce only, by indices its searches keep inside the table.
+// radiance_sky_wave.h's wave, its paths started by the queries: a batch's rays, points or pixels.
 template <bool COMPACT, bool EXACT, int START>
-__global__ void __launch_bounds__(256) radiance_sky_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, SkyDev sky,
-                                                           CameraDev cam) {
+__global__ void __launch_bounds__(256) radiance_sky_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    const LaneStack stack = lane_stack(lds_stack, rd.spill, sc);
-    const unsigned long long n_items = (unsigned long long)rd.n * rd.chunks;
-
-    bool has = false;  // the lane holds a path: walking while tv.cur != TRAV_DONE, then finished (waiting to be shaded)
-    uint32_t item = 0, ray = 0;
-    uint32_t s = 0, s_end = 0;  // the path's sample, the chunk's end
-    uint32_t bounce = 0, queries = 0;
-    Rng rng{0, 0};
-    V3 o = mk(0, 0, 0), d = mk(0, 0, 1);
-    V3 thr = mk(1, 1, 1), light = mk(0, 0, 0), sum = mk(0, 0, 0);
-    V3 first = mk(0, 0, 0);  // LIT_START_POINT: the virtual bounce's credit, added to the path's value at its end
-    // the ray the lane walks is a shadow ray; after it the path goes on along l (else the sample ends); the shadow sample's worth
-    bool shadow = false, goes_on = false;
-    V3 l = mk(0, 0, 1), credit = mk(0, 0, 0);
-    double w = 1.0;  // the weight of a listed object's emission met by the path's ray
-    Trav tv;
-    tv.inv = mk(0, 0, 0), tv.best_t = 0, tv.best_prim = 0xffffffffu, tv.cur = TRAV_DONE, tv.sp = 0;
-    bool no_more = false;  // wave-uniform: the cursor ran off the launch's items
-
-    for (;;) {
-        const bool live = has && tv.cur != TRAV_DONE;
-        const bool at_int = live && trav_at_interior(tv);
-        const bool at_leaf = live && !trav_at_interior(tv);
-        const bool fin = has && tv.cur == TRAV_DONE;
-        const int n_int = __popcll(__ballot(at_int));
-        const int n_leaf = __popcll(__ballot(at_leaf));
-        const int n_fin = __popcll(__ballot(fin));
-        const int n_walk = n_int + n_leaf;
-        const bool do_shade = n_fin > 0 && (n_fin >= (int)rd.shade_at || n_walk == 0);
-        const bool do_refill = !no_more && n_walk < (int)rd.refill_below && (do_shade || n_walk + n_fin < 64);
-        if (do_shade || do_refill) {
-            bool new_sample = false, new_ray = false;
-            // ---- shade: for every finished lane, the end of its shadow ray or one turn of radiance()'s loop (lib.rs:526-556)
-            if (do_shade && fin) {
-                bool ended = true;
-                V3 result = light;
-                if (shadow) {  // the shadow sample's credit, then the continuation or the sample's end (the roulette's word)
-                    const bool missed = tv.best_prim == 0xffffffffu;
-                    if (missed || direct_listed(lights, slots, tv.best_prim)) {  // the sky's light, or a listed object's
-                        V3 source;
-                        if (missed) {
-                            source = background(sc, d);
-                        } else {
-                            const PrimRec<COMPACT> rec = load_prim<COMPACT>(sc.prims, tv.best_prim);
-                            const double* emit = sc.surfaces[rec.tag() >> 8].emit;
-                            source = mk(emit[0], emit[1], emit[2]);
-                        }
-                        const V3 worth = v_mul(credit, source);
-                        if (START == LIT_START_POINT && bounce == 0u) first = worth;  // (the path has not met a surface yet)
-                        else light = v_add(light, worth);
-                    }
-                    shadow = false;
-                    result = light;
-                    if (goes_on) d = l, ended = false, new_ray = true;
-                } else if (tv.best_prim != 0xffffffffu) {
-                    const PrimRec<COMPACT> rec = load_prim<COMPACT>(sc.prims, tv.best_prim);
-                    const V3 position = hit_position(o, d, tv.best_t);
-                    const HitPoint hp = hit_point<COMPACT>(rec, position, d);
-                    const SurfaceDev* surf = sc.surfaces + hp.sid;
-                    bool diffuse;
-                    const Scatter ev = direct_material_evaluate(surf, hp.normal, hp.view, rng, diffuse);
-                    if (ev.scatter) {
-                        V3 e = mk(surf->emit[0], surf->emit[1], surf->emit[2]);
-                        if (direct_listed(lights, slots, tv.best_prim)) e = v_scale(e, w);
-                        light = v_add(light, v_mul(thr, e));
-                        w = 1.0;
-                        if (diffuse) {
-                            const DirectBounce db = sky_bounce(mk(surf->color[0], surf->color[1], surf->color[2]), thr, position,
-                                                               hp.normal, ev.dir, rng, lights, sky);
-                            shadow = db.shadow, credit = db.credit, w = db.w_next;
-                            if (shadow) d = db.l_s;
-                        }
-                        thr = v_mul(thr, ev.color);  // the roulette and DivAssign (device_path.h bounce_step)
-                        const double p = rr_max(rr_max(thr.x, thr.y), thr.z);
-                        goes_on = !(rng.next() > p);
-                        if (goes_on) thr = mk(thr.x / p, thr.y / p, thr.z / p);
-                        bounce++;
-                        goes_on = goes_on && bounce < rd.max_bounces;
-                        result = light;  // lib.rs:550, the roulette, or lib.rs:559
-                        if (shadow) o = position, l = ev.dir, ended = false, new_ray = true;
-                        else if (goes_on) o = position, d = ev.dir, ended = false, new_ray = true;
-                    }
-                } else {
-                    result = v_add(light, v_mul(thr, v_scale(background(sc, d), w)));  // light + throughput * (background(dir) * w)
-                }
-                if (ended) {
-                    if (START == LIT_START_POINT) result = v_add(first, result);  // L = credit + radiance(..)
-                    sum = v_add(sum, result);
-                    s++;
-                    if (s < s_end) {
-                        new_sample = true;
-                    } else {  // the chunk is done: plain vector stores, and the lane is idle
-                        double* dst = rd.partial + (size_t)item * 3u;
-                        dst[0] = sum.x, dst[1] = sum.y, dst[2] = sum.z;
-                        rd.partial_queries[item] = queries;
-                        has = false;
-                    }
-                }
-            }
-            // ---- refill: idle lanes take the next items, lowest lane first
-            if (do_refill) {
-                bool need = !has;
-                const unsigned long long need_mask = __ballot(need);
-                if (need_mask != 0ull) {
-                    const uint32_t wanted = (uint32_t)__popcll(need_mask);
-                    unsigned long long base = 0ull;
-                    if ((threadIdx.x & 63u) == 0u) base = atomicAdd(rd.cursor, (unsigned long long)wanted);
-                    base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-                    const unsigned long long left = base < n_items ? n_items - base : 0ull;
-                    const uint32_t avail = left < wanted ? (uint32_t)left : wanted;
-                    if (need && lanes_below(need_mask) < avail) {
-                        item = (uint32_t)base + lanes_below(need_mask);  // (n_items <= 2^20)
-                        ray = item / rd.chunks;
-                        s = (item - ray * rd.chunks) * rd.chunk;
-                        s_end = rd.samples - s < rd.chunk ? rd.samples : s + rd.chunk;
-                        sum = mk(0.0, 0.0, 0.0);  // C_k = Vec3::zeros()
-                        queries = 0u;
-                        has = true, new_sample = true;
-                    }
-                    if (avail < wanted) no_more = true;
-                }
-            }
-            // ---- a new sample's start; every new ray is one Bvh::intersect call
-            if (new_sample) {
-                const SkyStart st = sky_path_start<START>(rd, lights, sky, cam, ray, s);
-                rng = st.rng, o = st.o, d = st.d;
-                thr = mk(1.0, 1.0, 1.0), light = mk(0.0, 0.0, 0.0);
-                bounce = 0u;
-                shadow = false, w = 1.0;
-                if (START == LIT_START_POINT) first = mk(0.0, 0.0, 0.0);
-                if (START == LIT_START_POINT) {  // the virtual bounce: no roulette, the path goes on (max_bounces >= 1)
-                    shadow = st.first.shadow, credit = st.first.credit, w = st.first.w_next;
-                    goes_on = true;
-                    if (shadow) l = d, d = st.first.l_s;
-                }
-                new_ray = true;
-            }
-            if (new_ray) {
-                trav_init(sc, o, d, tv);
-                queries++;
-            }
-            // ---- the whole wave: fresh lanes get the hot group's test, where the scene has one, before they walk
-            closest_start<EXACT>(sc, o, d, new_ray, tv);
-            continue;
-        }
-        if (n_walk == 0) break;  // (no lane holds a path and no item is left)
-        const bool leaf_phase = n_leaf >= (int)rd.leaf_min || n_int == 0;
-        if (leaf_phase) {
-            if (at_leaf) closest_leaf_step<COMPACT>(sc, o, d, stack, tv);
-        } else {
-            if (at_int) closest_interior_step<COMPACT, EXACT>(sc, o, stack, tv);
-        }
-    }
+    sky_wave<COMPACT, EXACT>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
 }
 
 // A ray's chunk sums added in chunk order (the first assigned), scaled by the reciprocal of S, and its query counts added:

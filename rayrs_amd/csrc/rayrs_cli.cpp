@@ -3,7 +3,13 @@
 //     rayrs hdri_path [spp] [--scene NAME] [--seed N] [--device N] [--max-bounces N] [--fast-traversal 0|1]
 //                           [--gpus N | --devices a,b,...] [--sample-chunk C] [--pass N] [--until-noise TAU]
 //                           [--denoise [LEVELS]] [--features] [--denoise-guided [LEVELS]] [--noise]
-//                           [--ao [S]] [--ao-radius R]
+//                           [--ao [S]] [--ao-radius R] [--direct] [--sky]
+//
+// --direct and --sky make the film direct-lit (include/rayrs_hip.h DIRECT-LIT FILMS): --direct lists the scene's emissive spheres
+// and rectangles that DIRECT LIGHTING's material rule admits, in object order, --sky adds the sky.  Both need a film (--pass or
+// --until-noise); without one, with --direct on a scene that has no admissible lamp and no --sky, or with more than 8 lamps, the
+// program prints a usage error naming the option, exits with status 2 and writes nothing.  Every other option works on such a film
+// unchanged, and with neither option every file is the same bytes as without this paragraph.
 //
 // --ao additionally writes <scene>_ao.png (no gamma) and <scene>_ao.hdr: the ambient-occlusion plane of include/rayrs_hip.h
 // (AMBIENT OCCLUSION PLANE) on three channels, S samples a pixel (default 16), ao_seed 0xA0, rays leaving the surface by a bias
@@ -153,6 +159,7 @@ int main(int argc, char** argv) {
     uint32_t denoise_levels = 5;
     bool want_guided = false, want_noise = false;
     uint32_t guided_levels = 5;
+    bool want_direct = false, want_sky = false;  // --direct, --sky: a direct-lit film
     bool want_ao = false;
     uint32_t ao_samples = 16;
     double ao_radius = INFINITY;
@@ -194,6 +201,11 @@ int main(int argc, char** argv) {
         }
         if (opt == "--temporal") {
             temporal = true;
+            i--;
+            continue;
+        }
+        if (opt == "--direct" || opt == "--sky") {
+            (opt == "--direct" ? want_direct : want_sky) = true;
             i--;
             continue;
         }
@@ -274,6 +286,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Usage: --denoise-guided and --noise read a film's noise estimate: give --pass N (or --until-noise TAU)\n");
         return 2;
     }
+    if ((want_direct || want_sky) && !use_film) {
+        std::fprintf(stderr, "Usage: %s makes the film direct-lit: give --pass N (or --until-noise TAU)\n", want_direct ? "--direct" : "--sky");
+        return 2;
+    }
     if ((orbit_given || temporal) && (!use_film || pass == 0)) {
         std::fprintf(stderr, "Usage: --orbit FRAMES DEGREES and --temporal render every frame through a film: give --pass N\n");
         return 2;
@@ -309,6 +325,31 @@ int main(int argc, char** argv) {
     uint32_t hw = 0, hh = 0;
     int st = rayrs_hdr_load(hdri_path, &hdri, &hw, &hh);  // main.rs:36-41; the clip(0,3) of :43 happens in rayrs_scene_new
     if (st != RAYRS_OK) return fail("hdri", st);
+
+    // --direct's list: the emissive spheres and rectangles, in object order, whose material always scatters (DIRECT LIGHTING's rule)
+    std::vector<uint32_t> lamps;
+    uint32_t n_objects = 0;
+    auto note_object = [&](const rayrs_material& m, const rayrs_emission& e) {
+        const bool emits = e.emissive != 0 && (e.strength * e.color[0] != 0.0 || e.strength * e.color[1] != 0.0 || e.strength * e.color[2] != 0.0);
+        const bool always_scatters = m.kind == RAYRS_MAT_LAMBERTIAN || m.kind == RAYRS_MAT_REFLECT || m.kind == RAYRS_MAT_GLASS;
+        if (emits && always_scatters) lamps.push_back(n_objects);
+        n_objects++;
+    };
+    if (want_direct || want_sky) {  // (before anything is made: a usage error leaves nothing behind)
+        rayrs_emission none;
+        std::memset(&none, 0, sizeof none);
+        note_object(cook_torrance_metal(1, 1, 1, 0.5, 0.8, 0.8, 0.8), none);
+        for (const rayrs_material& m : def.spheres) note_object(m, none);
+        if (!want_direct) lamps.clear();
+        if (want_direct && lamps.empty() && !want_sky) {
+            std::fprintf(stderr, "Usage: --direct needs a lamp, and scene %s has no emissive sphere or rectangle it can list: give --sky\n", scene_name.c_str());
+            return 2;
+        }
+        if (lamps.size() > RAYRS_MAX_LIGHTS) {
+            std::fprintf(stderr, "Usage: --direct lists at most %d lamps, scene %s has %zu\n", RAYRS_MAX_LIGHTS, scene_name.c_str(), lamps.size());
+            return 2;
+        }
+    }
 
     rayrs_objects* objs = nullptr;
     if ((st = rayrs_objects_create(&objs)) != RAYRS_OK) return fail("objects", st);
@@ -408,6 +449,13 @@ int main(int argc, char** argv) {
         if ((s = rayrs_hdr_save((scene_name + ".hdr").c_str(), rgb.data(), cam.x_pixels, cam.y_pixels)) != RAYRS_OK) return fail("hdr", s), s;
         return RAYRS_OK;
     };
+    // the film of the options: plain, or direct-lit with --direct's lamps and, with --sky, the sky
+    auto make_film = [&](const rayrs_film_params* fprm, rayrs_film** film) -> int {
+        const uint32_t* list = lamps.empty() ? nullptr : lamps.data();
+        if (want_sky) return rayrs_film_create_sky(scene, &cam, fprm, list, (uint32_t)lamps.size(), film);
+        if (want_direct) return rayrs_film_create_direct(scene, &cam, fprm, list, (uint32_t)lamps.size(), film);
+        return rayrs_film_create(scene, &cam, fprm, film);
+    };
     if (orbit_given) {
         // <scene>_%04d.png/.hdr per frame; --temporal: <scene>_%04d_temporal.*, the history after the frame's push;
         // --denoise-guided: <scene>_%04d_guided.*, the history (--temporal) or the frame's film through the guided filter
@@ -430,7 +478,7 @@ int main(int argc, char** argv) {
             std::memset(&fprm, 0, sizeof fprm);
             fprm.sample_chunk = sample_chunk, fprm.max_bounces = max_bounces, fprm.seed = seed, fprm.fast_traversal = fast_traversal;
             rayrs_film* film = nullptr;
-            if ((st = rayrs_film_create(scene, &cam, &fprm, &film)) != RAYRS_OK) return fail("film", st);
+            if ((st = make_film(&fprm, &film)) != RAYRS_OK) return fail("film", st);
             for (uint32_t done = 0; done < spp;) {
                 const uint32_t n = spp - done < pass ? spp - done : pass;
                 if ((st = rayrs_film_render(film, n, nullptr)) != RAYRS_OK) return fail("film pass", st);
@@ -470,7 +518,7 @@ int main(int argc, char** argv) {
         fprm.seed = seed;
         fprm.fast_traversal = fast_traversal;
         rayrs_film* film = nullptr;
-        if ((st = rayrs_film_create(scene, &cam, &fprm, &film)) != RAYRS_OK) return fail("film", st);
+        if ((st = make_film(&fprm, &film)) != RAYRS_OK) return fail("film", st);
         rayrs_film_status fs;
         std::memset(&fs, 0, sizeof fs);
         uint32_t done = 0;
