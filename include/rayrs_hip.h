@@ -1190,6 +1190,104 @@ int rayrs_film_create_direct(rayrs_scene* scene, const rayrs_camera* camera, con
 int rayrs_film_create_sky(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params,
                           const uint32_t* lights /* HOST */, uint32_t n_lights, rayrs_film** out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * BAKE.  The progressive film's machinery for the callers of the radiance queries: a bake is a device-resident accumulation
+ * buffer over n rays or points of the caller's -- lightmap texels, probe positions -- bound to one scene, one strategy (unlit,
+ * DIRECT LIGHTING, SKY SAMPLING) and one set of sampling settings, to which samples are added in passes, to every point or only
+ * to the points the noise estimate calls for.  Points are independent, so the unit of everything below is the single point i
+ * with its own sample count N_i.  a and b are HOST arrays of n*3 f64 (kind 0: positions and normals, kind 1: origins and
+ * directions), copied to the device at creation; lights is a HOST array, copied at creation and fixed for the bake's life.
+ *
+ * THE CONTRACT PER POINT.  After any sequence of passes that leaves point i at N_i samples, rayrs_bake_read returns for point i,
+ * bit for bit, the radiance the matching query returns for that one point with samples = N_i, sample_chunk = c,
+ * index_base = index_base + i and the same seed, max_bounces, bias, walk and list, and as its query count that call's `queries`,
+ * kept in 64 bits.  The matching query: kind 0 rayrs_scene_irradiance (sky = 0, n_lights == 0), rayrs_scene_irradiance_direct
+ * (sky = 0, n_lights > 0) or rayrs_scene_irradiance_sky (sky = 1); kind 1 the _radiance ones.  (A bake with sky = 0 and an empty
+ * list runs DIRECT LIGHTING's paths with K = 0, which are the unlit query's bit for bit.)  This holds for every partition into
+ * passes that the rules allow and across a rayrs_bake_state_get / new bake / rayrs_bake_state_set in between: a sample's random
+ * numbers depend on (seed, index_base + i, sample index) only, the record's sum starts by assignment with the first chunk sum,
+ * later chunk sums are added in chunk order, and the read is sum * (1.0 / N_i).  A point without samples reads +0 and 0.
+ *
+ * RULES.  The progressive film's, per point.  c = sample_chunk is fixed for the bake's life; while the bake is open every N_i is
+ * a multiple of c.  rayrs_bake_render(n) adds the samples N_i .. N_i + n - 1 to every point from its own N_i, and CLOSES the bake
+ * if n % c != 0; n = 0, or any pass on a closed bake, is RAYRS_INVALID_ARG and changes nothing.  (largest N_i) + n < 2^30, else
+ * RAYRS_UNSUPPORTED.  A pass of more than 2^16 chunks per point (ceil(n / c) > 65536) is RAYRS_UNSUPPORTED and leaves the bake
+ * unchanged.  An adaptive pass needs n % c == 0 (else RAYRS_INVALID_ARG) and never closes the bake.  A pass uses the scene's
+ * radiance scratch and stack strip under the queries' ordering rule, and is synchronous.  max_bounces == 0: every sample is +0 and
+ * makes no query, as the queries have it.  The scene outlives its bakes; the calls on one scene, its films and its bakes come from
+ * one thread at a time.
+ *
+ * NOISE is the film's, word for word, with M_i = N_i / c per point: S1 and S2 are the sums over the point's full chunks of
+ * y = (x + y) + z of the chunk sum and of y*y, accumulated in chunk order starting by assignment, unfused; the converged-at-tau
+ * predicate and the non-finite rule are NOISE's.  rayrs_bake_noise is NOISE PLANE's formula per point with M = M_i: +infinity
+ * for M_i < 2 or non-finite sums, selected and never computed.
+ *
+ * SELECTION.  rayrs_bake_render_adaptive(n, tau, max_point_samples) takes point i iff N_i + n <= max_point_samples (0 = no cap
+ * but the 30-bit cursor) and the point is unconverged at tau; a non-finite point is never taken.  The selected points are sampled
+ * in ascending index order, so a pass's work is a function of the bake's state alone.  *active_points = the number selected; 0
+ * is RAYRS_OK with no launch and stats zeroed.  tau: finite and >= 0.
+ *
+ * rayrs_bake_pass: points = the points the pass sampled, paths = points * n, rays = the closest-hit queries its paths made
+ * (shadow rays included), kernel_ms = one HIP-event time of all the pass's kernels, total_ms = the call's wall time, launches =
+ * the launches of the wave kernels.  rayrs_bake_status: samples = the largest N_i, rays and paths summed over all passes,
+ * unconverged and nonfinite by NOISE at the call's tau, points = n.
+ *
+ * Refusals at creation, all decided before the device is touched, in the queries' order.  RAYRS_INVALID_ARG: a NULL scene, a, b,
+ * params or out; fast_traversal > 1; kind > 1; sky > 1; pad != 0; lights == NULL with n_lights > 0; an index >= the scene's
+ * object count.  Then RAYRS_UNSUPPORTED: c >= 2^30; max_bounces > 8000; c * max_bounces >= 2^32 for the unlit bake,
+ * c * (2 * max_bounces + 1) >= 2^32 for the others (an item's query counter is 32 bits); n_lights > RAYRS_MAX_LIGHTS; an index
+ * naming a triangle; DIRECT LIGHTING's material rule; with sky = 1 the empty table; n >= 2^32.  Then RAYRS_NO_DEVICE.  n == 0 on
+ * a device scene makes a legal, empty bake: its passes launch nothing and its reads return nothing.
+ *
+ * Checkpoint: an opaque, versioned byte image -- the records, the query counts, the sample counts, the counters and the settings
+ * (kind, sky, c, max_bounces, walk, seed, index_base, bias) and n.  The points, the scene and the list are NOT recorded, as a
+ * film's camera and list are not: continuing on other points is the caller's error.  rayrs_bake_state_set refuses
+ * (RAYRS_INVALID_ARG, the bake unchanged) an image of another image version, settings or n, or a length that is not
+ * rayrs_bake_state_bytes.  The footprint on the device: 100 bytes per point (48 of them the point itself). */
+typedef struct rayrs_bake rayrs_bake;
+
+typedef struct {            /* zero-initialise */
+    uint32_t kind;          /* 0: irradiance (a = positions, b = normals); 1: radiance (a = origins, b = directions) */
+    uint32_t sample_chunk;  /* c >= 1, fixed for the bake's life; 0 = 4 */
+    uint32_t max_bounces;
+    uint32_t fast_traversal;/* taken as asked, as the queries take it */
+    uint64_t seed, index_base;
+    double   bias;          /* kind 0 only */
+    uint32_t sky;           /* 1: SKY SAMPLING's paths (lights may be empty); 0: DIRECT LIGHTING's, the unlit ones with n_lights == 0 */
+    uint32_t pad;
+} rayrs_bake_params;
+
+typedef struct {
+    uint64_t points;        /* the points the pass sampled */
+    uint64_t paths, rays;
+    double kernel_ms, total_ms;
+    uint32_t launches, pad;
+} rayrs_bake_pass;
+
+typedef struct {
+    uint64_t samples;       /* the largest N_i */
+    uint64_t rays, paths;   /* summed over all passes */
+    uint64_t unconverged, nonfinite; /* NOISE, for the tau of the call */
+    uint64_t points;        /* n */
+    uint32_t closed;        /* 1 = the last pass ended in a short chunk: no further pass is accepted */
+    uint32_t pad;
+} rayrs_bake_status;
+
+int rayrs_bake_create(rayrs_scene* scene, const double* a, const double* b, uint64_t n, const rayrs_bake_params* params,
+                      const uint32_t* lights /* HOST */, uint32_t n_lights, rayrs_bake** out);
+void rayrs_bake_destroy(rayrs_bake* bake);
+int rayrs_bake_render(rayrs_bake* bake, uint32_t n_samples, rayrs_bake_pass* stats /* may be NULL */);
+int rayrs_bake_render_adaptive(rayrs_bake* bake, uint32_t n_samples, double tau, uint32_t max_point_samples,
+                               uint64_t* active_points /* may be NULL */, rayrs_bake_pass* stats /* may be NULL */);
+/* host buffers; either may be NULL = not wanted, not both */
+int rayrs_bake_read(rayrs_bake* bake, double* radiance /* n*3 */, uint64_t* queries /* n */);
+int rayrs_bake_point_samples(rayrs_bake* bake, uint32_t* out /* n */);
+int rayrs_bake_noise(rayrs_bake* bake, double* variance /* n */);
+int rayrs_bake_status_get(rayrs_bake* bake, double tau, rayrs_bake_status* out);
+uint64_t rayrs_bake_state_bytes(const rayrs_bake* bake);
+int rayrs_bake_state_get(rayrs_bake* bake, void* out_host, uint64_t cap);
+int rayrs_bake_state_set(rayrs_bake* bake, const void* in_host, uint64_t bytes);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -1204,7 +1302,9 @@ int rayrs_film_create_sky(rayrs_scene* scene, const rayrs_camera* camera, const 
  * rayrs_scene_irradiance_lit, their _launch forms and rayrs_render_lit (LIGHT SAMPLING), and with rayrs_scene_radiance_direct,
  * rayrs_scene_irradiance_direct, their _launch forms and rayrs_render_direct (DIRECT LIGHTING), and with rayrs_scene_radiance_sky,
  * rayrs_scene_irradiance_sky, their _launch forms, rayrs_render_sky, rayrs_scene_sky_table, rayrs_scene_sky_sample and
- * rayrs_scene_sky_density (SKY SAMPLING), and with rayrs_film_create_direct and rayrs_film_create_sky (DIRECT-LIT FILMS).  The
+ * rayrs_scene_sky_density (SKY SAMPLING), and with rayrs_film_create_direct and rayrs_film_create_sky (DIRECT-LIT FILMS), and with
+ * rayrs_bake_* and its three structs (BAKE; they are not in the layout table below: all their fields are 4 or 8 bytes wide and
+ * naturally aligned).  The
  * layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised

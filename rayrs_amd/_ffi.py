@@ -39,6 +39,9 @@ SYMBOLS = [
     "rayrs_scene_radiance_sky", "rayrs_scene_radiance_sky_launch", "rayrs_scene_irradiance_sky", "rayrs_scene_irradiance_sky_launch",
     "rayrs_render_sky", "rayrs_scene_sky_table", "rayrs_scene_sky_sample", "rayrs_scene_sky_density",
     "rayrs_film_create_direct", "rayrs_film_create_sky",
+    "rayrs_bake_create", "rayrs_bake_destroy", "rayrs_bake_render", "rayrs_bake_render_adaptive", "rayrs_bake_read",
+    "rayrs_bake_point_samples", "rayrs_bake_noise", "rayrs_bake_status_get", "rayrs_bake_state_bytes", "rayrs_bake_state_get",
+    "rayrs_bake_state_set",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -119,6 +122,27 @@ class FilmStatus(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("full_chunks", C.c_uint64), ("rays", C.c_uint64), ("paths", C.c_uint64),
                 ("nan_pixels", C.c_uint64), ("neg_pixels", C.c_uint64), ("unconverged", C.c_uint64),
                 ("nonfinite", C.c_uint64), ("closed", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+class BakeParams(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("sample_chunk", C.c_uint32), ("max_bounces", C.c_uint32), ("fast_traversal", C.c_uint32),
+                ("seed", C.c_uint64), ("index_base", C.c_uint64), ("bias", C.c_double), ("sky", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class BakePass(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double),
+                ("total_ms", C.c_double), ("launches", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+class BakeStatus(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("rays", C.c_uint64), ("paths", C.c_uint64), ("unconverged", C.c_uint64),
+                ("nonfinite", C.c_uint64), ("points", C.c_uint64), ("closed", C.c_uint32), ("pad", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
@@ -291,11 +315,25 @@ def lib():
                        ("rayrs_scene_sky_sample", [vp, vp, C.c_uint64, vp]),
                        ("rayrs_scene_sky_density", [vp, vp, C.c_uint64, vp]),
                        ("rayrs_film_create_direct", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, C.POINTER(vp)]),
-                       ("rayrs_film_create_sky", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, C.POINTER(vp)])):
+                       ("rayrs_film_create_sky", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, C.POINTER(vp)]),
+                       ("rayrs_bake_create", [vp, vp, vp, C.c_uint64, C.POINTER(BakeParams), vp, C.c_uint32, C.POINTER(vp)]),
+                       ("rayrs_bake_destroy", [vp]),
+                       ("rayrs_bake_render", [vp, C.c_uint32, C.POINTER(BakePass)]),
+                       ("rayrs_bake_render_adaptive", [vp, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(BakePass)]),
+                       ("rayrs_bake_read", [vp, vp, vp]),
+                       ("rayrs_bake_point_samples", [vp, vp]),
+                       ("rayrs_bake_noise", [vp, vp]),
+                       ("rayrs_bake_status_get", [vp, C.c_double, C.POINTER(BakeStatus)]),
+                       ("rayrs_bake_state_bytes", [vp]),
+                       ("rayrs_bake_state_get", [vp, vp, C.c_uint64]),
+                       ("rayrs_bake_state_set", [vp, vp, C.c_uint64])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):
         L.rayrs_history_destroy.restype = None
+    if hasattr(L, "rayrs_bake_destroy"):
+        L.rayrs_bake_destroy.restype = None
+        L.rayrs_bake_state_bytes.restype = C.c_uint64
     if hasattr(L, "rayrs_lab_query_steps"):  # (private: rayrs_amd/csrc/rayrs_lab.h; an older build behind RAYRS_HIP_LIB has none)
         L.rayrs_lab_query_steps.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]
     if hasattr(L, "rayrs_lab_ao_refill"):

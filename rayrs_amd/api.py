@@ -1057,6 +1057,163 @@ def render_until(film, tau: float, max_unconverged_fraction: float = 0.0, pass_s
     return st, reason
 
 
+# ---- the bake (include/rayrs_hip.h BAKE)
+
+class Bake:
+    """Progressive, adaptive radiance queries at fixed points (include/rayrs_hip.h BAKE): a device-resident accumulation
+    buffer over the n rays or points (a, b) -- kind="irradiance": points and normals, kind="radiance": origins and directions,
+    host arrays of shape (n, 3) -- to which samples are added pass by pass, to every point or only to the noisy ones.  After
+    passes that leave point i at N_i samples, values()[i] is, bit for bit, scene.irradiance (scene.radiance) of that one point
+    with samples=N_i, sample_chunk=sample_chunk, index_base=index_base + i and the same seed, bounces, bias, walk and lights.
+    lights and direct as the queries take them: direct=True with a list is the direct-lit bake, SKY in the list the sky bake;
+    a list without direct=True (the one-sample mix) has no bake.  The scene must outlive the bake."""
+
+    def __init__(self, scene: Scene, a, b, kind: str = "irradiance", sample_chunk: int = 4, max_bounces: int = 50, seed: int = 0,
+                 index_base: int = 0, bias: float = 0.0, fast_traversal: bool = False, lights=None, direct: bool = False):
+        if kind not in ("irradiance", "radiance"):
+            raise ValueError('kind is "irradiance" or "radiance"')
+        if direct and lights is None:
+            raise ValueError("direct=True needs a light list (lights=[...])")
+        if lights is not None and not direct:
+            raise ValueError("a bake with a light list is direct-lit: pass direct=True (the one-sample mix has no bake)")
+        a, b = (np.ascontiguousarray(x, dtype=np.float64) for x in (a, b))
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape:
+            raise ValueError("a and b are arrays of shape (n, 3)")
+        self._L, self._h = scene._L, None
+        self.scene, self.kind, self.n = scene, kind, int(a.shape[0])
+        self.sample_chunk = int(sample_chunk) or 4
+        self.lights = None if lights is None else [int(v) for v in _light_list(lights)]
+        p = _ffi.BakeParams()
+        p.kind, p.sample_chunk, p.max_bounces = 0 if kind == "irradiance" else 1, int(sample_chunk), int(max_bounces)
+        p.fast_traversal, p.seed, p.index_base, p.bias = 1 if fast_traversal else 0, int(seed), int(index_base), float(bias)
+        lamps = _light_list([] if lights is None else lights)
+        p.sky = 1 if (lamps == SKY).any() else 0   # (the rule the queries choose their entry point by)
+        lamps = lamps[lamps != SKY]
+        if self.n == 0:
+            a = b = np.zeros((1, 3))
+        h = C.c_void_p()
+        _ffi.check(self._L.rayrs_bake_create(scene._h, a.ctypes.data, b.ctypes.data, self.n, C.byref(p),
+                                             lamps.ctypes.data if len(lamps) else None, len(lamps), C.byref(h)), "rayrs_bake_create")
+        self._h = h
+
+    def render(self, n: int) -> dict:
+        """Adds n samples to every point from its own count; the pass's points, paths, rays, kernel_ms, total_ms and launches.
+        n that is not a multiple of sample_chunk closes the bake: no further pass is accepted."""
+        st = _ffi.BakePass()
+        _ffi.check(self._L.rayrs_bake_render(self._h, int(n), C.byref(st)), "rayrs_bake_render")
+        return st.as_dict()
+
+    def render_adaptive(self, n: int, tau: float, max_point_samples: int = 0):
+        """Adds n samples (a multiple of sample_chunk) to the points that are unconverged at tau and hold at most
+        max_point_samples - n samples (0: no cap).  Returns (active_points, stats); no point selected is (0, zeroed stats) and
+        leaves the bake as it is."""
+        st, active = _ffi.BakePass(), C.c_uint64(0)
+        _ffi.check(self._L.rayrs_bake_render_adaptive(self._h, int(n), float(tau), int(max_point_samples), C.byref(active),
+                                                      C.byref(st)), "rayrs_bake_render_adaptive")
+        return int(active.value), st.as_dict()
+
+    def values(self, queries: bool = False):
+        """The values as they stand, (n, 3) f64: a point's sum over its own sample count, +0 for a point without samples; with
+        queries also the closest-hit queries its paths made, (n,) uint64."""
+        m = max(self.n, 1)
+        rad, cnt = np.zeros((m, 3)), np.zeros(m, dtype=np.uint64)
+        _ffi.check(self._L.rayrs_bake_read(self._h, rad.ctypes.data, cnt.ctypes.data if queries else None), "rayrs_bake_read")
+        return (rad[:self.n], cnt[:self.n]) if queries else rad[:self.n]
+
+    def point_samples(self):
+        """Samples per point, (n,) uint32."""
+        out = np.zeros(max(self.n, 1), dtype=np.uint32)
+        _ffi.check(self._L.rayrs_bake_point_samples(self._h, out.ctypes.data), "rayrs_bake_point_samples")
+        return out[:self.n]
+
+    def noise(self):
+        """The noise estimate per point, (n,) f64 (include/rayrs_hip.h NOISE PLANE's formula): the batch-means variance of the
+        channel sum of values(); +inf where a point holds fewer than two full chunks."""
+        out = np.zeros(max(self.n, 1))
+        _ffi.check(self._L.rayrs_bake_noise(self._h, out.ctypes.data), "rayrs_bake_noise")
+        return out[:self.n]
+
+    def status(self, tau: float = 0.0) -> dict:
+        """samples (the largest per point), rays, paths, points, closed, and for this tau the noise estimate's counts
+        unconverged and nonfinite (include/rayrs_hip.h NOISE)."""
+        st = _ffi.BakeStatus()
+        _ffi.check(self._L.rayrs_bake_status_get(self._h, float(tau), C.byref(st)), "rayrs_bake_status_get")
+        return st.as_dict()
+
+    def state(self) -> bytes:
+        n = int(self._L.rayrs_bake_state_bytes(self._h))
+        buf = np.zeros(n, dtype=np.uint8)
+        _ffi.check(self._L.rayrs_bake_state_get(self._h, buf.ctypes.data, n), "rayrs_bake_state_get")
+        return buf.tobytes()
+
+    def set_state(self, image: bytes):
+        buf = np.frombuffer(image, dtype=np.uint8)
+        _ffi.check(self._L.rayrs_bake_state_set(self._h, buf.ctypes.data, len(buf)), "rayrs_bake_state_set")
+
+    def save(self, path):
+        """The bake's byte image in a file, nothing else (not the points, the scene or the lights)."""
+        with open(path, "wb") as f:
+            f.write(self.state())
+
+    def load(self, path):
+        """Continue from a saved bake: refused (RayrsError, the bake unchanged) unless the image was made with this bake's
+        kind, strategy, sample_chunk, seed, index_base, bias, max_bounces, walk and number of points."""
+        with open(path, "rb") as f:
+            self.set_state(f.read())
+
+    def close(self):
+        if self._h is not None:
+            self._L.rayrs_bake_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bake_until(bake, tau: float, pass_samples: int = 16, max_samples: int = 1024, adaptive: bool = True,
+               time_budget: Optional[float] = None):
+    """render_until for a bake: adds passes of pass_samples samples (rounded up to a multiple of the bake's sample_chunk) until
+    no point is unconverged at tau ("converged"), or the next pass would take the bake beyond max_samples ("max_samples"), or
+    time_budget seconds have passed ("time_budget").  adaptive: the passes are bake.render_adaptive(step, tau, max_samples) --
+    only the points that are still unconverged get samples, none beyond max_samples -- and "max_samples" is a pass that selects
+    no point while points are still unconverged.  Returns (status, reason); the status is bake.status(tau) as it stands with
+    "point_samples" added, the samples summed over the points, and with adaptive "active_points" of the last pass."""
+    import time
+    c = int(bake.sample_chunk)
+    step = -(-int(pass_samples) // c) * c
+    if step <= 0:
+        raise ValueError("pass_samples must be positive")
+    t0 = time.monotonic()
+    st = bake.status(tau)
+    active = None
+    while True:
+        if (st["samples"] > 0 or st["points"] == 0) and st["unconverged"] == 0:
+            reason = "converged"
+            break
+        if st["closed"] or (max_samples < step if adaptive else st["samples"] + step > max_samples):
+            reason = "max_samples"
+            break
+        if time_budget is not None and time.monotonic() - t0 >= time_budget:
+            reason = "time_budget"
+            break
+        if adaptive:
+            active, _ = bake.render_adaptive(step, tau, max_samples)
+            if active == 0:  # every point that is still noisy has its max_samples
+                reason = "max_samples"
+                break
+        else:
+            bake.render(step)
+        st = bake.status(tau)
+    st = dict(st)
+    if adaptive and active is not None:
+        st["active_points"] = active
+    st["point_samples"] = int(bake.point_samples().astype(np.uint64).sum())
+    return st, reason
+
+
 # ---- temporal accumulation (include/rayrs_hip.h TEMPORAL ACCUMULATION)
 
 # Starting points, not tuned values: the weight a history pixel may carry into a blend, in samples (16 frames of 16); the
