@@ -10,22 +10,13 @@
 
 namespace rayrs {
 
-// Sample s of point i: the operation of the header, in lambertian_scatter's operand and operation order (device_path.h), unfused.
+// Sample s of point i: the operation of the header, its direction device_path.h cosine_direction's on draws 0 and 1.
 RR_DEV void ao_ray(const AoDev& ao, uint32_t i, uint32_t s, V3& o, V3& l) {
     const double* pp = ao.position + (size_t)i * 3u;
     const double* pn = ao.normal + (size_t)i * 3u;
     const V3 p = mk(pp[0], pp[1], pp[2]), n = mk(pn[0], pn[1], pn[2]);
     Rng rng{rr_path_key(ao.seed, ao.index_base + i, (uint64_t)s), 0};
-    V3 e1, e2;
-    v_onb(n, e1, e2);
-    const double u = rng.next();
-    const double phi = 2.0 * RR_PI * rng.next();
-    const double su = rr_sqrt(u);
-    const rr_sincos_t sc_phi = rr_sincos(phi);
-    const double x = sc_phi.c * su;
-    const double y = sc_phi.s * su;
-    const double z = rr_sqrt(1.0 - u);
-    l = v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(n, z));
+    l = cosine_direction(n, rng);
     o = v_add(p, v_scale(n, ao.bias));
 }
 

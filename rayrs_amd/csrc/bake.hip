@@ -232,40 +232,17 @@ __global__ void __launch_bounds__(256) bake_read_kernel(BakeDev bk, double* radi
     dst[0] = bk.rec[BAKE_SX * bk.n + i] * inv, dst[1] = bk.rec[BAKE_SY * bk.n + i] * inv, dst[2] = bk.rec[BAKE_SZ * bk.n + i] * inv;
 }
 
-namespace {
-
-template <int KIND>
-hipError_t launch_bake_kind(bool compact, const SceneDev& sc, const RadianceDev& rd, const BakeStartDev& bs, const LightsDev& lights,
-                            const LightSlotsDev& slots, const SkyDev* sky, uint32_t blocks, uint32_t lds, hipStream_t stream) {
-    return with_bools([&](auto C, auto E) {
-        if (sky) {
-            auto kernel = &bake_sky_kernel<decltype(C)::value, decltype(E)::value, KIND>;
-            const hipError_t e = raise_dynamic_lds(kernel, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, stream, sc, rd, bs, lights, slots, *sky);
-        } else {
-            auto kernel = &bake_direct_kernel<decltype(C)::value, decltype(E)::value, KIND>;
-            const hipError_t e = raise_dynamic_lds(kernel, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, stream, sc, rd, bs, lights, slots);
-        }
-        return hipGetLastError();
-    }, compact, sc.exact != 0u);
-}
-
-}  // namespace
-
 hipError_t launch_bake_wave(bool compact, const SceneDev& sc, const RadianceDev& rd, const BakeStartDev& bs, const LightsDev& lights,
                             const LightSlotsDev& slots, const SkyDev* sky, bool irradiance, int cu_count, hipStream_t stream) {
     if (rd.n == 0u) return hipSuccess;
-    const uint32_t lds = lane_stacks_lds_bytes(sc.stack_lds);
-    const uint64_t n_items = (uint64_t)rd.n * rd.chunks;
-    const uint64_t waves = (n_items + 63u) / 64u;  // (a wave takes up to 64 items at its first refill)
-    uint64_t blocks = (uint64_t)(cu_count > 0 ? cu_count : 1) * RADIANCE_BLOCKS_PER_CU;
-    if (blocks > QUERY_LAUNCH_RAYS / 256u) blocks = QUERY_LAUNCH_RAYS / 256u;  // (the stack strip is the queries')
-    if (blocks > waves) blocks = waves;
-    if (irradiance) return launch_bake_kind<LIT_START_POINT>(compact, sc, rd, bs, lights, slots, sky, (uint32_t)blocks, lds, stream);
-    return launch_bake_kind<LIT_START_RAY>(compact, sc, rd, bs, lights, slots, sky, (uint32_t)blocks, lds, stream);
+    const uint32_t blocks = radiance_grid_blocks(rd, cu_count);
+    return with_bools([&](auto C, auto E, auto P) {
+        constexpr int KIND = decltype(P)::value ? LIT_START_POINT : LIT_START_RAY;
+        if (sky) return launch_lane_stacks(&bake_sky_kernel<decltype(C)::value, decltype(E)::value, KIND>, blocks, sc.stack_lds, stream, sc, rd,
+                                           bs, lights, slots, *sky);
+        return launch_lane_stacks(&bake_direct_kernel<decltype(C)::value, decltype(E)::value, KIND>, blocks, sc.stack_lds, stream, sc, rd, bs,
+                                  lights, slots);
+    }, compact, sc.exact != 0u, irradiance);
 }
 
 hipError_t launch_bake_accumulate(const RadianceDev& rd, const BakeStartDev& bs, const BakeDev& bk, uint32_t full_chunks,

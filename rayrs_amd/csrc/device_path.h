@@ -1115,6 +1115,21 @@ RR_DEV Scatter ct_evaluate_refraction(const CtLayer& ct, V3 n, V3 h, V3 v, V3 l,
     return Scatter{true, color, l};
 }
 
+// The cosine-weighted direction about n on the next two draws, for the query kernels: lambertian_scatter's direction (below),
+// its operand and operation order, unfused.
+RR_DEV V3 cosine_direction(V3 n, Rng& rng) {
+    V3 e1, e2;
+    v_onb(n, e1, e2);
+    const double u = rng.next();
+    const double phi = 2.0 * RR_PI * rng.next();
+    const double su = rr_sqrt(u);
+    const rr_sincos_t sc_phi = rr_sincos(phi);
+    const double x = sc_phi.c * su;
+    const double y = sc_phi.s * su;
+    const double z = rr_sqrt(1.0 - u);
+    return v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(n, z));
+}
+
 RR_DEV Scatter lambertian_scatter(V3 color_in, V3 n, Rng& rng) {  // :259-281, :982-993, :1233-1243
     V3 e1, e2;
     v_onb(n, e1, e2);

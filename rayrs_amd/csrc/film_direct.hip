@@ -58,25 +58,12 @@ __global__ void __launch_bounds__(256) film_direct_count_kernel(RadianceDev rd, 
 hipError_t launch_film_direct(bool compact, const SceneDev& sc, const RadianceDev& rd, const FilmStartDev& fs, const LightsDev& lights,
                               const LightSlotsDev& slots, const SkyDev* sky, const CameraDev& cam, int cu_count, hipStream_t stream) {
     if (rd.n == 0u) return hipSuccess;
-    const uint32_t lds = lane_stacks_lds_bytes(sc.stack_lds);
-    const uint64_t n_items = (uint64_t)rd.n * rd.chunks;
-    const uint64_t waves = (n_items + 63u) / 64u;  // (a wave takes up to 64 items at its first refill)
-    uint64_t blocks = (uint64_t)(cu_count > 0 ? cu_count : 1) * RADIANCE_BLOCKS_PER_CU;
-    if (blocks > QUERY_LAUNCH_RAYS / 256u) blocks = QUERY_LAUNCH_RAYS / 256u;  // (the stack strip is the queries')
-    if (blocks > waves) blocks = waves;
+    const uint32_t blocks = radiance_grid_blocks(rd, cu_count);
     return with_bools([&](auto C, auto E) {
-        if (sky) {
-            auto kernel = &film_sky_kernel<decltype(C)::value, decltype(E)::value>;
-            const hipError_t e = raise_dynamic_lds(kernel, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), lds, stream, sc, rd, fs, lights, slots, *sky, cam);
-        } else {
-            auto kernel = &film_direct_kernel<decltype(C)::value, decltype(E)::value>;
-            const hipError_t e = raise_dynamic_lds(kernel, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), lds, stream, sc, rd, fs, lights, slots, cam);
-        }
-        return hipGetLastError();
+        if (sky) return launch_lane_stacks(&film_sky_kernel<decltype(C)::value, decltype(E)::value>, blocks, sc.stack_lds, stream, sc, rd, fs,
+                                           lights, slots, *sky, cam);
+        return launch_lane_stacks(&film_direct_kernel<decltype(C)::value, decltype(E)::value>, blocks, sc.stack_lds, stream, sc, rd, fs, lights,
+                                  slots, cam);
     }, compact, sc.exact != 0u);
 }
 

@@ -1,5 +1,5 @@
 // launch_dispatch.h -- what the launch glue of the .hip files shares: run-time bools into template arguments, a kernel's
-// dynamic-LDS limit, and the LDS of a launch whose lanes each walk the tree with a stack of their own.
+// dynamic-LDS limit, and the LDS and the launch of a kernel whose lanes each walk the tree with a stack of their own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,5 +41,15 @@ hipError_t raise_dynamic_lds(void (*kernel_fn)(Args...), uint32_t lds) {
 // Dynamic LDS of a 256-thread workgroup of one-lane queries (device_path.h lane_stack): four waves' stacks of
 // stack_lds entries and the spare one.
 inline uint32_t lane_stacks_lds_bytes(uint32_t stack_lds) { return 4u * 64u * (stack_lds + 1u) * 4u; }
+
+// The launch of such a kernel on `blocks` workgroups of 256: its dynamic-LDS limit raised to the stacks' size, then the launch.
+template <class... Params, class... Args>
+hipError_t launch_lane_stacks(void (*kernel)(Params...), uint32_t blocks, uint32_t stack_lds, hipStream_t stream, const Args&... args) {
+    const uint32_t lds = lane_stacks_lds_bytes(stack_lds);
+    const hipError_t e = raise_dynamic_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, stream, args...);
+    return hipGetLastError();
+}
 
 }  // namespace rayrs

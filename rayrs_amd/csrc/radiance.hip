@@ -7,12 +7,12 @@
 #include "device_path.h"
 #include "launch_dispatch.h"
 #include "radiance_kernels.h"
+#include "radiance_wave_parts.h"
 
 namespace rayrs {
 
 // The start of sample s of ray (point) `ray`: its RNG and its first ray.  RADIANCE QUERY: the caller's ray, draw 0 next.
-// IRRADIANCE: AMBIENT OCCLUSION's ray (ao.hip ao_ray: lambertian_scatter's operand and operation order, unfused) on draws 0
-// and 1, draw 2 next.
+// IRRADIANCE: AMBIENT OCCLUSION's ray (ao.hip ao_ray: device_path.h cosine_direction) on draws 0 and 1, draw 2 next.
 template <bool IRRADIANCE>
 RR_DEV void radiance_sample_start(const RadianceDev& rd, uint32_t ray, uint32_t s, Rng& rng, V3& o, V3& d) {
     const double* pa = rd.a + (size_t)ray * 3u;
@@ -20,16 +20,7 @@ RR_DEV void radiance_sample_start(const RadianceDev& rd, uint32_t ray, uint32_t 
     const V3 a = mk(pa[0], pa[1], pa[2]), b = mk(pb[0], pb[1], pb[2]);
     rng = Rng{rr_path_key(rd.seed, rd.index_base + ray, (uint64_t)s), 0};
     if (IRRADIANCE) {
-        V3 e1, e2;
-        v_onb(b, e1, e2);
-        const double u = rng.next();
-        const double phi = 2.0 * RR_PI * rng.next();
-        const double su = rr_sqrt(u);
-        const rr_sincos_t sc_phi = rr_sincos(phi);
-        const double x = sc_phi.c * su;
-        const double y = sc_phi.s * su;
-        const double z = rr_sqrt(1.0 - u);
-        d = v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(b, z));
+        d = cosine_direction(b, rng);
         o = v_add(a, v_scale(b, rd.bias));
     } else {
         o = a, d = b;
@@ -134,6 +125,7 @@ __global__ void __launch_bounds__(256) radiance_kernel(SceneDev sc, RadianceDev 
                     const uint32_t avail = left < wanted ? (uint32_t)left : wanted;
                     if (need && lanes_below(need_mask) < avail) {
                         item = (uint32_t)base + lanes_below(need_mask);  // (n_items <= 2^20)
+                        // (radiance_wave_parts.h QueryStart::take, written out: called, it moves these kernels' code)
                         ray = item / rd.chunks;
                         s = (item - ray * rd.chunks) * rd.chunk;
                         s_end = rd.samples - s < rd.chunk ? rd.samples : s + rd.chunk;
@@ -181,45 +173,16 @@ __global__ void __launch_bounds__(256) radiance_kernel(SceneDev sc, RadianceDev 
     }
 }
 
-// A ray's chunk sums added in chunk order (the first assigned), scaled by the reciprocal of S, and its query counts added:
-// one thread per ray.
-__global__ void __launch_bounds__(256) radiance_resolve_kernel(RadianceDev rd) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= rd.n) return;
-    const double* p = rd.partial + (size_t)i * rd.chunks * 3u;
-    const uint32_t* pq = rd.partial_queries + (size_t)i * rd.chunks;
-    V3 sum = mk(p[0], p[1], p[2]);
-    uint32_t q = pq[0];
-    for (uint32_t k = 1; k < rd.chunks; k++) {
-        sum = v_add(sum, mk(p[3u * k], p[3u * k + 1u], p[3u * k + 2u]));
-        q += pq[k];
-    }
-    const double inv = 1.0 / (double)rd.samples;
-    if (rd.radiance != nullptr) {
-        double* dst = rd.radiance + (size_t)i * 3u;
-        dst[0] = sum.x * inv, dst[1] = sum.y * inv, dst[2] = sum.z * inv;
-    }
-    if (rd.queries != nullptr) rd.queries[i] = q;
-}
+__global__ void __launch_bounds__(256) radiance_resolve_kernel(RadianceDev rd) { radiance_resolve(rd); }
 
 hipError_t launch_radiance(bool compact, const SceneDev& sc, const RadianceDev& rd, int cu_count, hipStream_t stream) {
     if (rd.n == 0u) return hipSuccess;
-    const uint32_t lds = lane_stacks_lds_bytes(sc.stack_lds);
-    const uint64_t n_items = (uint64_t)rd.n * rd.chunks;
-    const uint64_t waves = (n_items + 63u) / 64u;  // (a wave takes up to 64 items at its first refill)
-    uint64_t blocks = (uint64_t)(cu_count > 0 ? cu_count : 1) * RADIANCE_BLOCKS_PER_CU;
-    if (blocks > QUERY_LAUNCH_RAYS / 256u) blocks = QUERY_LAUNCH_RAYS / 256u;  // (the stack strip is the queries')
-    if (blocks > waves) blocks = waves;
     const hipError_t e = with_bools([&](auto C, auto E, auto I, auto S) {
-        auto kernel = &radiance_kernel<decltype(C)::value, decltype(E)::value, decltype(I)::value, decltype(S)::value>;
-        const hipError_t e = raise_dynamic_lds(kernel, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), lds, stream, sc, rd);
-        return hipGetLastError();
+        return launch_lane_stacks(&radiance_kernel<decltype(C)::value, decltype(E)::value, decltype(I)::value, decltype(S)::value>,
+                                  radiance_grid_blocks(rd, cu_count), sc.stack_lds, stream, sc, rd);
     }, compact, sc.exact != 0u, rd.irradiance != 0u, rd.turns != nullptr);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(radiance_resolve_kernel, dim3((rd.n + 255u) / 256u), dim3(256), 0, stream, rd);
-    return hipGetLastError();
+    return launch_radiance_resolve(radiance_resolve_kernel, rd, stream);
 }
 
 }  // namespace rayrs

@@ -10,28 +10,9 @@
 #include "device_path.h"
 #include "radiance_direct_device.h"
 #include "radiance_direct_kernels.h"
+#include "radiance_wave_parts.h"
 
 namespace rayrs {
-
-// Who starts the wave's paths: which items a launch has, what item `item` is, and the pixel of a LIT_START_PIXEL ray.  This one
-// is the queries': item = ray * chunks + chunk of the rays 0 .. rd.n - 1, every item taken; a pixel is index_base + ray in image
-// order.  KIND is the LIT_START_* the sample's start is made by; SKIPS says whether take() can turn an item down.
-template <int START>
-struct QueryStart {
-    static constexpr int KIND = START;
-    static constexpr bool SKIPS = false;
-    RR_DEV unsigned long long n_items(const RadianceDev& rd) const { return (unsigned long long)rd.n * rd.chunks; }
-    RR_DEV bool take(const RadianceDev& rd, const CameraDev&, uint32_t item, uint32_t& ray, uint32_t& s, uint32_t& s_end) const {
-        ray = item / rd.chunks;
-        s = (item - ray * rd.chunks) * rd.chunk;
-        s_end = rd.samples - s < rd.chunk ? rd.samples : s + rd.chunk;
-        return true;
-    }
-    RR_DEV void pixel(const RadianceDev& rd, const CameraDev& cam, uint32_t ray, uint32_t& row, uint32_t& col) const {
-        const uint32_t pix = (uint32_t)rd.index_base + ray;  // (the image's pixels: below 2^32)
-        row = pix / cam.W, col = pix - row * cam.W;
-    }
-};
 
 // The start of sample s of ray (point, pixel) `ray`: its RNG and its first ray.  LIT_START_POINT with lights is IRRADIANCE,
 // DIRECT's virtual bounce: `first` is then its shadow sample and the weight of the first ray's meeting with a listed object.
@@ -43,38 +24,15 @@ struct DirectStart {
 template <class START>
 RR_DEV DirectStart direct_sample_start(const START& start, const RadianceDev& rd, const LightsDev& lights, const CameraDev& cam,
                                        uint32_t ray, uint32_t s) {
-    Rng rng;
-    V3 o, d;
+    SampleStart st = sample_start(start, rd, cam, ray, s);
     DirectBounce first;
     first.shadow = false, first.l_s = mk(0.0, 0.0, 1.0), first.credit = mk(0.0, 0.0, 0.0), first.w_next = 1.0;
-    if (START::KIND == LIT_START_PIXEL) {
-        uint32_t row, col;
-        start.pixel(rd, cam, ray, row, col);
-        rng = Rng{sample_key(rd.seed, cam, row, col, s), 0};
-        sample_ray(cam, row, col, rng, o, d);
-        return DirectStart{rng, o, d, first};
+    if (START::KIND == LIT_START_POINT) {  // IRRADIANCE's ray, then DIRECT's virtual bounce at the point
+        const V3 n = st.d;
+        st.d = cosine_direction(n, st.rng);
+        if (lights.n != 0u) first = direct_bounce(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), st.o, n, st.d, st.rng, lights);
     }
-    const double* pa = rd.a + (size_t)ray * 3u;
-    const double* pb = rd.b + (size_t)ray * 3u;
-    const V3 a = mk(pa[0], pa[1], pa[2]), b = mk(pb[0], pb[1], pb[2]);
-    rng = Rng{rr_path_key(rd.seed, rd.index_base + ray, (uint64_t)s), 0};
-    if (START::KIND == LIT_START_POINT) {  // IRRADIANCE's ray (radiance.hip radiance_sample_start)
-        o = v_add(a, v_scale(b, rd.bias));
-        V3 e1, e2;
-        v_onb(b, e1, e2);
-        const double u = rng.next();
-        const double phi = 2.0 * RR_PI * rng.next();
-        const double su = rr_sqrt(u);
-        const rr_sincos_t sc_phi = rr_sincos(phi);
-        const double x = sc_phi.c * su;
-        const double y = sc_phi.s * su;
-        const double z = rr_sqrt(1.0 - u);
-        d = v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(b, z));
-        if (lights.n != 0u) first = direct_bounce(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), o, b, d, rng, lights);
-    } else {
-        o = a, d = b;
-    }
-    return DirectStart{rng, o, d, first};
+    return DirectStart{st.rng, st.o, st.d, first};
 }
 
 // radiance_lit.hip radiance_lit_kernel's wave and its termination argument, turn for turn: a lane that holds a path either

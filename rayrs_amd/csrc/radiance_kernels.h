@@ -59,6 +59,18 @@ inline uint32_t radiance_chunks(uint32_t samples, uint32_t sample_chunk) {
     return (samples + c - 1u) / c;  // (samples + c - 1 < 2^31: samples < 2^30)
 }
 
+// The grid of every kernel that runs the radiance wave over rd's items (radiance.hip, radiance_lit.hip, radiance_direct.hip,
+// radiance_sky.hip, film_direct.hip, bake.hip): cu_count * RADIANCE_BLOCKS_PER_CU workgroups, at most the queries' stack strip's
+// and at most a wave per 64 items.
+inline uint32_t radiance_grid_blocks(const RadianceDev& rd, int cu_count) {
+    const uint64_t n_items = (uint64_t)rd.n * rd.chunks;
+    const uint64_t waves = (n_items + 63u) / 64u;  // (a wave takes up to 64 items at its first refill)
+    uint64_t blocks = (uint64_t)(cu_count > 0 ? cu_count : 1) * RADIANCE_BLOCKS_PER_CU;
+    if (blocks > QUERY_LAUNCH_RAYS / 256u) blocks = QUERY_LAUNCH_RAYS / 256u;  // (the stack strip is the queries')
+    if (blocks > waves) blocks = waves;
+    return (uint32_t)blocks;
+}
+
 // radiance_kernel on a grid of at most cu_count * RADIANCE_BLOCKS_PER_CU workgroups, then radiance_resolve_kernel.
 hipError_t launch_radiance(bool compact, const SceneDev& sc, const RadianceDev& rd, int cu_count, hipStream_t stream);
 

@@ -9,6 +9,7 @@
 #include "launch_dispatch.h"
 #include "radiance_lit_device.h"
 #include "radiance_lit_kernels.h"
+#include "radiance_wave_parts.h"
 
 namespace rayrs {
 
@@ -20,40 +21,18 @@ struct LitStart {
 };
 template <int START>
 RR_DEV LitStart lit_sample_start(const RadianceDev& rd, const LightsDev& lights, const CameraDev& cam, uint32_t ray, uint32_t s) {
-    Rng rng;
-    V3 o, d, first = mk(1.0, 1.0, 1.0);
-    if (START == LIT_START_PIXEL) {
-        const uint32_t pix = (uint32_t)rd.index_base + ray;  // (the image's pixels: below 2^32)
-        const uint32_t row = pix / cam.W, col = pix - row * cam.W;
-        rng = Rng{sample_key(rd.seed, cam, row, col, s), 0};
-        sample_ray(cam, row, col, rng, o, d);
-        return LitStart{rng, o, d, first};
-    }
-    const double* pa = rd.a + (size_t)ray * 3u;
-    const double* pb = rd.b + (size_t)ray * 3u;
-    const V3 a = mk(pa[0], pa[1], pa[2]), b = mk(pb[0], pb[1], pb[2]);
-    rng = Rng{rr_path_key(rd.seed, rd.index_base + ray, (uint64_t)s), 0};
+    SampleStart st = sample_start(QueryStart<START>{}, rd, cam, ray, s);
+    V3 first = mk(1.0, 1.0, 1.0);
     if (START == LIT_START_POINT) {
-        o = v_add(a, v_scale(b, rd.bias));
+        const V3 n = st.d;
         if (lights.n != 0u) {
-            const Scatter ev = lit_lambertian_scatter(mk(1.0, 1.0, 1.0), o, b, rng, lights);
-            d = ev.dir, first = ev.color;
-        } else {  // IRRADIANCE's ray (radiance.hip radiance_sample_start)
-            V3 e1, e2;
-            v_onb(b, e1, e2);
-            const double u = rng.next();
-            const double phi = 2.0 * RR_PI * rng.next();
-            const double su = rr_sqrt(u);
-            const rr_sincos_t sc_phi = rr_sincos(phi);
-            const double x = sc_phi.c * su;
-            const double y = sc_phi.s * su;
-            const double z = rr_sqrt(1.0 - u);
-            d = v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(b, z));
+            const Scatter ev = lit_lambertian_scatter(mk(1.0, 1.0, 1.0), st.o, n, st.rng, lights);
+            st.d = ev.dir, first = ev.color;
+        } else {  // IRRADIANCE's ray
+            st.d = cosine_direction(n, st.rng);
         }
-    } else {
-        o = a, d = b;
     }
-    return LitStart{rng, o, d, first};
+    return LitStart{st.rng, st.o, st.d, first};
 }
 
 // radiance.hip radiance_kernel's wave and its termination argument, turn for turn; a chunk's sum is made in this one lane in
@@ -133,6 +112,7 @@ __global__ void __launch_bounds__(256) radiance_lit_kernel(SceneDev sc, Radiance
                     const uint32_t avail = left < wanted ? (uint32_t)left : wanted;
                     if (need && lanes_below(need_mask) < avail) {
                         item = (uint32_t)base + lanes_below(need_mask);  // (n_items <= 2^20)
+                        // (radiance_wave_parts.h QueryStart::take, written out: called, it moves these kernels' code)
                         ray = item / rd.chunks;
                         s = (item - ray * rd.chunks) * rd.chunk;
                         s_end = rd.samples - s < rd.chunk ? rd.samples : s + rd.chunk;
@@ -170,59 +150,19 @@ __global__ void __launch_bounds__(256) radiance_lit_kernel(SceneDev sc, Radiance
     }
 }
 
-// A ray's chunk sums added in chunk order (the first assigned), scaled by the reciprocal of S, and its query counts added:
-// one thread per ray.
-__global__ void __launch_bounds__(256) radiance_lit_resolve_kernel(RadianceDev rd) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= rd.n) return;
-    const double* p = rd.partial + (size_t)i * rd.chunks * 3u;
-    const uint32_t* pq = rd.partial_queries + (size_t)i * rd.chunks;
-    V3 sum = mk(p[0], p[1], p[2]);
-    uint32_t q = pq[0];
-    for (uint32_t k = 1; k < rd.chunks; k++) {
-        sum = v_add(sum, mk(p[3u * k], p[3u * k + 1u], p[3u * k + 2u]));
-        q += pq[k];
-    }
-    const double inv = 1.0 / (double)rd.samples;
-    if (rd.radiance != nullptr) {
-        double* dst = rd.radiance + (size_t)i * 3u;
-        dst[0] = sum.x * inv, dst[1] = sum.y * inv, dst[2] = sum.z * inv;
-    }
-    if (rd.queries != nullptr) rd.queries[i] = q;
-}
-
-namespace {
-
-template <int START>
-hipError_t launch_lit_start(bool compact, const SceneDev& sc, const RadianceDev& rd, const LightsDev& lights, const CameraDev& cam,
-                            uint32_t blocks, uint32_t lds, hipStream_t stream) {
-    return with_bools([&](auto C, auto E) {
-        auto kernel = &radiance_lit_kernel<decltype(C)::value, decltype(E)::value, START>;
-        const hipError_t e = raise_dynamic_lds(kernel, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, stream, sc, rd, lights, cam);
-        return hipGetLastError();
-    }, compact, sc.exact != 0u);
-}
-
-}  // namespace
+__global__ void __launch_bounds__(256) radiance_lit_resolve_kernel(RadianceDev rd) { radiance_resolve(rd); }
 
 hipError_t launch_radiance_lit(bool compact, const SceneDev& sc, const RadianceDev& rd, const LightsDev& lights, const CameraDev& cam,
                                int start, int cu_count, hipStream_t stream) {
     if (rd.n == 0u) return hipSuccess;
-    const uint32_t lds = lane_stacks_lds_bytes(sc.stack_lds);
-    const uint64_t n_items = (uint64_t)rd.n * rd.chunks;
-    const uint64_t waves = (n_items + 63u) / 64u;  // (a wave takes up to 64 items at its first refill)
-    uint64_t blocks = (uint64_t)(cu_count > 0 ? cu_count : 1) * RADIANCE_BLOCKS_PER_CU;
-    if (blocks > QUERY_LAUNCH_RAYS / 256u) blocks = QUERY_LAUNCH_RAYS / 256u;  // (the stack strip is the queries')
-    if (blocks > waves) blocks = waves;
-    hipError_t e;
-    if (start == LIT_START_PIXEL) e = launch_lit_start<LIT_START_PIXEL>(compact, sc, rd, lights, cam, (uint32_t)blocks, lds, stream);
-    else if (start == LIT_START_POINT) e = launch_lit_start<LIT_START_POINT>(compact, sc, rd, lights, cam, (uint32_t)blocks, lds, stream);
-    else e = launch_lit_start<LIT_START_RAY>(compact, sc, rd, lights, cam, (uint32_t)blocks, lds, stream);
+    const hipError_t e = with_lit_start([&](auto S) {
+        return with_bools([&](auto C, auto E) {
+            return launch_lane_stacks(&radiance_lit_kernel<decltype(C)::value, decltype(E)::value, decltype(S)::value>,
+                                      radiance_grid_blocks(rd, cu_count), sc.stack_lds, stream, sc, rd, lights, cam);
+        }, compact, sc.exact != 0u);
+    }, start);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(radiance_lit_resolve_kernel, dim3((rd.n + 255u) / 256u), dim3(256), 0, stream, rd);
-    return hipGetLastError();
+    return launch_radiance_resolve(radiance_lit_resolve_kernel, rd, stream);
 }
 
 }  // namespace rayrs

@@ -84,16 +84,7 @@ RR_DEV Scatter lit_lambertian_scatter(V3 color_in, V3 position, V3 n, Rng& rng, 
         const V3 q = light_sample(kind, axis, v0, v1, v2, v3, v4, u1, u2);
         l = v_unit(v_sub(q, position));
     } else {  // Pdf::Cosine.generate: lambertian_scatter's direction
-        V3 e1, e2;
-        v_onb(n, e1, e2);
-        const double u = rng.next();
-        const double phi = 2.0 * RR_PI * rng.next();
-        const double su = rr_sqrt(u);
-        const rr_sincos_t sc_phi = rr_sincos(phi);
-        const double x = sc_phi.c * su;
-        const double y = sc_phi.s * su;
-        const double z = rr_sqrt(1.0 - u);
-        l = v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(n, z));
+        l = cosine_direction(n, rng);
     }
     const double ndl = v_dot(n, l);
     double pdf = (double)__builtin_inf();

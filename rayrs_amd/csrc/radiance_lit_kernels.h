@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/rayrs_hip.h"
 #include "layout.h"
 #include "radiance_kernels.h"
@@ -32,6 +34,13 @@ struct LightsDev {
 // bias, n) with albedo (1, 1, 1) -- with K = 0 IRRADIANCE's ray on draws 0 and 1 --; the camera's pixel, sample_ray on draws
 // 0 and 1, draw 2 next.
 constexpr int LIT_START_RAY = 0, LIT_START_POINT = 1, LIT_START_PIXEL = 2;
+// with_lit_start(f, start) calls f(S) with S() the LIT_START_* that `start` is, as launch_dispatch.h's with_bools does for bools.
+template <class F>
+auto with_lit_start(F f, int start) {
+    if (start == LIT_START_PIXEL) return f(std::integral_constant<int, LIT_START_PIXEL>{});
+    if (start == LIT_START_POINT) return f(std::integral_constant<int, LIT_START_POINT>{});
+    return f(std::integral_constant<int, LIT_START_RAY>{});
+}
 
 // radiance_lit_kernel on a grid of at most cu_count * RADIANCE_BLOCKS_PER_CU workgroups, then radiance_lit_resolve_kernel.
 // start: LIT_START_*; cam is read by LIT_START_PIXEL only, rd.a and rd.b by the other two.

@@ -23,38 +23,15 @@ struct SkyStart {
 template <class START>
 RR_DEV SkyStart sky_path_start(const START& start, const RadianceDev& rd, const LightsDev& lights, const SkyDev& sky, const CameraDev& cam,
                                uint32_t ray, uint32_t s) {
-    Rng rng;
-    V3 o, d;
+    SampleStart st = sample_start(start, rd, cam, ray, s);
     DirectBounce first;
     first.shadow = false, first.l_s = mk(0.0, 0.0, 1.0), first.credit = mk(0.0, 0.0, 0.0), first.w_next = 1.0;
-    if (START::KIND == LIT_START_PIXEL) {
-        uint32_t row, col;
-        start.pixel(rd, cam, ray, row, col);
-        rng = Rng{sample_key(rd.seed, cam, row, col, s), 0};
-        sample_ray(cam, row, col, rng, o, d);
-        return SkyStart{rng, o, d, first};
+    if (START::KIND == LIT_START_POINT) {  // IRRADIANCE's ray, then the virtual bounce at the point, whatever K is
+        const V3 n = st.d;
+        st.d = cosine_direction(n, st.rng);
+        first = sky_bounce(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), st.o, n, st.d, st.rng, lights, sky);
     }
-    const double* pa = rd.a + (size_t)ray * 3u;
-    const double* pb = rd.b + (size_t)ray * 3u;
-    const V3 a = mk(pa[0], pa[1], pa[2]), b = mk(pb[0], pb[1], pb[2]);
-    rng = Rng{rr_path_key(rd.seed, rd.index_base + ray, (uint64_t)s), 0};
-    if (START::KIND == LIT_START_POINT) {  // IRRADIANCE's ray (radiance.hip radiance_sample_start)
-        o = v_add(a, v_scale(b, rd.bias));
-        V3 e1, e2;
-        v_onb(b, e1, e2);
-        const double u = rng.next();
-        const double phi = 2.0 * RR_PI * rng.next();
-        const double su = rr_sqrt(u);
-        const rr_sincos_t sc_phi = rr_sincos(phi);
-        const double x = sc_phi.c * su;
-        const double y = sc_phi.s * su;
-        const double z = rr_sqrt(1.0 - u);
-        d = v_add(v_add(v_scale(e1, x), v_scale(e2, y)), v_scale(b, z));
-        first = sky_bounce(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), o, b, d, rng, lights, sky);
-    } else {
-        o = a, d = b;
-    }
-    return SkyStart{rng, o, d, first};
+    return SkyStart{st.rng, st.o, st.d, first};
 }
 
 // radiance_direct_wave.h direct_wave's wave and its termination argument, turn for turn: a lane that holds a path either walks

@@ -1,10 +1,11 @@
 """Per-kernel comparison of the gfx950 code of two builds of the library's device objects (development aid).
 
-usage: python scripts/kernel_disasm_diff.py OLD_DIR NEW_DIR [NAME ...]
+usage: python scripts/kernel_disasm_diff.py [--objects a,b,c] OLD_DIR NEW_DIR [NAME ...]
 
-OLD_DIR / NEW_DIR hold kernels.o, wavefront.o, local_pool.o and film.o of two builds (e.g. a copy of rayrs_amd/csrc/*.o made
+OLD_DIR / NEW_DIR hold the objects to compare (default kernels.o, wavefront.o, local_pool.o and film.o; --objects names others,
+e.g. ao,radiance,radiance_lit,radiance_direct,radiance_sky,film_direct,bake) of two builds (e.g. a copy of rayrs_amd/csrc/*.o made
 before a change, and rayrs_amd/csrc after `make`).  Every kernel whose symbol contains one of NAME (default: the kernels
-a render and rayrs_test_intersect run; `all`: every kernel of the four objects) is disassembled from both builds and compared instruction by instruction, with
+a render and rayrs_test_intersect run; `all`: every kernel of the objects) is disassembled from both builds and compared instruction by instruction, with
 addresses, branch targets, pc-relative symbol offsets and the alignment padding behind a kernel's last instruction
 normalised away.  Exit status 1 when one of them differs."""
 import os
@@ -47,11 +48,14 @@ def disassemble(obj, tmp):
 
 
 def main():
-    old_dir, new_dir = sys.argv[1], sys.argv[2]
-    names = tuple(sys.argv[3:]) or DEFAULT
+    args, objects = sys.argv[1:], OBJECTS
+    if args and args[0] == "--objects":
+        objects, args = tuple(args[1].split(",")), args[2:]
+    old_dir, new_dir = args[0], args[1]
+    names = tuple(args[2:]) or DEFAULT
     same, differ = 0, []
     with tempfile.TemporaryDirectory() as tmp:
-        for o in OBJECTS:
+        for o in objects:
             a = disassemble(os.path.join(old_dir, o + ".o"), tmp)
             b = disassemble(os.path.join(new_dir, o + ".o"), tmp)
             for k in sorted(set(a) | set(b)):

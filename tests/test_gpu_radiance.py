@@ -248,6 +248,41 @@ def test_every_threshold_gives_the_same_bits(name, max_bounces, stack_lds):
     assert f.scene._L.rayrs_lab_radiance_tuning(f.scene._h, 65, 0, 0) == -1
 
 
+def lab_turns(scene, irradiance, a, b, samples, max_bounces, chunk, bias, index_base, fast):
+    """rayrs_lab.h rayrs_lab_radiance_turns: the kernel's instance that also counts its turns.  (queries, turns)."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    queries, turns = np.zeros(len(a), dtype=np.uint32), np.zeros(3, dtype=np.uint64)
+    rayrs_amd._ffi.check(scene._L.rayrs_lab_radiance_turns(scene._h, int(irradiance), a.ctypes.data, b.ctypes.data, len(a), samples, max_bounces,
+                                                          chunk, bias, SEED, index_base, int(fast), queries.ctypes.data, turns.ctypes.data),
+                         "rayrs_lab_radiance_turns")
+    return queries, turns
+
+
+def test_the_turn_counting_instance_makes_the_oracles_queries():
+    """The lab's instance of the kernel answers with query counts and three turn counters, no radiance: the counts are the
+    oracle's, ray for ray, on 130 rays (two full waves and two lanes) and 130 points, S = 5 in chunks of 2 (three chunks, the last
+    short), max_bounces 4.  The counters: a shade turn of a lane ends exactly one ray, so the lane-turns spent shading are the
+    queries; a lane walks or is shaded at most once in a wave's turn, so both together are at most 64 x the waves' turns."""
+    f = family("material_test")
+    a, n, samples, chunk, bounces = schedule_start(), 130, 5, 2, 4
+    for fast in (False, True):
+        values, queries = expected_paths("material_test", bounces, fast=fast, samples=samples, first=a, n=n)
+        want = _radiance.answers(values, queries, chunk)[1]
+        assert (queries == bounces).sum() >= 30 and (queries == 1).sum() >= 200   # (paths cut by the budget, and rays that miss)
+        got, turns = lab_turns(f.scene, False, f.o[a:a + n], f.d[a:a + n], samples, bounces, chunk, 0.0, a, fast)
+        assert np.array_equal(got, want), (fast, np.flatnonzero(got != want)[:5])
+        assert int(turns[2]) == int(want.sum()) and turns[0] % 64 == 0 and turns[1] + turns[2] <= turns[0], (fast, turns)
+    p = floor_grid()[:n]
+    nrm = np.tile((0.0, 1.0, 0.0), (n, 1))
+    values, queries = _radiance.irradiance_paths(f.osc, p, nrm, samples, 1e-4, bounces, SEED)
+    want = _radiance.answers(values, queries, chunk)[1]
+    got, turns = lab_turns(f.scene, True, p, nrm, samples, bounces, chunk, 1e-4, 0, False)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)[:5]
+    assert int(turns[2]) == int(want.sum()) and turns[0] % 64 == 0 and turns[1] + turns[2] <= turns[0], turns
+    # and the same counts from the kernel that does not count turns
+    assert np.array_equal(f.scene.irradiance(p, nrm, samples=samples, bias=1e-4, max_bounces=bounces, seed=SEED, sample_chunk=chunk, queries=True)[1], got)
+
+
 # ------------------------------------------------------------------------------------------------------ slices, launches, outputs
 
 def test_a_slice_with_its_index_base_is_the_slice_of_the_whole_also_across_launches():
