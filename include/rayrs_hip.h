@@ -1151,6 +1151,138 @@ int rayrs_scene_sky_table(rayrs_scene* scene, double* cells /* (h-1)*(w-1), may 
 int rayrs_scene_sky_sample(rayrs_scene* scene, const double* u /* n*2 */, uint64_t n, double* dir /* n*3 */);
 int rayrs_scene_sky_density(rayrs_scene* scene, const double* dir /* n*3 */, uint64_t n, double* p);
 
+/* ---- radiance queries with a mesh-light group among the lights: DIRECT LIGHTING's lamps are spheres and axis-aligned rectangles,
+ * at most RAYRS_MAX_LIGHTS of them, because every density there sums over the whole list.  A scene's lamp is as often a mesh: a
+ * tube, a tilted panel, a glowing object.  Here any number of listed triangles together are ONE more light of DIRECT LIGHTING /
+ * SKY SAMPLING: it is chosen like a lamp, its points are drawn uniformly by area from a prefix table in device memory, and it is
+ * weighted by the balance heuristic in AREA measure at the first visible point, so no density ever sums over the list.  The
+ * kernels are a unit of their own (radiance_mesh.hip); nothing above changes.
+ *
+ * MESH LIGHTS, specified to the operation.  Everything is f64 and unfused; the draws are taken from the path's rng in program
+ * order; the elementary functions are rayrs_numeric.h's.
+ *
+ * The handle.  rayrs_mesh_lights_create makes a group of the n_tris triangles `tris` (a HOST array of object indices in the
+ * numbering rayrs_scene_intersect returns; it is copied).  The handle is bound to its scene and must be destroyed before it.  It
+ * owns the table on the host and its device copy, which is uploaded once, at the handle's first call that launches; a handle of
+ * a host-only scene (device -1) serves the three host calls below.  n_tris == 0 is a legal, empty group.
+ * rayrs_mesh_lights_destroy waits for the scene's radiance work that may still read the device copy, then frees it.  Refusals at
+ * creation, in this order.  RAYRS_INVALID_ARG: a NULL scene or out; tris == NULL with n_tris > 0; an index >= the object count;
+ * a duplicate index; n_tris >= 2^31.  RAYRS_UNSUPPORTED: an index that names a sphere or a plane; a listed triangle that emits
+ * and whose material is not LambertianDiffuse, Reflect or Glass (DIRECT LIGHTING's material rule, unchanged: a dark triangle may
+ * be anything); with n_tris >= 1, a total area T that is not > 0.0 or not finite.
+ *
+ * The table.  N = n_tris entries in list order.  For entry j, p1, p2, p3 are the host scene's f64 vertices and
+ *     e1 = p2 - p1;  e2 = p3 - p1;  nrm = e1.cross(e2)            Triangle::new's own arithmetic (geometry.rs:341-353)
+ *     n_j = nrm.unit();  A_j = nrm.mag() / 2.0                    (mag = rr_sqrt(nrm . nrm); unit multiplies by 1.0 / mag)
+ *     P[j] = the inclusive prefix of A in list order: the first assigned, then one add per entry
+ *     T = P[N-1]
+ * Beside each entry the table keeps the slot the closest-hit walk reports for that triangle, and a bitmap over the scene's
+ * primitive slots says which are listed.  A zero-area triangle is legal: the search below never lands on it unless it is the
+ * fall-through entry, and there IEEE gives 0 / 0 -- the NaN direction fails ndl_s > 0.0, as SKY SAMPLING's empty cell does.
+ *
+ * mesh_sample(u1, u2):
+ *     ty = u1 * T;  j = the first index with P[j] > ty, or N-1 if there is none
+ *     below = j > 0 ? P[j-1] : 0.0;  r = (ty - below) / A_j
+ *     su = rr_sqrt(r);  b0 = 1.0 - su;  b1 = su * (1.0 - u2);  b2 = su * u2
+ *     q = (p1 * b0 + p2 * b1) + p3 * b2                           (per component)
+ * u1 chooses the triangle and is rescaled for the point, as sky_sample rescales its row draw.
+ *
+ * p_tri(position, j, q):
+ *     l_s = (q - position).unit()
+ *     p_tri = (position - q).mag2() / (|n_j . l_s| * T)
+ * the solid-angle density at `position` of mesh_sample's points AT q: 1 / T per area, times distance^2 / cosine.  It prices the
+ * one point, not the direction: other listed triangles crossed by the same line are not in it.
+ *
+ * The turn is DIRECT LIGHTING's, or SKY SAMPLING's with sky = 1.  G = 1 if N >= 1, else 0; M = K + G + sky lights: the lamps are
+ * indices 0 .. K-1, the group is K, the sky is last.  With G = 1 every diffuse bounce has the three draws, whatever K and sky are:
+ *     b = rng.next();  u1 = rng.next();  u2 = rng.next()
+ *     k = min((uint32)(b * (double)M), M - 1)
+ *     p_R(position, l) = (the lamps' p_k in list order, the first assigned, then, with sky = 1, += p_env(l) last -- with K = 0,
+ *         p_env assigned) / (double)M; with K = 0 and sky = 0 it is 0.0: the lamps' and the sky's density, the group's not in it
+ *     if k == K (the group):
+ *         (j, q) = mesh_sample(u1, u2);  l_s and p_tri as above;  ndl_s = normal . l_s
+ *         if ndl_s > 0.0:
+ *             den = p_tri / (double)M + ndl_s * RR_FRAC_1_PI
+ *             if den < +inf:
+ *                 C = ((albedo * RR_FRAC_1_PI) * ndl_s) / den
+ *                 hit_s = Bvh::intersect(Ray{position, l_s}, z_near, z_far)       one query, counted
+ *                 if hit_s is Hit and its object IS triangle j:  light = light + (throughput * C) * emit of that triangle
+ *         anything else in front earns nothing: another listed triangle, a lamp, and a Miss even with the sky on
+ *     else (a lamp, or the sky):
+ *         l_s as in DIRECT LIGHTING / SKY SAMPLING;  den = p_R(position, l_s) + ndl_s * RR_FRAC_1_PI;  the rest unchanged:
+ *         credited on a listed LAMP, or on a Miss with sky = 1; meeting a listed triangle earns nothing
+ *     l = ev.ray.direction;  pc = (normal . l) * RR_FRAC_1_PI;  pr = p_R(position, l)
+ *     w_next = pc / (pc + pr) if pr > 0.0 else 1.0                the weight of a listed lamp, or of the sky, met next
+ *     the path keeps pc, and that its ray leaves a diffuse bounce
+ * At the next hit, where ev scatters, with Ray{o, d} the path's ray, t the hit's and normal the hit's (Triangle::normal):
+ *     if obj is a listed triangle:
+ *         if the ray left a diffuse bounce:
+ *             p = (o - ray.point(t)).mag2() / (|normal . d| * T)
+ *             wt = pc / (pc + p / (double)M) if p > 0.0 else 1.0  (a NaN p: 1.0)
+ *             e = emit * wt
+ *         else e = emit                                           (a first ray, or a bounce that is not diffuse: weight 1)
+ *     else if obj is a listed lamp: e = emit * w                  as before
+ *     else e = emit                                               unlisted objects keep weight 1, emissive triangles outside
+ *                                                                 the group included
+ * A Miss of the path's own ray is SKY SAMPLING's (background * w) with sky = 1 and the unlit one with sky = 0.  IRRADIANCE's
+ * virtual bounce is DIRECT LIGHTING's with this turn (draws 2, 3 and 4, the path going on at draw 5, its first ray leaving a
+ * diffuse bounce); it is present whenever K + G + sky >= 1.  The overflow guard, the material rule for listed lamps,
+ * queries_i (shadow rays counted), max_bounces == 0 and the image form are DIRECT LIGHTING's.
+ *
+ * Why it is unbiased.  Light leaving a first-visible point y of a listed triangle along l towards a diffuse point is collected
+ * by two techniques only.  The group's arm, when it draws y: its solid-angle density there is p_tri / M -- drawing a point that
+ * is hidden, by anything, earns nothing, so hidden crossings of the same line do not count.  And the continuation, when the
+ * cosine arm draws l: density pc.  The two weights are p / (p + pc) with p = p_tri / M -- C is brdf * cosine / p times that --
+ * and pc / (p + pc), both evaluated at that same point, and they sum to 1 up to the rounding between q and the hit point.  Lamp-
+ * and sky-drawn samples never collect a triangle and group-drawn samples never collect a lamp or the sky, so DIRECT LIGHTING's
+ * and SKY SAMPLING's argument stands as written for the lamps and the sky, with the new M in their arm's probability.
+ *
+ * When the group is empty (mesh == NULL, or a handle of no triangles): G = 0, and the entry points below return, bit for bit and
+ * count for count, what their _direct counterparts return with sky = 0 and what their _sky counterparts return with sky = 1 --
+ * and therefore the unlit answers with K = 0 and no sky.
+ *
+ * rayrs_scene_radiance_mesh, rayrs_scene_irradiance_mesh, their _launch forms and rayrs_render_mesh take the arguments of their
+ * _direct counterparts plus the group and sky (0 or 1).  Refusals: DIRECT LIGHTING's in its order (SKY SAMPLING's with sky = 1);
+ * a handle of another scene, and a sky above 1, join the RAYRS_INVALID_ARG group; RAYRS_NO_DEVICE comes last.  The lamps stay in
+ * the kernel arguments and the group is two device pointers and T beside them, so a _launch form allocates and copies nothing
+ * after a handle's first device call on a given walk.  All twenty-four path kernels of the unit (both record formats, both
+ * walks, without and with the sky, the three starts) use at most 256 VGPRs, no scratch and no static LDS.
+ *
+ * Three calls on the host, which need no device: the areas A_j in list order (N f64, may be NULL) and T; mesh_sample of n pairs
+ * (u1, u2) -> j and q; p_tri of n (position, j, q).  The last two refuse an empty group as RAYRS_UNSUPPORTED, and the last a j
+ * that is not below N as RAYRS_INVALID_ARG. */
+typedef struct rayrs_mesh_lights rayrs_mesh_lights;
+int rayrs_mesh_lights_create(rayrs_scene* scene, const uint32_t* tris, uint64_t n_tris, rayrs_mesh_lights** out);
+void rayrs_mesh_lights_destroy(rayrs_mesh_lights* mesh);
+int rayrs_mesh_lights_table(const rayrs_mesh_lights* mesh, double* areas /* N, may be NULL */, double* total);
+int rayrs_mesh_lights_sample(const rayrs_mesh_lights* mesh, const double* u /* n*2 */, uint64_t n, uint32_t* j /* n */,
+                             double* q /* n*3 */);
+int rayrs_mesh_lights_density(const rayrs_mesh_lights* mesh, const double* position /* n*3 */, const uint32_t* j /* n */,
+                              const double* q /* n*3 */, uint64_t n, double* p);
+int rayrs_scene_radiance_mesh(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                              uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base, uint32_t fast_traversal,
+                              const uint32_t* lights, uint32_t n_lights, const rayrs_mesh_lights* mesh /* may be NULL: empty */,
+                              uint32_t sky, double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */);
+int rayrs_scene_radiance_mesh_launch(rayrs_scene* scene, const double* origin, const double* direction, uint64_t n, uint32_t samples,
+                                     uint32_t max_bounces, uint32_t sample_chunk, uint64_t seed, uint64_t index_base,
+                                     uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                     const rayrs_mesh_lights* mesh /* may be NULL: empty */, uint32_t sky,
+                                     double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_scene_irradiance_mesh(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                                uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                const rayrs_mesh_lights* mesh /* may be NULL: empty */, uint32_t sky,
+                                double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */);
+int rayrs_scene_irradiance_mesh_launch(rayrs_scene* scene, const double* position, const double* normal, uint64_t n, uint32_t samples,
+                                       uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
+                                       uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                                       const rayrs_mesh_lights* mesh /* may be NULL: empty */, uint32_t sky,
+                                       double* radiance /* may be NULL */, uint32_t* queries /* may be NULL */, void* hip_stream);
+int rayrs_render_mesh(rayrs_scene* scene, const rayrs_camera* camera, uint64_t seed, uint32_t samples, uint32_t max_bounces,
+                      uint32_t sample_chunk, uint32_t fast_traversal, const uint32_t* lights, uint32_t n_lights,
+                      const rayrs_mesh_lights* mesh /* may be NULL: empty */, uint32_t sky, double* out_rgb /* H*W*3 */,
+                      uint32_t* queries /* H*W, may be NULL */);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * DIRECT-LIT FILMS.  A film whose passes are direct-lit: rayrs_film_create_direct makes a film of DIRECT LIGHTING's paths,
  * rayrs_film_create_sky one of SKY SAMPLING's (lights, n_lights name the lamps, the sky is always on, n_lights == 0 is legal: the
@@ -1304,7 +1436,8 @@ int rayrs_bake_state_set(rayrs_bake* bake, const void* in_host, uint64_t bytes);
  * rayrs_scene_irradiance_sky, their _launch forms, rayrs_render_sky, rayrs_scene_sky_table, rayrs_scene_sky_sample and
  * rayrs_scene_sky_density (SKY SAMPLING), and with rayrs_film_create_direct and rayrs_film_create_sky (DIRECT-LIT FILMS), and with
  * rayrs_bake_* and its three structs (BAKE; they are not in the layout table below: all their fields are 4 or 8 bytes wide and
- * naturally aligned).  The
+ * naturally aligned), and with rayrs_mesh_lights_*, rayrs_scene_radiance_mesh, rayrs_scene_irradiance_mesh, their _launch forms
+ * and rayrs_render_mesh (MESH LIGHTS).  The
  * layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised

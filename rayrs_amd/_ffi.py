@@ -38,6 +38,9 @@ SYMBOLS = [
     "rayrs_scene_irradiance_direct_launch", "rayrs_render_direct",
     "rayrs_scene_radiance_sky", "rayrs_scene_radiance_sky_launch", "rayrs_scene_irradiance_sky", "rayrs_scene_irradiance_sky_launch",
     "rayrs_render_sky", "rayrs_scene_sky_table", "rayrs_scene_sky_sample", "rayrs_scene_sky_density",
+    "rayrs_mesh_lights_create", "rayrs_mesh_lights_destroy", "rayrs_mesh_lights_table", "rayrs_mesh_lights_sample",
+    "rayrs_mesh_lights_density", "rayrs_scene_radiance_mesh", "rayrs_scene_radiance_mesh_launch", "rayrs_scene_irradiance_mesh",
+    "rayrs_scene_irradiance_mesh_launch", "rayrs_render_mesh",
     "rayrs_film_create_direct", "rayrs_film_create_sky",
     "rayrs_bake_create", "rayrs_bake_destroy", "rayrs_bake_render", "rayrs_bake_render_adaptive", "rayrs_bake_read",
     "rayrs_bake_point_samples", "rayrs_bake_noise", "rayrs_bake_status_get", "rayrs_bake_state_bytes", "rayrs_bake_state_get",
@@ -314,6 +317,21 @@ def lib():
                        ("rayrs_scene_sky_table", [vp, vp, vp]),
                        ("rayrs_scene_sky_sample", [vp, vp, C.c_uint64, vp]),
                        ("rayrs_scene_sky_density", [vp, vp, C.c_uint64, vp]),
+                       ("rayrs_mesh_lights_create", [vp, vp, C.c_uint64, C.POINTER(vp)]),
+                       ("rayrs_mesh_lights_table", [vp, vp, vp]),
+                       ("rayrs_mesh_lights_sample", [vp, vp, C.c_uint64, vp, vp]),
+                       ("rayrs_mesh_lights_density", [vp, vp, vp, vp, C.c_uint64, vp]),
+                       ("rayrs_scene_radiance_mesh", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                      C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]),
+                       ("rayrs_scene_radiance_mesh_launch", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                             C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]),
+                       ("rayrs_scene_irradiance_mesh", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64,
+                                                        C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp]),
+                       ("rayrs_scene_irradiance_mesh_launch", [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
+                                                               C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp,
+                                                               vp]),
+                       ("rayrs_render_mesh", [vp, C.POINTER(CameraDesc), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp,
+                                              C.c_uint32, vp, C.c_uint32, vp, vp]),
                        ("rayrs_film_create_direct", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, C.POINTER(vp)]),
                        ("rayrs_film_create_sky", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, C.POINTER(vp)]),
                        ("rayrs_bake_create", [vp, vp, vp, C.c_uint64, C.POINTER(BakeParams), vp, C.c_uint32, C.POINTER(vp)]),
@@ -331,6 +349,9 @@ def lib():
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):
         L.rayrs_history_destroy.restype = None
+    if hasattr(L, "rayrs_mesh_lights_destroy"):
+        L.rayrs_mesh_lights_destroy.argtypes = [vp]
+        L.rayrs_mesh_lights_destroy.restype = None
     if hasattr(L, "rayrs_bake_destroy"):
         L.rayrs_bake_destroy.restype = None
         L.rayrs_bake_state_bytes.restype = C.c_uint64

@@ -495,9 +495,11 @@ class Scene:
     # ---- radiance queries (include/rayrs_hip.h RADIANCE QUERY, IRRADIANCE)
 
     def _radiance(self, name, a, b, samples, max_bounces, sample_chunk, bias, seed, index_base, fast_traversal, queries, lights=None,
-                  direct=False):
+                  direct=False, mesh=None):
         if direct and lights is None:
             raise ValueError("direct=True needs a light list (lights=[...])")
+        if mesh is not None and not direct:
+            raise ValueError("mesh=... needs direct=True (a mesh-light group is a light of direct lighting)")
         torch, a, b, _, n = self._query_inputs(a, b)
         if int(samples) < 1:
             raise ValueError("samples must be at least 1")
@@ -509,8 +511,10 @@ class Scene:
             sky = bool(direct) and bool((lights == SKY).any())   # (SKY SAMPLING: the sky beside the lamps, named once or often)
             if sky:
                 lights = lights[lights != SKY]
-            name += "_sky" if sky else "_direct" if direct else "_lit"
+            name += "_mesh" if mesh is not None else "_sky" if sky else "_direct" if direct else "_lit"
             args += (lights.ctypes.data if len(lights) else None, len(lights))
+            if mesh is not None:  # (MESH LIGHTS: the group and the sky as arguments of their own)
+                args += (mesh._handle(), int(sky))
         if torch is None:
             rad, cnt = np.zeros((m, 3)), np.zeros(m, dtype=np.uint32)
             a, b = (x if n else np.zeros((1, 3)) for x in (a, b))
@@ -525,7 +529,8 @@ class Scene:
         return (rad[:n], cnt[:n]) if queries else rad[:n]
 
     def radiance(self, origins, directions, samples: int = 1, max_bounces: int = 50, seed: int = 0x5EED, index_base: int = 0,
-                 sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None, direct: bool = False):
+                 sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None,
+                 mesh: Optional["MeshLights"] = None, direct: bool = False):
         """The path-traced light arriving along every ray (origins[i], directions[i]), the mean of `samples` paths of the
         render's radiance loop: radiance (n, 3) f64, and with queries also the number of closest-hit queries the ray's paths
         made, (n,) uint32.  Rays are used as given.  Sample s of ray i draws from the key of (seed, index_base + i, s), so a
@@ -535,13 +540,15 @@ class Scene:
         computes).  direct=True (with lights): every diffuse bounce keeps its own direction and sends one more ray towards a
         sampled point of a light, the two weighted by the balance heuristic (include/rayrs_hip.h DIRECT LIGHTING); with SKY in
         the list the environment map is one more of those lights, its directions drawn in proportion to its brightness
-        (include/rayrs_hip.h SKY SAMPLING; lights=[SKY] is the sky alone).  Inputs and where the answers live as intersect()."""
+        (include/rayrs_hip.h SKY SAMPLING; lights=[SKY] is the sky alone).  mesh (with direct=True): a group of emissive
+        triangles of this scene (mesh_lights()) as one more of those lights, its points drawn uniformly by area
+        (include/rayrs_hip.h MESH LIGHTS; lights may then be empty).  Inputs and where the answers live as intersect()."""
         return self._radiance("rayrs_scene_radiance", origins, directions, samples, max_bounces, sample_chunk, None, seed, index_base,
-                              fast_traversal, queries, lights, direct)
+                              fast_traversal, queries, lights, direct, mesh)
 
     def irradiance(self, points, normals, samples: int = 64, bias: float = 0.0, max_bounces: int = 50, seed: int = 0x5EED,
                    index_base: int = 0, sample_chunk: int = 0, fast_traversal: bool = False, queries: bool = False, lights=None,
-                   direct: bool = False):
+                   mesh: Optional["MeshLights"] = None, direct: bool = False):
         """The cosine-weighted mean of the light arriving at points[i] around normals[i], E / pi, from `samples` paths that
         leave points[i] + normals[i] * bias in ambient_occlusion()'s directions: (n, 3) f64 (multiply by pi for the
         irradiance; a Lambertian texel of albedo rho radiates rho times the value).  Points and normals are used as given.
@@ -550,7 +557,14 @@ class Scene:
         and the point sends a shadow ray of its own, as a diffuse bounce does.  The other arguments, inputs and answers as
         radiance()."""
         return self._radiance("rayrs_scene_irradiance", points, normals, samples, max_bounces, sample_chunk, bias, seed, index_base,
-                              fast_traversal, queries, lights, direct)
+                              fast_traversal, queries, lights, direct, mesh)
+
+    # ---- a mesh-light group (include/rayrs_hip.h MESH LIGHTS)
+
+    def mesh_lights(self, tris) -> "MeshLights":
+        """A mesh-light group of this scene: `tris` are the object indices of its triangles (mesh_emitters()), each at most
+        once.  What radiance(), irradiance() and render_lit() take as mesh=...; close it before the scene."""
+        return MeshLights(self, tris)
 
     # ---- the sky as a light (include/rayrs_hip.h SKY SAMPLING): host only, a scene without a device has them too
 
@@ -756,24 +770,117 @@ def emitters(objects) -> List[int]:
     return out
 
 
+def mesh_emitters(objects) -> List[int]:
+    """The indices, in the scene's numbering, of the emissive triangles of an object list (a mesh: one index per triangle): what
+    Scene.mesh_lights() takes."""
+    out, index = [], 0
+    for o in flatten_objects(objects):
+        if o.kind == "mesh":
+            n = int(o.idx.shape[0])
+            if o.emission.emissive:
+                out.extend(range(index, index + n))
+            index += n
+            continue
+        if o.kind == "triangle" and o.emission.emissive:
+            out.append(index)
+        index += 1
+    return out
+
+
+class MeshLights:
+    """A mesh-light group (include/rayrs_hip.h MESH LIGHTS): listed triangles of one scene that together are one more light of
+    direct lighting.  The table lives on the host; its device copy is made by the first call that launches."""
+
+    def __init__(self, scene: Scene, tris):
+        tris = _light_list(tris)
+        self._L, self._h, self._scene = scene._L, None, scene   # (the scene outlives the handle)
+        h = C.c_void_p()
+        _ffi.check(self._L.rayrs_mesh_lights_create(scene._h, tris.ctypes.data if len(tris) else None, len(tris), C.byref(h)),
+                   "rayrs_mesh_lights_create")
+        self._h, self._n = h, len(tris)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the mesh-light group is closed")
+        return self._h
+
+    def __len__(self):
+        return self._n
+
+    def areas(self):
+        """A_j of every entry, in list order: (N,) f64."""
+        out, total = np.zeros(max(self._n, 1)), C.c_double()
+        _ffi.check(self._L.rayrs_mesh_lights_table(self._handle(), out.ctypes.data, C.addressof(total)), "rayrs_mesh_lights_table")
+        return out[:self._n]
+
+    @property
+    def total(self) -> float:
+        """T, the group's area."""
+        total = C.c_double()
+        _ffi.check(self._L.rayrs_mesh_lights_table(self._handle(), None, C.addressof(total)), "rayrs_mesh_lights_table")
+        return total.value
+
+    def sample(self, u):
+        """mesh_sample(u1, u2) of every row of u (n, 2): (j (n,) uint32, q (n, 3) f64), points uniform by area over the group."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.ndim != 2 or u.shape[1] != 2:
+            raise ValueError("u must be (n, 2)")
+        m = max(len(u), 1)
+        j, q = np.zeros(m, dtype=np.uint32), np.zeros((m, 3))
+        _ffi.check(self._L.rayrs_mesh_lights_sample(self._handle(), u.ctypes.data if len(u) else q.ctypes.data, len(u), j.ctypes.data,
+                                                    q.ctypes.data), "rayrs_mesh_lights_sample")
+        return j[:len(u)], q[:len(u)]
+
+    def density(self, positions, j, q):
+        """p_tri of every (position, j, q): the solid-angle density at the position of sample()'s points at q, (n,) f64."""
+        p = np.ascontiguousarray(positions, dtype=np.float64)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        j = _light_list(j)
+        if p.ndim != 2 or p.shape[1] != 3 or q.shape != p.shape or len(j) != len(p):
+            raise ValueError("positions and q must be (n, 3), j (n,)")
+        m = max(len(p), 1)
+        out = np.zeros(m)
+        pad = np.zeros((1, 3))
+        _ffi.check(self._L.rayrs_mesh_lights_density(self._handle(), (p if len(p) else pad).ctypes.data,
+                                                     (j if len(p) else np.zeros(1, dtype=np.uint32)).ctypes.data,
+                                                     (q if len(p) else pad).ctypes.data, len(p), out.ctypes.data),
+                   "rayrs_mesh_lights_density")
+        return out[:len(p)]
+
+    def close(self):
+        if self._h is not None:
+            self._L.rayrs_mesh_lights_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def render_lit(scene: Scene, camera: Camera, samples: int, lights, max_bounces: int = 50, seed: int = 0x5EED, sample_chunk: int = 0,
-               fast_traversal: bool = False, queries: bool = False, direct: bool = False):
+               fast_traversal: bool = False, queries: bool = False, mesh: Optional[MeshLights] = None, direct: bool = False):
     """The view's radiance with light sampling (include/rayrs_hip.h LIGHT SAMPLING, the image form): (H, W, 3) f64, the mean of
     `samples` paths per pixel whose diffuse surfaces sample `lights` half of the time; with queries also the (H, W) uint32
     closest-hit queries per pixel.  With an empty list the frame is render(..., out_f64=True)'s, bit for bit.  direct=True:
     DIRECT LIGHTING's image form instead, a shadow ray per diffuse bounce beside the surface's own direction; with SKY in the
-    list, SKY SAMPLING's: the environment map is one more of the lights."""
+    list, SKY SAMPLING's: the environment map is one more of the lights; with mesh (a Scene.mesh_lights() group), MESH LIGHTS':
+    its triangles are one more of them."""
     if direct and lights is None:
         raise ValueError("direct=True needs a light list (lights=[...])")
+    if mesh is not None and not direct:
+        raise ValueError("mesh=... needs direct=True (a mesh-light group is a light of direct lighting)")
     H, W = camera.y_pixels(), camera.x_pixels()
     lights = _light_list(lights)
     sky = bool(direct) and bool((lights == SKY).any())
     if sky:
         lights = lights[lights != SKY]
     out, cnt = np.zeros((H, W, 3)), np.zeros((H, W), dtype=np.uint32)
-    name = "rayrs_render_sky" if sky else "rayrs_render_direct" if direct else "rayrs_render_lit"
+    name = "rayrs_render_mesh" if mesh is not None else "rayrs_render_sky" if sky else "rayrs_render_direct" if direct else "rayrs_render_lit"
+    extra = () if mesh is None else (mesh._handle(), int(sky))
     _ffi.check(getattr(scene._L, name)(scene._h, C.byref(camera.desc), int(seed), int(samples), int(max_bounces), int(sample_chunk),
-                                       int(bool(fast_traversal)), lights.ctypes.data if len(lights) else None, len(lights),
+                                       int(bool(fast_traversal)), lights.ctypes.data if len(lights) else None, len(lights), *extra,
                                        out.ctypes.data, cnt.ctypes.data), name)
     return (out, cnt) if queries else out
 

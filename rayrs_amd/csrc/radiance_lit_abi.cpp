@@ -12,11 +12,11 @@
 #include "radiance_direct_kernels.h"
 #include "radiance_lit_host.hpp"
 #include "radiance_lit_kernels.h"
+#include "radiance_mesh_kernels.h"
 #include "radiance_sky_kernels.h"
 #include "scene_internal.hpp"
 
 namespace rayrs {
-namespace {
 
 // The depth-first slot of every object (the inverse of flat.prim_object), made once.
 const std::vector<uint32_t>& lit_object_prim(rayrs_scene* scene) {
@@ -36,6 +36,8 @@ const uint32_t* prim_record(const rayrs_scene* scene, uint32_t p) {
 uint32_t lit_prim_tag(const rayrs_scene* scene, uint32_t p) {
     return prim_record(scene, p)[(scene->flat.compact ? PRIM_DWORDS_COMPACT : PRIM_DWORDS_FULL) - 1u];
 }
+
+namespace {
 
 // DIRECT LIGHTING's material rule on a list whose indices are checked (true: refuse).  A listed object that emits must have a
 // material whose scatter has no NoScatter path -- LambertianDiffuse, Reflect, Glass (material.rs: Refract and the Cook-Torrance
@@ -96,6 +98,7 @@ int lit_check(rayrs_scene* scene, const void* a, const void* b, const void* radi
     if (!scene || !a || !b || (!radiance && !queries)) return RAYRS_INVALID_ARG;
     if (c.samples == 0u || c.fast_traversal > 1u || extra_invalid) return RAYRS_INVALID_ARG;
     RAYRS_TRY(lit_list_invalid(scene, c));
+    if (c.mesh && c.mesh->scene != scene) return RAYRS_INVALID_ARG;
     if (c.samples > SLOT_SAMPLE_MASK || c.max_bounces > 8000u || extra_unsupported) return RAYRS_UNSUPPORTED;
     const uint64_t path_queries = c.direct ? 2ull * c.max_bounces + 1u : c.max_bounces;
     if ((uint64_t)c.samples * path_queries >= (1ull << 32)) return RAYRS_UNSUPPORTED;
@@ -173,6 +176,10 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
     SkyDev sky;
     std::memset(&sky, 0, sizeof(sky));
     if (c.sky) RAYRS_TRY(sky_device_table(scene, &sky));  // (uploaded by the scene's first sky call, then kept)
+    MeshDev mesh;
+    std::memset(&mesh, 0, sizeof(mesh));
+    const bool grouped = c.mesh && c.mesh->n != 0u;  // (an empty group: DIRECT LIGHTING's call, or SKY SAMPLING's)
+    if (grouped) RAYRS_TRY(mesh_device_table(c.mesh, &mesh));  // (uploaded by the handle's first call, then kept)
     if (c.max_bounces == 0u) {  // the loop runs no turn: +0 and no query, whatever the scene
         if (radiance) HIP_TRY(hipMemsetAsync(radiance, 0, n * 3u * sizeof(double), stream));
         if (queries) HIP_TRY(hipMemsetAsync(queries, 0, n * sizeof(uint32_t), stream));
@@ -195,7 +202,8 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
         rd.radiance = radiance ? radiance + base * 3u : nullptr;
         rd.queries = queries ? queries + base : nullptr;
         HIP_TRY(hipMemsetAsync(rd.cursor, 0, sizeof(unsigned long long), stream));
-        if (c.sky) HIP_TRY(launch_radiance_sky(scene->flat.compact, sc, rd, lights, slots, sky, cam, c.start, scene->cu_count, stream));
+        if (grouped) HIP_TRY(launch_radiance_mesh(scene->flat.compact, sc, rd, lights, slots, mesh, sky, c.sky, cam, c.start, scene->cu_count, stream));
+        else if (c.sky) HIP_TRY(launch_radiance_sky(scene->flat.compact, sc, rd, lights, slots, sky, cam, c.start, scene->cu_count, stream));
         else if (c.direct) HIP_TRY(launch_radiance_direct(scene->flat.compact, sc, rd, lights, slots, cam, c.start, scene->cu_count, stream));
         else HIP_TRY(launch_radiance_lit(scene->flat.compact, sc, rd, lights, cam, c.start, scene->cu_count, stream));
     }

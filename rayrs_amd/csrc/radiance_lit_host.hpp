@@ -1,12 +1,30 @@
-// radiance_lit_host.hpp -- what the three units of entry points that take a light list share (radiance_lit_abi.cpp: LIGHT SAMPLING,
-// radiance_direct_abi.cpp: DIRECT LIGHTING, radiance_sky_abi.cpp: SKY SAMPLING): a call's description and its way from the refusals
-// through the launches, all in radiance_lit_abi.cpp.  A call differs between the three in `direct` and `sky` alone.
+// radiance_lit_host.hpp -- what the four units of entry points that take a light list share (radiance_lit_abi.cpp: LIGHT SAMPLING,
+// radiance_direct_abi.cpp: DIRECT LIGHTING, radiance_sky_abi.cpp: SKY SAMPLING, radiance_mesh_abi.cpp: MESH LIGHTS): a call's
+// description and its way from the refusals through the launches, all in radiance_lit_abi.cpp.  A call differs between them in
+// `direct`, `sky` and `mesh` alone.
 #pragma once
+#include <vector>
+
 #include "../../include/rayrs_hip.h"
+#include "device_mem.hpp"
 #include "radiance_direct_kernels.h"
 #include "radiance_lit_kernels.h"
+#include "radiance_mesh_table.h"
 #include "radiance_sky_table.h"
 #include "scene_internal.hpp"
+
+// A mesh-light group (include/rayrs_hip.h MESH LIGHTS): bound to its scene, it owns the host table (radiance_mesh_table.h: P,
+// the records; the bitmap over the scene's primitive slots) and the device copy, uploaded at the first call that launches.
+struct rayrs_mesh_lights {
+    rayrs_scene* scene = nullptr;
+    uint32_t n = 0;
+    double total = 0.0;
+    std::vector<double> table;     // mesh_table_bytes(n) / 8 doubles; empty with n == 0
+    std::vector<uint32_t> listed;
+    bool uploaded = false;
+    rayrs::DevBuf d_table, d_listed;
+    ~rayrs_mesh_lights();  // waits for the scene's radiance work, which may still read the device copy (radiance_mesh_abi.cpp)
+};
 
 namespace rayrs {
 
@@ -21,6 +39,8 @@ struct LitCall {
     uint32_t n_lights;
     bool direct;  // DIRECT LIGHTING: radiance_direct.hip's kernels, its overflow guard and its material rule
     bool sky;     // SKY SAMPLING (with direct): radiance_sky.hip's kernels, the sky one more light; an empty table is refused
+    // MESH LIGHTS (with direct): a handle of another scene is refused; one of N >= 1 triangles takes radiance_mesh.hip's kernels
+    const rayrs_mesh_lights* mesh = nullptr;
 };
 
 // the four ray and point entry points, and the image form, of either unit
@@ -37,6 +57,16 @@ LightsDev lights_resolve(rayrs_scene* scene, const LitCall& c);
 LightSlotsDev direct_slots(rayrs_scene* scene, const LitCall& c);
 int lit_scratch_begin(rayrs_scene* scene, const SceneDev& sc, hipStream_t stream, RadianceDev* rd);
 int lit_scratch_end(rayrs_scene* scene, hipStream_t stream);
+
+// The depth-first slot of every object (the inverse of flat.prim_object, made once), and the tag of the primitive in a slot and
+// its record (layout.h).
+const std::vector<uint32_t>& lit_object_prim(rayrs_scene* scene);
+const uint32_t* prim_record(const rayrs_scene* scene, uint32_t p);
+uint32_t lit_prim_tag(const rayrs_scene* scene, uint32_t p);
+
+// The group as the kernels take it, with the device copy, uploaded at the handle's first call (the scene's device is current;
+// mesh->n >= 1) (radiance_mesh_abi.cpp).
+int mesh_device_table(const rayrs_mesh_lights* mesh, MeshDev* out);
 
 // The sky's table of the host scene's HDRI, built at the first call (radiance_sky_abi.cpp); `table` is a host pointer.
 SkyDev sky_host_table(rayrs_scene* scene);
