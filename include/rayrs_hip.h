@@ -1420,6 +1420,53 @@ uint64_t rayrs_bake_state_bytes(const rayrs_bake* bake);
 int rayrs_bake_state_get(rayrs_bake* bake, void* out_host, uint64_t cap);
 int rayrs_bake_state_set(rayrs_bake* bake, const void* in_host, uint64_t bytes);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * MESH-LIT FILMS AND BAKES.  MESH LIGHTS' group in the two accumulating forms: rayrs_film_create_mesh makes a film, and
+ * rayrs_bake_create_mesh a bake, whose passes run MESH LIGHTS' paths -- the lamps of `lights`, the group, and the sky with
+ * sky = 1 (the bake: params->sky = 1).  lights is a HOST array, copied at creation; n_lights == 0 is legal (the group alone, or
+ * with the sky).  The film is a rayrs_film and the bake a rayrs_bake like any other: every rayrs_film_* call,
+ * rayrs_history_push_film and every rayrs_bake_* call take them unchanged.  The kernels are two units of their own
+ * (film_mesh.hip, bake_mesh.hip): MESH LIGHTS' wave, started as DIRECT-LIT FILMS and BAKE start theirs; nothing above changes.
+ *
+ * THE FILM.  DIRECT-LIT FILMS' contract holds word for word with rayrs_render_mesh in rayrs_render_direct's place: after passes
+ * adding up to N_t samples in tile t, rayrs_film_read(RAYRS_OUT_F64) returns, bit for bit, rayrs_render_mesh's pixels for
+ * samples = N_t, called with the same seed, max_bounces, sample_chunk = c, list, group, sky and the walk a render with the
+ * film's settings takes; RAYRS_OUT_F32 is that value converted; a film with tile_ranks > 1 holds its share's pixels and the rest
+ * read +0.  This holds for every partition into passes the rules allow, uniform or adaptive, and across a rayrs_film_state_get /
+ * new film / rayrs_film_state_set in between.  rayrs_film_status.rays is the sum over the share's in-image pixels of the
+ * `queries` plane rayrs_render_mesh returns at N_t, shadow rays included; paths and pass_stats are DIRECT-LIT FILMS'.  The pass
+ * rules are DIRECT-LIT FILMS', the limit of 16384 chunks per pass among them (a longer pass is RAYRS_UNSUPPORTED and leaves the
+ * film unchanged).  NOISE, ADAPTIVE PASSES, NOISE PLANE, FEATURES, DENOISER, GUIDED FILTER and TEMPORAL ACCUMULATION apply
+ * unchanged.
+ *
+ * THE BAKE.  BAKE's CONTRACT PER POINT holds with rayrs_scene_irradiance_mesh (kind 0) or rayrs_scene_radiance_mesh (kind 1) as
+ * the matching query, called with the group and sky = params->sky on the one point with index_base = index_base + i.  RULES,
+ * NOISE, SELECTION, rayrs_bake_pass and rayrs_bake_status are BAKE's, unchanged.
+ *
+ * THE EMPTY GROUP (mesh == NULL, or a handle of no triangles).  The film holds, byte for byte in rayrs_film_state_get, the
+ * records of rayrs_film_create_direct's film (sky = 0) or rayrs_film_create_sky's (sky = 1) with the same list, and the bake
+ * those of rayrs_bake_create's: their passes launch the direct and the sky kernels, as the queries' calls with an empty group do.
+ *
+ * Refusals at creation, all decided before the device is touched, in MESH LIGHTS' order: the film's are
+ * rayrs_film_create_direct's in their order (sky = 1: rayrs_film_create_sky's), the bake's are rayrs_bake_create's in theirs; a
+ * handle of another scene and, for the film, a sky above 1 join the RAYRS_INVALID_ARG group (the bake's sky is params->sky,
+ * which BAKE refuses above 1 already); RAYRS_NO_DEVICE comes last.  A bake with a group of N >= 1 triangles is never the unlit
+ * bake: its counter rule is c * (2 * max_bounces + 1) >= 2^32.
+ *
+ * Lifetime.  The film or the bake BORROWS the group: the handle must outlive every film and bake made with it, as the scene
+ * outlives them, and is destroyed before the scene.  Its device table is uploaded at the first pass if no call has uploaded it
+ * yet.  A pass runs under the queries' scratch ordering rule, so rayrs_mesh_lights_destroy's wait covers the last pass.
+ *
+ * Checkpoints.  Both images are byte for byte the formats they were: the group is NOT recorded, as the list is not.  Continuing an
+ * image on a film or a bake with another group (or with none) is the caller's error, which rayrs_film_state_set and
+ * rayrs_bake_state_set cannot tell: the result is the mean of samples of different estimators. */
+int rayrs_film_create_mesh(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params,
+                           const uint32_t* lights /* HOST */, uint32_t n_lights,
+                           const rayrs_mesh_lights* mesh /* may be NULL: empty */, uint32_t sky, rayrs_film** out);
+int rayrs_bake_create_mesh(rayrs_scene* scene, const double* a, const double* b, uint64_t n, const rayrs_bake_params* params,
+                           const uint32_t* lights /* HOST */, uint32_t n_lights,
+                           const rayrs_mesh_lights* mesh /* may be NULL: empty */, rayrs_bake** out);   /* sky: params->sky */
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -1437,7 +1484,7 @@ int rayrs_bake_state_set(rayrs_bake* bake, const void* in_host, uint64_t bytes);
  * rayrs_scene_sky_density (SKY SAMPLING), and with rayrs_film_create_direct and rayrs_film_create_sky (DIRECT-LIT FILMS), and with
  * rayrs_bake_* and its three structs (BAKE; they are not in the layout table below: all their fields are 4 or 8 bytes wide and
  * naturally aligned), and with rayrs_mesh_lights_*, rayrs_scene_radiance_mesh, rayrs_scene_irradiance_mesh, their _launch forms
- * and rayrs_render_mesh (MESH LIGHTS).  The
+ * and rayrs_render_mesh (MESH LIGHTS), and with rayrs_film_create_mesh and rayrs_bake_create_mesh (MESH-LIT FILMS AND BAKES).  The
  * layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised

@@ -45,6 +45,7 @@ SYMBOLS = [
     "rayrs_bake_create", "rayrs_bake_destroy", "rayrs_bake_render", "rayrs_bake_render_adaptive", "rayrs_bake_read",
     "rayrs_bake_point_samples", "rayrs_bake_noise", "rayrs_bake_status_get", "rayrs_bake_state_bytes", "rayrs_bake_state_get",
     "rayrs_bake_state_set",
+    "rayrs_film_create_mesh", "rayrs_bake_create_mesh",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -344,7 +345,10 @@ def lib():
                        ("rayrs_bake_status_get", [vp, C.c_double, C.POINTER(BakeStatus)]),
                        ("rayrs_bake_state_bytes", [vp]),
                        ("rayrs_bake_state_get", [vp, vp, C.c_uint64]),
-                       ("rayrs_bake_state_set", [vp, vp, C.c_uint64])):
+                       ("rayrs_bake_state_set", [vp, vp, C.c_uint64]),
+                       ("rayrs_film_create_mesh", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, vp, C.c_uint32,
+                                                   C.POINTER(vp)]),
+                       ("rayrs_bake_create_mesh", [vp, vp, vp, C.c_uint64, C.POINTER(BakeParams), vp, C.c_uint32, vp, C.POINTER(vp)])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):

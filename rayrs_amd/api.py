@@ -849,7 +849,10 @@ class MeshLights:
 
     def close(self):
         if self._h is not None:
-            self._L.rayrs_mesh_lights_destroy(self._h)
+            # (a scene that is already closed took the device with it, and the library's destructor would read the freed scene:
+            # garbage collection at interpreter exit finalizes a scene and its dependents in any order)
+            if self._scene._h is not None:
+                self._L.rayrs_mesh_lights_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -948,10 +951,17 @@ class Film:
     With lights=[...] and direct=True the film is direct-lit (DIRECT-LIT FILMS): its passes take a shadow sample per diffuse
     bounce towards the list's lamps, and towards the sky too if SKY is in the list, and image() is
     render_lit(scene, camera, N, lights, direct=True, sample_chunk=sample_chunk), bit for bit.  The list is fixed for the
-    film's life (film.lights); everything else a film does works on such a film unchanged."""
+    film's life (film.lights); everything else a film does works on such a film unchanged.
+
+    With mesh=group as well (MESH-LIT FILMS AND BAKES; a Scene.mesh_lights() group, lights may be empty) the group is one more
+    of those lights and image() is render_lit(..., direct=True, mesh=group), bit for bit.  The film keeps a reference to the
+    group (film.mesh), which must stay open while the film lives."""
 
     def __init__(self, scene: Scene, camera: Camera, sample_chunk: int = 4, max_bounces: int = 50, seed: int = 0x5EED,
-                 tile_rank: int = 0, tile_ranks: int = 1, fast_traversal: bool = False, lights=None, direct: bool = False):
+                 tile_rank: int = 0, tile_ranks: int = 1, fast_traversal: bool = False, lights=None, direct: bool = False,
+                 mesh: Optional["MeshLights"] = None):
+        if mesh is not None and not direct:
+            raise ValueError("mesh=... needs direct=True (a mesh-light group is a light of direct lighting)")
         if direct and lights is None:
             raise ValueError("direct=True needs a light list (lights=[...])")
         if lights is not None and not direct:
@@ -959,6 +969,7 @@ class Film:
         self._L, self._h = scene._L, None
         self.scene, self.camera = scene, camera
         self.lights = None if lights is None else [int(v) for v in _light_list(lights)]
+        self.mesh = mesh
         p = _ffi.FilmParams()
         p.sample_chunk, p.max_bounces, p.seed = int(sample_chunk), int(max_bounces), int(seed)
         p.tile_rank, p.tile_ranks, p.fast_traversal = int(tile_rank), int(tile_ranks), 1 if fast_traversal else 0
@@ -969,10 +980,12 @@ class Film:
             _ffi.check(self._L.rayrs_film_create(scene._h, C.byref(camera.desc), C.byref(p), C.byref(h)), "rayrs_film_create")
         else:  # (the rule render_lit chooses its entry point by: SKY in the list is the sky, the rest the lamps)
             lamps = _light_list(lights)
-            name = "rayrs_film_create_sky" if (lamps == SKY).any() else "rayrs_film_create_direct"
+            sky = bool((lamps == SKY).any())
+            name = "rayrs_film_create_mesh" if mesh is not None else "rayrs_film_create_sky" if sky else "rayrs_film_create_direct"
             lamps = lamps[lamps != SKY]
+            extra = () if mesh is None else (mesh._handle(), int(sky))  # (the group and the sky as arguments of their own)
             _ffi.check(getattr(self._L, name)(scene._h, C.byref(camera.desc), C.byref(p), lamps.ctypes.data if len(lamps) else None,
-                                              len(lamps), C.byref(h)), name)
+                                              len(lamps), *extra, C.byref(h)), name)
         self._h = h
 
     def render(self, n: int) -> dict:
@@ -1097,7 +1110,10 @@ class Film:
 
     def close(self):
         if self._h is not None:
-            self._L.rayrs_film_destroy(self._h)
+            # (a scene that is already closed took the device with it, and the library's destructor would read the freed scene:
+            # garbage collection at interpreter exit finalizes a scene and its dependents in any order)
+            if self.scene._h is not None:
+                self._L.rayrs_film_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1173,12 +1189,18 @@ class Bake:
     passes that leave point i at N_i samples, values()[i] is, bit for bit, scene.irradiance (scene.radiance) of that one point
     with samples=N_i, sample_chunk=sample_chunk, index_base=index_base + i and the same seed, bounces, bias, walk and lights.
     lights and direct as the queries take them: direct=True with a list is the direct-lit bake, SKY in the list the sky bake;
-    a list without direct=True (the one-sample mix) has no bake.  The scene must outlive the bake."""
+    a list without direct=True (the one-sample mix) has no bake.  mesh=group (with direct=True; lights may be empty): a
+    Scene.mesh_lights() group as one more of those lights (MESH-LIT FILMS AND BAKES), the matching query then being the one
+    with mesh=group; the bake keeps a reference to the group (bake.mesh), which must stay open while the bake lives.  The
+    scene must outlive the bake."""
 
     def __init__(self, scene: Scene, a, b, kind: str = "irradiance", sample_chunk: int = 4, max_bounces: int = 50, seed: int = 0,
-                 index_base: int = 0, bias: float = 0.0, fast_traversal: bool = False, lights=None, direct: bool = False):
+                 index_base: int = 0, bias: float = 0.0, fast_traversal: bool = False, lights=None, direct: bool = False,
+                 mesh: Optional["MeshLights"] = None):
         if kind not in ("irradiance", "radiance"):
             raise ValueError('kind is "irradiance" or "radiance"')
+        if mesh is not None and not direct:
+            raise ValueError("mesh=... needs direct=True (a mesh-light group is a light of direct lighting)")
         if direct and lights is None:
             raise ValueError("direct=True needs a light list (lights=[...])")
         if lights is not None and not direct:
@@ -1190,6 +1212,7 @@ class Bake:
         self.scene, self.kind, self.n = scene, kind, int(a.shape[0])
         self.sample_chunk = int(sample_chunk) or 4
         self.lights = None if lights is None else [int(v) for v in _light_list(lights)]
+        self.mesh = mesh
         p = _ffi.BakeParams()
         p.kind, p.sample_chunk, p.max_bounces = 0 if kind == "irradiance" else 1, int(sample_chunk), int(max_bounces)
         p.fast_traversal, p.seed, p.index_base, p.bias = 1 if fast_traversal else 0, int(seed), int(index_base), float(bias)
@@ -1199,8 +1222,10 @@ class Bake:
         if self.n == 0:
             a = b = np.zeros((1, 3))
         h = C.c_void_p()
-        _ffi.check(self._L.rayrs_bake_create(scene._h, a.ctypes.data, b.ctypes.data, self.n, C.byref(p),
-                                             lamps.ctypes.data if len(lamps) else None, len(lamps), C.byref(h)), "rayrs_bake_create")
+        name = "rayrs_bake_create" if mesh is None else "rayrs_bake_create_mesh"
+        extra = () if mesh is None else (mesh._handle(),)
+        _ffi.check(getattr(self._L, name)(scene._h, a.ctypes.data, b.ctypes.data, self.n, C.byref(p),
+                                          lamps.ctypes.data if len(lamps) else None, len(lamps), *extra, C.byref(h)), name)
         self._h = h
 
     def render(self, n: int) -> dict:
@@ -1270,7 +1295,10 @@ class Bake:
 
     def close(self):
         if self._h is not None:
-            self._L.rayrs_bake_destroy(self._h)
+            # (a scene that is already closed took the device with it, and the library's destructor would read the freed scene:
+            # garbage collection at interpreter exit finalizes a scene and its dependents in any order)
+            if self.scene._h is not None:
+                self._L.rayrs_bake_destroy(self._h)
             self._h = None
 
     def __del__(self):

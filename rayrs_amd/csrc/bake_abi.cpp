@@ -1,5 +1,6 @@
 // bake_abi.cpp -- the bake of include/rayrs_hip.h (BAKE: rayrs_bake_*): a bake's lifetime, a pass as launches of bake.hip's
-// wave kernels on the scene's radiance scratch with bake_accumulate_kernel behind each, the selection of an adaptive pass, the
+// wave kernels (with a mesh-light group of N >= 1 triangles, MESH-LIT FILMS AND BAKES: bake_mesh.hip's) on the scene's radiance
+// scratch with bake_accumulate_kernel behind each, the selection of an adaptive pass, the
 // values, the counts and the noise read from the records, and the checkpoint image.  The refusals, the light table and the
 // scratch's ordering rule are the light-list queries' (radiance_lit_host.hpp), piece by piece as the direct-lit films take them.
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 
 #include "../../include/rayrs_hip.h"
 #include "bake_kernels.h"
+#include "passes_mesh_kernels.h"
 #include "radiance_lit_host.hpp"
 #include "scene_internal.hpp"
 
@@ -45,6 +47,9 @@ struct rayrs_bake {
     uint64_t samples = 0, rays = 0, paths = 0;  // samples: the largest N_i
     bool closed = false;
     std::vector<uint32_t> lights;  // the list as given, fixed for the bake's life; not part of the checkpoint image
+    // MESH-LIT FILMS AND BAKES: the group of rayrs_bake_create_mesh, borrowed (it outlives the bake); null or empty: none
+    const rayrs_mesh_lights* mesh = nullptr;
+    bool grouped() const { return mesh && mesh->n != 0u; }
     DevBuf d_a, d_b;      // the points
     DevBuf d_rec;         // bake_kernels.h: five planes of n doubles
     DevBuf d_queries;     // n x 8 bytes
@@ -60,7 +65,7 @@ struct rayrs_bake {
     bool unlit() const { return prm.sky == 0u && lights.empty(); }
     LitCall call(uint32_t samples_) const {
         return LitCall{prm.kind == 0u ? LIT_START_POINT : LIT_START_RAY, samples_, prm.max_bounces, prm.sample_chunk, prm.bias, prm.seed,
-                       prm.index_base, prm.fast_traversal, lights.data(), (uint32_t)lights.size(), true, prm.sky != 0u};
+                       prm.index_base, prm.fast_traversal, lights.data(), (uint32_t)lights.size(), true, prm.sky != 0u, mesh};
     }
     size_t record_bytes() const { return (size_t)n * BAKE_PLANES * sizeof(double); }
     size_t query_bytes() const { return (size_t)n * sizeof(unsigned long long); }
@@ -86,7 +91,8 @@ static int bake_enter(rayrs_bake* b) { return scene_settle(b->scene); }
 
 // One pass of n samples: over the list bake_select has just made (n_list entries, each point from the N_i the list holds), or,
 // n_list == 0, over every point from its own N_i.  Whole points, as many as fit RADIANCE_LAUNCH_ITEMS items, per launch of the
-// direct or the sky wave on the scene's radiance scratch; behind each launch, on the same stream, bake_accumulate_kernel over its
+// direct, the sky or (a group of N >= 1 triangles) the mesh wave on the scene's radiance scratch; behind each launch, on the same
+// stream, bake_accumulate_kernel over its
 // entries.  The host waits once, for the pass's query total.
 static int bake_pass(rayrs_bake* bake, uint32_t n, uint32_t n_list, rayrs_bake_pass* st) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -99,6 +105,10 @@ static int bake_pass(rayrs_bake* bake, uint32_t n, uint32_t n_list, rayrs_bake_p
     SkyDev sky;
     std::memset(&sky, 0, sizeof(sky));
     if (use_sky) RAYRS_TRY(sky_device_table(scene, &sky));
+    MeshDev mesh;
+    std::memset(&mesh, 0, sizeof(mesh));
+    const bool grouped = bake->grouped();
+    if (grouped) RAYRS_TRY(mesh_device_table(bake->mesh, &mesh));  // (uploaded by the handle's first call, then kept)
     const SceneDev sc = make_scene_dev(scene, bake->prm.fast_traversal == 0u);
     const hipStream_t stream = nullptr;
     RadianceDev rd;
@@ -128,8 +138,10 @@ static int bake_pass(rayrs_bake* bake, uint32_t n, uint32_t n_list, rayrs_bake_p
             HIP_TRY(hipMemsetAsync(rd.partial, 0, (size_t)rd.n * rd.chunks * 3u * sizeof(double), stream));
         } else {
             HIP_TRY(hipMemsetAsync(rd.cursor, 0, sizeof(unsigned long long), stream));
-            HIP_TRY(launch_bake_wave(scene->flat.compact, sc, rd, bs, lights, slots, use_sky ? &sky : nullptr, bake->prm.kind == 0u,
-                                     scene->cu_count, stream));
+            if (grouped) HIP_TRY(launch_bake_mesh(scene->flat.compact, sc, rd, bs, lights, slots, mesh, sky, use_sky, bake->prm.kind == 0u,
+                                                  scene->cu_count, stream));
+            else HIP_TRY(launch_bake_wave(scene->flat.compact, sc, rd, bs, lights, slots, use_sky ? &sky : nullptr, bake->prm.kind == 0u,
+                                          scene->cu_count, stream));
             launches++;
         }
         HIP_TRY(launch_bake_accumulate(rd, bs, bk, n / c, has_queries, counts, stream));
@@ -157,7 +169,7 @@ static int bake_pass_unsupported(const rayrs_bake* bake, uint32_t n) {
 }
 
 static int bake_create(rayrs_scene* scene, const double* a, const double* b, uint64_t n, const rayrs_bake_params* params,
-                       const uint32_t* lights, uint32_t n_lights, rayrs_bake** out) {
+                       const uint32_t* lights, uint32_t n_lights, const rayrs_mesh_lights* mesh, rayrs_bake** out) {
     if (!scene || !a || !b || !params || !out) return RAYRS_INVALID_ARG;
     *out = nullptr;
     rayrs_bake_params prm = *params;
@@ -166,9 +178,10 @@ static int bake_create(rayrs_scene* scene, const double* a, const double* b, uin
     const LitCall list{prm.kind == 0u ? LIT_START_POINT : LIT_START_RAY, prm.sample_chunk, prm.max_bounces, prm.sample_chunk, prm.bias,
                        prm.seed, prm.index_base, prm.fast_traversal, lights, n_lights, true, prm.sky != 0u};
     RAYRS_TRY(lit_list_invalid(scene, list));
+    if (mesh && mesh->scene != scene) return RAYRS_INVALID_ARG;
     if (prm.sample_chunk > SLOT_SAMPLE_MASK || prm.max_bounces > 8000u) return RAYRS_UNSUPPORTED;
     // (an item is one chunk of at most max_bounces, with shadow rays 2 * max_bounces + 1, queries a sample, counted in 32 bits)
-    const bool unlit = prm.sky == 0u && n_lights == 0u;
+    const bool unlit = prm.sky == 0u && n_lights == 0u && !(mesh && mesh->n != 0u);  // (a group's paths have shadow rays)
     const uint64_t path_queries = unlit ? (uint64_t)prm.max_bounces : 2ull * prm.max_bounces + 1u;
     if ((uint64_t)prm.sample_chunk * path_queries >= (1ull << 32)) return RAYRS_UNSUPPORTED;
     RAYRS_TRY(lit_list_unsupported(scene, list));
@@ -179,6 +192,7 @@ static int bake_create(rayrs_scene* scene, const double* a, const double* b, uin
     k->prm = prm;
     k->n = n;
     k->lights.assign(lights, lights + n_lights);
+    k->mesh = mesh;
     HIP_TRY(hipSetDevice(scene->device));
     if (n) {
         HIP_TRY(k->d_a.upload(a, (size_t)n * 3u * sizeof(double)));
@@ -204,7 +218,12 @@ extern "C" {
 
 int rayrs_bake_create(rayrs_scene* scene, const double* a, const double* b, uint64_t n, const rayrs_bake_params* params,
                       const uint32_t* lights, uint32_t n_lights, rayrs_bake** out) {
-    RAYRS_GUARDED({ return bake_create(scene, a, b, n, params, lights, n_lights, out); })
+    RAYRS_GUARDED({ return bake_create(scene, a, b, n, params, lights, n_lights, nullptr, out); })
+}
+
+int rayrs_bake_create_mesh(rayrs_scene* scene, const double* a, const double* b, uint64_t n, const rayrs_bake_params* params,
+                           const uint32_t* lights, uint32_t n_lights, const rayrs_mesh_lights* mesh, rayrs_bake** out) {
+    RAYRS_GUARDED({ return bake_create(scene, a, b, n, params, lights, n_lights, mesh, out); })
 }
 
 void rayrs_bake_destroy(rayrs_bake* bake) {

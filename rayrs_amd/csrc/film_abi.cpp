@@ -1,7 +1,8 @@
 // film_abi.cpp -- the progressive film of include/rayrs_hip.h (rayrs_film_*): a film's lifetime, a pass as a render of a
 // sample window whose chunk sums go to the film's records (render.cpp render_enqueue, film.hip), the frame and the status
 // read from the records, and the checkpoint image.  A direct-lit film (DIRECT-LIT FILMS) differs in who makes a pass's chunk
-// sums: film_direct.hip's kernels on the scene's radiance scratch, launch by launch (film_pass_lit).
+// sums: film_direct.hip's kernels on the scene's radiance scratch, launch by launch (film_pass_lit); with a mesh-light group
+// of N >= 1 triangles (MESH-LIT FILMS AND BAKES) film_mesh.hip's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -16,6 +17,7 @@
 #include "film.h"
 #include "film_direct_kernels.h"
 #include "film_host.hpp"
+#include "passes_mesh_kernels.h"
 #include "radiance_lit_host.hpp"
 #include "scene_internal.hpp"
 
@@ -70,11 +72,14 @@ struct rayrs_film {
     // (rayrs_film_create_sky); the list as given, fixed for the film's life.  Not part of the checkpoint image.
     bool lit = false, sky = false;
     std::vector<uint32_t> lights;
+    // MESH-LIT FILMS AND BAKES: the group of rayrs_film_create_mesh, borrowed (it outlives the film); null or empty: none
+    const rayrs_mesh_lights* mesh = nullptr;
+    bool grouped() const { return mesh && mesh->n != 0u; }
     DevBuf d_lit_counts;  // one FilmDirectCounts, read once per pass
     Event lit_ev[2];      // around a pass's launches
     LitCall lit_call(uint32_t n) const {
         return LitCall{LIT_START_PIXEL, n, prm.max_bounces, prm.sample_chunk, 0.0, prm.seed, 0u, prm.fast_traversal, lights.data(),
-                       (uint32_t)lights.size(), true, sky};
+                       (uint32_t)lights.size(), true, sky, mesh};
     }
     // a lit pass of n samples is too long: a tile's items of one pass do not fit one launch
     bool lit_pass_too_long(uint32_t n) const { return lit && ((uint64_t)n + prm.sample_chunk - 1u) / prm.sample_chunk * 64u > RADIANCE_LAUNCH_ITEMS; }
@@ -146,8 +151,9 @@ static int film_pass(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_render
     return RAYRS_OK;
 }
 
-// The same pass of a direct-lit film.  Whole tiles, as many as fit RADIANCE_LAUNCH_ITEMS items, per launch of the direct or the
-// sky wave on the scene's radiance scratch (the queries' ordering rule, radiance_lit_abi.cpp lit_scratch_begin); behind each
+// The same pass of a direct-lit film.  Whole tiles, as many as fit RADIANCE_LAUNCH_ITEMS items, per launch of the direct, the
+// sky or (a group of N >= 1 triangles) the mesh wave on the scene's radiance scratch (the queries' ordering rule,
+// radiance_lit_abi.cpp lit_scratch_begin); behind each
 // launch, on the same stream, its counts and film_accumulate_kernel over its tile range, as behind a segment of a plain pass.
 // The host waits once, for the pass's two counters.
 static int film_pass_lit(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_render_stats* st) {
@@ -159,6 +165,10 @@ static int film_pass_lit(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_re
     SkyDev sky;
     std::memset(&sky, 0, sizeof(sky));
     if (film->sky) RAYRS_TRY(sky_device_table(scene, &sky));
+    MeshDev mesh;
+    std::memset(&mesh, 0, sizeof(mesh));
+    const bool grouped = film->grouped();
+    if (grouped) RAYRS_TRY(mesh_device_table(film->mesh, &mesh));  // (uploaded by the handle's first call, then kept)
     const FrameWalk walk = frame_walk(scene, &film->camera, film->prm.fast_traversal);  // the walk a render with these settings takes
     const SceneDev sc = make_scene_dev(scene, walk.exact || walk.use_local);
     const CameraDev cam = make_camera_dev(&film->camera);
@@ -205,7 +215,8 @@ static int film_pass_lit(rayrs_film* film, uint32_t n, uint32_t n_list, rayrs_re
             HIP_TRY(hipMemsetAsync(rd.partial, 0, (size_t)rd.n * rd.chunks * 3u * sizeof(double), stream));
         } else {
             HIP_TRY(hipMemsetAsync(rd.cursor, 0, sizeof(unsigned long long), stream));
-            HIP_TRY(launch_film_direct(scene->flat.compact, sc, rd, fs, lights, slots, film->sky ? &sky : nullptr, cam, scene->cu_count, stream));
+            if (grouped) HIP_TRY(launch_film_mesh(scene->flat.compact, sc, rd, fs, lights, slots, mesh, sky, film->sky, cam, scene->cu_count, stream));
+            else HIP_TRY(launch_film_direct(scene->flat.compact, sc, rd, fs, lights, slots, film->sky ? &sky : nullptr, cam, scene->cu_count, stream));
         }
         HIP_TRY(launch_film_direct_count(rd, fs, cam, rd.max_bounces != 0u ? 1u : 0u, counts, stream));
         HIP_TRY(launch_film_accumulate(cam, rp, fp, lt0, n_lt, stream));
@@ -242,6 +253,7 @@ static int film_create(rayrs_scene* scene, const rayrs_camera* camera, const ray
     if (camera->x_pixels == 0 || camera->y_pixels == 0) return RAYRS_INVALID_ARG;
     if (prm.tile_ranks == 0 || prm.tile_rank >= prm.tile_ranks || prm.fast_traversal > 1u || prm.pad != 0u) return RAYRS_INVALID_ARG;
     if (lit) RAYRS_TRY(lit_list_invalid(scene, *lit));
+    if (lit && lit->mesh && lit->mesh->scene != scene) return RAYRS_INVALID_ARG;
     if (camera->x_pixels > 65535u || camera->y_pixels > 65535u) return RAYRS_UNSUPPORTED;
     if (prm.max_bounces > 8000u) return RAYRS_UNSUPPORTED;
     if (prm.sample_chunk > SLOT_SAMPLE_MASK) return RAYRS_UNSUPPORTED;  // not one full chunk fits the 30-bit sample cursor
@@ -265,7 +277,7 @@ static int film_create(rayrs_scene* scene, const rayrs_camera* camera, const ray
     HIP_TRY(f->h_word.alloc(sizeof(uint32_t)));
     HIP_TRY(f->d_counts.reserve(sizeof(FilmCounts)));
     if (lit) {
-        f->lit = true, f->sky = lit->sky;
+        f->lit = true, f->sky = lit->sky, f->mesh = lit->mesh;
         f->lights.assign(lit->lights, lit->lights + lit->n_lights);
         HIP_TRY(f->d_lit_counts.reserve(sizeof(FilmDirectCounts)));
         HIP_TRY(f->lit_ev[0].create());
@@ -276,8 +288,8 @@ static int film_create(rayrs_scene* scene, const rayrs_camera* camera, const ray
 }
 
 // the list of a direct-lit film's creation as the light-list entry points describe a call (the film's own settings join it later)
-static LitCall film_list(const uint32_t* lights, uint32_t n_lights, bool sky) {
-    return LitCall{LIT_START_PIXEL, 0u, 0u, 0u, 0.0, 0u, 0u, 0u, lights, n_lights, true, sky};
+static LitCall film_list(const uint32_t* lights, uint32_t n_lights, bool sky, const rayrs_mesh_lights* mesh = nullptr) {
+    return LitCall{LIT_START_PIXEL, 0u, 0u, 0u, 0.0, 0u, 0u, 0u, lights, n_lights, true, sky, mesh};
 }
 
 extern "C" {
@@ -298,6 +310,16 @@ int rayrs_film_create_sky(rayrs_scene* scene, const rayrs_camera* camera, const 
                           uint32_t n_lights, rayrs_film** out) {
     RAYRS_GUARDED({
     const LitCall lit = film_list(lights, n_lights, true);
+    return film_create(scene, camera, params, &lit, out);
+    })
+}
+
+int rayrs_film_create_mesh(rayrs_scene* scene, const rayrs_camera* camera, const rayrs_film_params* params, const uint32_t* lights,
+                           uint32_t n_lights, const rayrs_mesh_lights* mesh, uint32_t sky, rayrs_film** out) {
+    RAYRS_GUARDED({
+    if (out) *out = nullptr;
+    if (sky > 1u) return RAYRS_INVALID_ARG;  // (of that group whatever else is asked, as MESH LIGHTS' entry points have it)
+    const LitCall lit = film_list(lights, n_lights, sky == 1u, mesh);
     return film_create(scene, camera, params, &lit, out);
     })
 }
