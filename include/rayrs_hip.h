@@ -1467,6 +1467,106 @@ int rayrs_bake_create_mesh(rayrs_scene* scene, const double* a, const double* b,
                            const uint32_t* lights /* HOST */, uint32_t n_lights,
                            const rayrs_mesh_lights* mesh /* may be NULL: empty */, rayrs_bake** out);   /* sky: params->sky */
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * LIGHT TREE.  MESH LIGHTS draws the group's points uniformly by area, from one table, for every shading point of the scene: a
+ * point below one of sixty-four lamps aims 63 of 64 shadow rays at the others, and a large dim panel takes the draws a small
+ * bright one beside it should have.  rayrs_mesh_lights_create_tree makes a group whose triangle is chosen, per shading point, by
+ * the descent of a binary tree over the listed triangles, each branch in proportion to power over squared distance (Conty and
+ * Kulla 2018, without the orientation cone: emitters here are two-sided).  MESH LIGHTS' weights are in area measure and never sum
+ * over the list, so the one factor that changes is 1 / T, which becomes p_sel(j | x) / A_j.  The kernels are a unit of their own
+ * (radiance_tree.hip); nothing above changes.
+ *
+ * LIGHT TREE, specified to the operation.  Everything is f64 and unfused; the elementary functions are rayrs_numeric.h's.
+ *
+ * The handle is a rayrs_mesh_lights: rayrs_mesh_lights_destroy, rayrs_mesh_lights_table, the binding to one scene and the lazy
+ * device copy are MESH LIGHTS'.  Refusals at creation are rayrs_mesh_lights_create's, in its order, and RAYRS_UNSUPPORTED gains: a
+ * listed triangle with a negative or non-finite emission channel; a non-finite vertex; with n_tris >= 1, a total power (the
+ * root's W) that is not > 0.0 or not finite.  n_tris == 0 is a legal, empty group.
+ *
+ * Entries, in list order: p1, p2, p3, n_j, A_j and the slot are MESH LIGHTS'.  With e the emission of the triangle's surface,
+ *     w_j = A_j * ((e_r + e_g) + e_b)                              the power of entry j
+ * Dark and zero-area triangles are legal; an entry with w_j == 0 is never drawn (below).
+ *
+ * The build is deterministic and top-down over a permutation of the entries.  c = (p1 + p2) + p3 (per component, no division)
+ * is an entry's centroid key.  A node over n > 1 entries takes lo and hi of its entries' keys per axis, picks the axis of the
+ * largest hi - lo (a tie: the lowest axis), orders its entries by (c[axis], list index), gives the first ceil(n / 2) to its
+ * left child and the rest to its right.  A node over one entry is a leaf.  Nodes are numbered in preorder: the root is 0, the
+ * left child of node i is i + 1, the right child's index is kept; there are 2N - 1.  Each node keeps, with lo and hi now the box
+ * over its entries' VERTICES (the first vertex assigned, then v < lo and v > hi compared),
+ *     m = (lo + hi) * 0.5;  r2 = (hi - m).mag2();  W = W_left + W_right (a leaf: w_j)
+ * and each entry its leaf's depth and its path word: bit k is set where the way from the root goes right at depth k.  The depth
+ * is at most ceil(log2 N), below 32.
+ *
+ * One step at a node with children l and r, seen from x, with the draw u and the probability p so far:
+ *     I_c = W_c > 0.0 ? W_c / rr_max(|x - m_c|^2, r2_c) : 0.0      (c = l, r; |.|^2 is mag2; rr_max ignores a NaN)
+ *     s = I_l + I_r
+ *     P_l = I_l / s if s > 0.0 && s < +inf, else W_l / (W_l + W_r)
+ *     P_r = 1.0 - P_l
+ *     left iff u < P_l:  u = u / P_l;  p = p * P_l                 else right:  u = (u - P_l) / P_r;  p = p * P_r
+ *
+ * tree_sample(x, u1, u2): descend from the root with u = u1, p = 1.0.  At the leaf of entry j:
+ *     r = rr_min(u, 1.0)
+ *     su = rr_sqrt(r);  b0, b1, b2 and q as mesh_sample has them from (r, u2)
+ *     (j, q, p_sel = p)
+ * tree_probability(x, j): the same descent, steered by j's path word instead of by u -- the same expressions in the same order,
+ * so it returns, bit for bit, the p tree_sample returned when it arrived at j.
+ *
+ * The descent ends at a leaf within the table for ANY f64 x, u1 and u2, NaN and infinities included: a step never computes
+ * where it goes, it follows one of the two child references the build wrote, so after at most depth steps it stands at a leaf,
+ * whatever P_l is.  u < P_l is false when either side is NaN: a NaN comparison goes RIGHT.  A NaN or infinite |x - m|^2 gives
+ * r2's importance or 0.0, an s that is not positive and finite gives the powers' ratio, and where that is 0 / 0 the step goes
+ * right with a NaN p: the sample then fails den < +inf and casts no ray.  An entry with w_j == 0 is arrived at only with
+ * p_sel == 0.0 or NaN (its side's P is 0.0 for every x), and such a sample earns nothing: a dark triangle's emission is 0 and a
+ * zero-area one's p_tri is NaN.
+ *
+ * The turn is MESH LIGHTS', word for word, with two substitutions.  The group's arm:
+ *     (j, q, p_sel) = tree_sample(position, u1, u2);  l_s = (q - position).unit()
+ *     p_tri = ((position - q).mag2() / (|n_j . l_s| * A_j)) * p_sel
+ * and a listed triangle met by a ray that left a diffuse bounce, with j the entry of the hit slot and o the ray's origin:
+ *     p = ((o - ray.point(t)).mag2() / (|normal . d| * A_j)) * tree_probability(o, j)
+ *     wt = pc / (pc + p / (double)M) if p > 0.0 else 1.0
+ * The draws b, u1, u2 and their order, M, the lamps, the sky, p_R, "only the very triangle it drew earns", the query counts,
+ * IRRADIANCE's virtual bounce and the image form are unchanged.  An empty tree group gives DIRECT LIGHTING's or SKY SAMPLING's
+ * bits, as an empty group does.
+ *
+ * Why it is unbiased.  MESH LIGHTS' argument stands with one density replaced.  The group's arm arrives at a first-visible point
+ * y of entry j with area density p_sel(j | x) / A_j -- the descent's probabilities of one node sum to 1 (P_r = 1.0 - P_l), so
+ * the leaves' sum to 1 for the fixed x, and every entry that emits has p_sel > 0: a child with W > 0 has I > 0, or the powers'
+ * ratio > 0 -- times distance^2 / cosine: p_tri, over M.  The continuation that meets y from o evaluates the same density, at the
+ * same x = o, with tree_probability(o, j) = that p_sel bit for bit.  The two weights p / (p + pc) and pc / (p + pc) are taken at
+ * the same point and sum to 1 up to the rounding between q and the hit point.  The position enters the DENSITY only, never the
+ * set of points that can be drawn, so nothing that emits is left out.
+ *
+ * On the device the tree is one 128-byte line per interior node, holding both children's m, r2, W and where they are, so a step
+ * reads one line; the record read at the leaf is MESH LIGHTS' 128-byte one with the path word, the depth and w_j in its padding;
+ * and one u32 per primitive slot (the entry, or 0xFFFFFFFF) replaces the bitmap, so one load at a hit tells "listed?" and "which
+ * entry".  rayrs_scene_radiance_mesh, rayrs_scene_irradiance_mesh, their _launch forms and rayrs_render_mesh take a tree handle
+ * as `mesh` and tell it by its kind; their refusals are unchanged, and a _launch form still allocates and copies nothing after
+ * the handle's first device call.  All twenty-four path kernels of the unit (both record formats, both walks, without and with
+ * the sky, the three starts) use at most 256 VGPRs (209 to 228 as compiled), no scratch and no static LDS.
+ *
+ * rayrs_film_create_mesh and rayrs_bake_create_mesh REFUSE a tree handle, empty or not, as RAYRS_UNSUPPORTED, first of that
+ * group and before the device is touched: their passes have no kernel that descends a tree, and they must not sample uniformly
+ * in its place.
+ *
+ * Host calls, which need no device.  rayrs_mesh_lights_tree_nodes: the 2N - 1 nodes in preorder -- m, r2, W (five f64 each), the
+ * right child's index (0xFFFFFFFF at a leaf) and the leaf's entry (0xFFFFFFFF at an interior node); any of the three may be
+ * NULL, not all.  rayrs_mesh_lights_tree_entries: w_j, the path word and the depth of every entry, likewise.
+ * rayrs_mesh_lights_tree_sample: tree_sample of n (position, u1, u2) -> j, q, p_sel.  rayrs_mesh_lights_tree_probability:
+ * tree_probability of n (position, j).  rayrs_mesh_lights_density on a tree handle returns this section's p_tri of n
+ * (position, j, q).  All four refuse a handle that is no tree as RAYRS_UNSUPPORTED, the last three an empty group as well, and a
+ * j that is not below N is RAYRS_INVALID_ARG.  rayrs_mesh_lights_sample needs no position: on a tree handle it is
+ * RAYRS_UNSUPPORTED. */
+int rayrs_mesh_lights_create_tree(rayrs_scene* scene, const uint32_t* tris, uint64_t n_tris, rayrs_mesh_lights** out);
+int rayrs_mesh_lights_tree_nodes(const rayrs_mesh_lights* mesh, double* mrw /* (2N-1)*5, may be NULL */,
+                                 uint32_t* right /* 2N-1, may be NULL */, uint32_t* entry /* 2N-1, may be NULL */);
+int rayrs_mesh_lights_tree_entries(const rayrs_mesh_lights* mesh, double* power /* N, may be NULL */, uint32_t* path /* N, may be NULL */,
+                                   uint32_t* depth /* N, may be NULL */);
+int rayrs_mesh_lights_tree_sample(const rayrs_mesh_lights* mesh, const double* position /* n*3 */, const double* u /* n*2 */,
+                                  uint64_t n, uint32_t* j /* n */, double* q /* n*3 */, double* p_sel /* n */);
+int rayrs_mesh_lights_tree_probability(const rayrs_mesh_lights* mesh, const double* position /* n*3 */, const uint32_t* j /* n */,
+                                       uint64_t n, double* p /* n */);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -1484,8 +1584,8 @@ int rayrs_bake_create_mesh(rayrs_scene* scene, const double* a, const double* b,
  * rayrs_scene_sky_density (SKY SAMPLING), and with rayrs_film_create_direct and rayrs_film_create_sky (DIRECT-LIT FILMS), and with
  * rayrs_bake_* and its three structs (BAKE; they are not in the layout table below: all their fields are 4 or 8 bytes wide and
  * naturally aligned), and with rayrs_mesh_lights_*, rayrs_scene_radiance_mesh, rayrs_scene_irradiance_mesh, their _launch forms
- * and rayrs_render_mesh (MESH LIGHTS), and with rayrs_film_create_mesh and rayrs_bake_create_mesh (MESH-LIT FILMS AND BAKES).  The
- * layout table below begins with this
+ * and rayrs_render_mesh (MESH LIGHTS), and with rayrs_film_create_mesh and rayrs_bake_create_mesh (MESH-LIT FILMS AND BAKES), and with
+ * rayrs_mesh_lights_create_tree and rayrs_mesh_lights_tree_* (LIGHT TREE).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

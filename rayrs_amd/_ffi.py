@@ -46,6 +46,8 @@ SYMBOLS = [
     "rayrs_bake_point_samples", "rayrs_bake_noise", "rayrs_bake_status_get", "rayrs_bake_state_bytes", "rayrs_bake_state_get",
     "rayrs_bake_state_set",
     "rayrs_film_create_mesh", "rayrs_bake_create_mesh",
+    "rayrs_mesh_lights_create_tree", "rayrs_mesh_lights_tree_nodes", "rayrs_mesh_lights_tree_entries", "rayrs_mesh_lights_tree_sample",
+    "rayrs_mesh_lights_tree_probability",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -348,7 +350,12 @@ def lib():
                        ("rayrs_bake_state_set", [vp, vp, C.c_uint64]),
                        ("rayrs_film_create_mesh", [vp, C.POINTER(CameraDesc), C.POINTER(FilmParams), vp, C.c_uint32, vp, C.c_uint32,
                                                    C.POINTER(vp)]),
-                       ("rayrs_bake_create_mesh", [vp, vp, vp, C.c_uint64, C.POINTER(BakeParams), vp, C.c_uint32, vp, C.POINTER(vp)])):
+                       ("rayrs_bake_create_mesh", [vp, vp, vp, C.c_uint64, C.POINTER(BakeParams), vp, C.c_uint32, vp, C.POINTER(vp)]),
+                       ("rayrs_mesh_lights_create_tree", [vp, vp, C.c_uint64, C.POINTER(vp)]),
+                       ("rayrs_mesh_lights_tree_nodes", [vp, vp, vp, vp]),
+                       ("rayrs_mesh_lights_tree_entries", [vp, vp, vp, vp]),
+                       ("rayrs_mesh_lights_tree_sample", [vp, vp, vp, C.c_uint64, vp, vp, vp]),
+                       ("rayrs_mesh_lights_tree_probability", [vp, vp, vp, C.c_uint64, vp])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):

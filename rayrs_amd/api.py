@@ -561,10 +561,12 @@ class Scene:
 
     # ---- a mesh-light group (include/rayrs_hip.h MESH LIGHTS)
 
-    def mesh_lights(self, tris) -> "MeshLights":
+    def mesh_lights(self, tris, tree: bool = False) -> "MeshLights":
         """A mesh-light group of this scene: `tris` are the object indices of its triangles (mesh_emitters()), each at most
-        once.  What radiance(), irradiance() and render_lit() take as mesh=...; close it before the scene."""
-        return MeshLights(self, tris)
+        once.  What radiance(), irradiance() and render_lit() take as mesh=...; close it before the scene.  tree=True: the
+        group's triangle is chosen per shading point by a light tree, by power over squared distance (include/rayrs_hip.h LIGHT
+        TREE), instead of uniformly by area; films and bakes do not take such a group."""
+        return MeshLights(self, tris, tree)
 
     # ---- the sky as a light (include/rayrs_hip.h SKY SAMPLING): host only, a scene without a device has them too
 
@@ -791,12 +793,13 @@ class MeshLights:
     """A mesh-light group (include/rayrs_hip.h MESH LIGHTS): listed triangles of one scene that together are one more light of
     direct lighting.  The table lives on the host; its device copy is made by the first call that launches."""
 
-    def __init__(self, scene: Scene, tris):
+    def __init__(self, scene: Scene, tris, tree: bool = False):
         tris = _light_list(tris)
         self._L, self._h, self._scene = scene._L, None, scene   # (the scene outlives the handle)
+        self.tree = bool(tree)   # LIGHT TREE: the triangle is chosen by the tree's descent from the shading point
         h = C.c_void_p()
-        _ffi.check(self._L.rayrs_mesh_lights_create(scene._h, tris.ctypes.data if len(tris) else None, len(tris), C.byref(h)),
-                   "rayrs_mesh_lights_create")
+        name = "rayrs_mesh_lights_create_tree" if self.tree else "rayrs_mesh_lights_create"
+        _ffi.check(getattr(self._L, name)(scene._h, tris.ctypes.data if len(tris) else None, len(tris), C.byref(h)), name)
         self._h, self._n = h, len(tris)
 
     def _handle(self):
@@ -820,19 +823,74 @@ class MeshLights:
         _ffi.check(self._L.rayrs_mesh_lights_table(self._handle(), None, C.addressof(total)), "rayrs_mesh_lights_table")
         return total.value
 
-    def sample(self, u):
-        """mesh_sample(u1, u2) of every row of u (n, 2): (j (n,) uint32, q (n, 3) f64), points uniform by area over the group."""
+    def _need_tree(self):
+        if not self.tree:
+            raise ValueError("the mesh-light group has no light tree (Scene.mesh_lights(tris, tree=True))")
+
+    def powers(self):
+        """LIGHT TREE: w_j of every entry, in list order: (N,) f64."""
+        self._need_tree()
+        out = np.zeros(max(self._n, 1))
+        _ffi.check(self._L.rayrs_mesh_lights_tree_entries(self._handle(), out.ctypes.data, None, None), "rayrs_mesh_lights_tree_entries")
+        return out[:self._n]
+
+    def paths(self):
+        """LIGHT TREE: (path word (N,) uint32, depth (N,) uint32) of every entry's leaf; bit k of the word: right at depth k."""
+        self._need_tree()
+        path, depth = np.zeros(max(self._n, 1), dtype=np.uint32), np.zeros(max(self._n, 1), dtype=np.uint32)
+        _ffi.check(self._L.rayrs_mesh_lights_tree_entries(self._handle(), None, path.ctypes.data, depth.ctypes.data),
+                   "rayrs_mesh_lights_tree_entries")
+        return path[:self._n], depth[:self._n]
+
+    def nodes(self):
+        """LIGHT TREE: the 2N - 1 nodes in preorder: (m, r2, W (2N-1, 5) f64, right (2N-1,) uint32, entry (2N-1,) uint32), with
+        0xFFFFFFFF for a leaf's right child and an interior node's entry."""
+        self._need_tree()
+        k = max(2 * self._n - 1, 0)
+        mrw, right, entry = np.zeros((max(k, 1), 5)), np.zeros(max(k, 1), dtype=np.uint32), np.zeros(max(k, 1), dtype=np.uint32)
+        _ffi.check(self._L.rayrs_mesh_lights_tree_nodes(self._handle(), mrw.ctypes.data, right.ctypes.data, entry.ctypes.data),
+                   "rayrs_mesh_lights_tree_nodes")
+        return mrw[:k], right[:k], entry[:k]
+
+    def probability(self, positions, j):
+        """LIGHT TREE: tree_probability(position, j) of every row: (n,) f64."""
+        self._need_tree()
+        p = np.ascontiguousarray(positions, dtype=np.float64)
+        j = _light_list(j)
+        if p.ndim != 2 or p.shape[1] != 3 or len(j) != len(p):
+            raise ValueError("positions must be (n, 3), j (n,)")
+        out = np.zeros(max(len(p), 1))
+        _ffi.check(self._L.rayrs_mesh_lights_tree_probability(self._handle(), (p if len(p) else np.zeros((1, 3))).ctypes.data,
+                                                              (j if len(p) else np.zeros(1, dtype=np.uint32)).ctypes.data, len(p),
+                                                              out.ctypes.data), "rayrs_mesh_lights_tree_probability")
+        return out[:len(p)]
+
+    def sample(self, u, positions=None):
+        """mesh_sample(u1, u2) of every row of u (n, 2): (j (n,) uint32, q (n, 3) f64), points uniform by area over the group.
+        LIGHT TREE: tree_sample(position, u1, u2) of every row, with positions (n, 3): (j, q, p_sel (n,) f64)."""
         u = np.ascontiguousarray(u, dtype=np.float64)
         if u.ndim != 2 or u.shape[1] != 2:
             raise ValueError("u must be (n, 2)")
         m = max(len(u), 1)
         j, q = np.zeros(m, dtype=np.uint32), np.zeros((m, 3))
+        if self.tree and positions is not None:
+            p = np.ascontiguousarray(positions, dtype=np.float64)
+            if p.shape != (len(u), 3):
+                raise ValueError("positions must be (n, 3)")
+            p_sel = np.zeros(m)
+            _ffi.check(self._L.rayrs_mesh_lights_tree_sample(self._handle(), (p if len(u) else q).ctypes.data,
+                                                             (u if len(u) else q).ctypes.data, len(u), j.ctypes.data, q.ctypes.data,
+                                                             p_sel.ctypes.data), "rayrs_mesh_lights_tree_sample")
+            return j[:len(u)], q[:len(u)], p_sel[:len(u)]
+        if positions is not None:
+            raise ValueError("positions=... is a light tree's (Scene.mesh_lights(tris, tree=True))")
         _ffi.check(self._L.rayrs_mesh_lights_sample(self._handle(), u.ctypes.data if len(u) else q.ctypes.data, len(u), j.ctypes.data,
                                                     q.ctypes.data), "rayrs_mesh_lights_sample")
         return j[:len(u)], q[:len(u)]
 
     def density(self, positions, j, q):
-        """p_tri of every (position, j, q): the solid-angle density at the position of sample()'s points at q, (n,) f64."""
+        """p_tri of every (position, j, q): the solid-angle density at the position of sample()'s points at q, (n,) f64 (a tree
+        group: LIGHT TREE's p_tri, with the tree's probability of j at the position)."""
         p = np.ascontiguousarray(positions, dtype=np.float64)
         q = np.ascontiguousarray(q, dtype=np.float64)
         j = _light_list(j)

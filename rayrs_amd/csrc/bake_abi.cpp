@@ -179,6 +179,7 @@ static int bake_create(rayrs_scene* scene, const double* a, const double* b, uin
                        prm.seed, prm.index_base, prm.fast_traversal, lights, n_lights, true, prm.sky != 0u};
     RAYRS_TRY(lit_list_invalid(scene, list));
     if (mesh && mesh->scene != scene) return RAYRS_INVALID_ARG;
+    if (mesh && mesh->tree) return RAYRS_UNSUPPORTED;  // LIGHT TREE: the passes have no kernel that descends a tree
     if (prm.sample_chunk > SLOT_SAMPLE_MASK || prm.max_bounces > 8000u) return RAYRS_UNSUPPORTED;
     // (an item is one chunk of at most max_bounces, with shadow rays 2 * max_bounces + 1, queries a sample, counted in 32 bits)
     const bool unlit = prm.sky == 0u && n_lights == 0u && !(mesh && mesh->n != 0u);  // (a group's paths have shadow rays)

@@ -254,6 +254,7 @@ static int film_create(rayrs_scene* scene, const rayrs_camera* camera, const ray
     if (prm.tile_ranks == 0 || prm.tile_rank >= prm.tile_ranks || prm.fast_traversal > 1u || prm.pad != 0u) return RAYRS_INVALID_ARG;
     if (lit) RAYRS_TRY(lit_list_invalid(scene, *lit));
     if (lit && lit->mesh && lit->mesh->scene != scene) return RAYRS_INVALID_ARG;
+    if (lit && lit->mesh && lit->mesh->tree) return RAYRS_UNSUPPORTED;  // LIGHT TREE: the passes have no kernel that descends a tree
     if (camera->x_pixels > 65535u || camera->y_pixels > 65535u) return RAYRS_UNSUPPORTED;
     if (prm.max_bounces > 8000u) return RAYRS_UNSUPPORTED;
     if (prm.sample_chunk > SLOT_SAMPLE_MASK) return RAYRS_UNSUPPORTED;  // not one full chunk fits the 30-bit sample cursor

@@ -13,6 +13,7 @@
 #include "radiance_lit_host.hpp"
 #include "radiance_lit_kernels.h"
 #include "radiance_mesh_kernels.h"
+#include "radiance_tree_kernels.h"
 #include "radiance_sky_kernels.h"
 #include "scene_internal.hpp"
 
@@ -179,7 +180,11 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
     MeshDev mesh;
     std::memset(&mesh, 0, sizeof(mesh));
     const bool grouped = c.mesh && c.mesh->n != 0u;  // (an empty group: DIRECT LIGHTING's call, or SKY SAMPLING's)
-    if (grouped) RAYRS_TRY(mesh_device_table(c.mesh, &mesh));  // (uploaded by the handle's first call, then kept)
+    const bool treed = grouped && c.mesh->tree;  // LIGHT TREE: the group's triangles are chosen by its tree
+    TreeDev tree;
+    std::memset(&tree, 0, sizeof(tree));
+    if (treed) RAYRS_TRY(tree_device_table(c.mesh, &tree));
+    else if (grouped) RAYRS_TRY(mesh_device_table(c.mesh, &mesh));  // (uploaded by the handle's first call, then kept)
     if (c.max_bounces == 0u) {  // the loop runs no turn: +0 and no query, whatever the scene
         if (radiance) HIP_TRY(hipMemsetAsync(radiance, 0, n * 3u * sizeof(double), stream));
         if (queries) HIP_TRY(hipMemsetAsync(queries, 0, n * sizeof(uint32_t), stream));
@@ -202,7 +207,8 @@ int lit_enqueue(rayrs_scene* scene, const LitCall& c, const SceneDev& sc, const 
         rd.radiance = radiance ? radiance + base * 3u : nullptr;
         rd.queries = queries ? queries + base : nullptr;
         HIP_TRY(hipMemsetAsync(rd.cursor, 0, sizeof(unsigned long long), stream));
-        if (grouped) HIP_TRY(launch_radiance_mesh(scene->flat.compact, sc, rd, lights, slots, mesh, sky, c.sky, cam, c.start, scene->cu_count, stream));
+        if (treed) HIP_TRY(launch_radiance_tree(scene->flat.compact, sc, rd, lights, slots, tree, sky, c.sky, cam, c.start, scene->cu_count, stream));
+        else if (grouped) HIP_TRY(launch_radiance_mesh(scene->flat.compact, sc, rd, lights, slots, mesh, sky, c.sky, cam, c.start, scene->cu_count, stream));
         else if (c.sky) HIP_TRY(launch_radiance_sky(scene->flat.compact, sc, rd, lights, slots, sky, cam, c.start, scene->cu_count, stream));
         else if (c.direct) HIP_TRY(launch_radiance_direct(scene->flat.compact, sc, rd, lights, slots, cam, c.start, scene->cu_count, stream));
         else HIP_TRY(launch_radiance_lit(scene->flat.compact, sc, rd, lights, cam, c.start, scene->cu_count, stream));

@@ -65,15 +65,8 @@ int mesh_device_table(const rayrs_mesh_lights* mesh, MeshDev* out) {
     return RAYRS_OK;
 }
 
-}  // namespace rayrs
-
-using namespace rayrs;
-
-extern "C" {
-
-int rayrs_mesh_lights_create(rayrs_scene* scene, const uint32_t* tris, uint64_t n_tris, rayrs_mesh_lights** out) {
-    RAYRS_GUARDED({
-    if (!scene || !out) return RAYRS_INVALID_ARG;
+// rayrs_mesh_lights_create past its null checks: the list's refusals in the header's order, then the handle with its table.
+int mesh_lights_make(rayrs_scene* scene, const uint32_t* tris, uint64_t n_tris, std::unique_ptr<rayrs_mesh_lights>& m) {
     if (!tris && n_tris > 0u) return RAYRS_INVALID_ARG;
     const size_t n_objects = scene->flat.prim_object.size();
     std::vector<uint32_t> seen((n_objects + 31u) / 32u, 0u);  // over OBJECT indices: the duplicate check
@@ -96,7 +89,7 @@ int rayrs_mesh_lights_create(rayrs_scene* scene, const uint32_t* tris, uint64_t 
         const bool always_scatters = s.kind == RAYRS_MAT_LAMBERTIAN || s.kind == RAYRS_MAT_REFLECT || s.kind == RAYRS_MAT_GLASS;
         if (!dark && !always_scatters) return RAYRS_UNSUPPORTED;
     }
-    std::unique_ptr<rayrs_mesh_lights> m(new rayrs_mesh_lights());
+    m.reset(new rayrs_mesh_lights());
     m->scene = scene;
     m->n = (uint32_t)n_tris;
     if (m->n != 0u) {
@@ -115,6 +108,20 @@ int rayrs_mesh_lights_create(rayrs_scene* scene, const uint32_t* tris, uint64_t 
         m->total = P[m->n - 1u];
         if (!(m->total > 0.0) || !std::isfinite(m->total)) return RAYRS_UNSUPPORTED;
     }
+    return RAYRS_OK;
+}
+
+}  // namespace rayrs
+
+using namespace rayrs;
+
+extern "C" {
+
+int rayrs_mesh_lights_create(rayrs_scene* scene, const uint32_t* tris, uint64_t n_tris, rayrs_mesh_lights** out) {
+    RAYRS_GUARDED({
+    if (!scene || !out) return RAYRS_INVALID_ARG;
+    std::unique_ptr<rayrs_mesh_lights> m;
+    RAYRS_TRY(mesh_lights_make(scene, tris, n_tris, m));
     *out = m.release();
     return RAYRS_OK;
     })
@@ -136,7 +143,7 @@ int rayrs_mesh_lights_table(const rayrs_mesh_lights* mesh, double* areas, double
 int rayrs_mesh_lights_sample(const rayrs_mesh_lights* mesh, const double* u, uint64_t n, uint32_t* j, double* q) {
     RAYRS_GUARDED({
     if (!mesh || !u || !j || !q) return RAYRS_INVALID_ARG;
-    if (mesh->n == 0u) return RAYRS_UNSUPPORTED;
+    if (mesh->n == 0u || mesh->tree) return RAYRS_UNSUPPORTED;  // (a tree's draw needs a position: rayrs_mesh_lights_tree_sample)
     const MeshDev t = mesh_host_table(mesh);
     for (uint64_t k = 0; k < n; k++) j[k] = mesh_sample(t, u[2u * k], u[2u * k + 1u], q + 3u * k);
     return RAYRS_OK;
@@ -150,6 +157,7 @@ int rayrs_mesh_lights_density(const rayrs_mesh_lights* mesh, const double* posit
     for (uint64_t k = 0; k < n; k++)
         if (j[k] >= mesh->n) return RAYRS_INVALID_ARG;
     if (mesh->n == 0u) return RAYRS_UNSUPPORTED;
+    if (mesh->tree) return tree_host_density(mesh, position, j, q, n, p);  // LIGHT TREE's p_tri
     const MeshDev t = mesh_host_table(mesh);
     for (uint64_t k = 0; k < n; k++) {
         double l_s[3];

@@ -11,13 +11,15 @@
 namespace rayrs {
 
 // One listed triangle, a 128-byte line: the host scene's f64 vertices, Triangle::new's unit normal and area, and the depth-first
-// slot a walk answers with for it (Trav::best_prim).
+// slot a walk answers with for it (Trav::best_prim).  path, depth and w are a light tree's (radiance_tree_table.h: the left/right
+// word of the entry's leaf, bit k for depth k, the leaf's depth and the entry's power); a group without a tree leaves them 0.
 struct MeshTri {
     double p1[3], p2[3], p3[3];
     double n[3];
     double A;
-    uint32_t slot, pad0;
-    double pad1[2];
+    uint32_t slot, path;
+    uint32_t depth, pad0;
+    double w;
 };
 static_assert(sizeof(MeshTri) == 128, "MeshTri");
 

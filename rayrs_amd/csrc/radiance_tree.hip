@@ -1,0 +1,37 @@
+// radiance_tree.hip -- the radiance queries with a mesh-light group whose triangles are chosen by a light tree (include/rayrs_hip.h
+// LIGHT TREE).  A unit of its own beside radiance_mesh.hip: the kernels of the queries' three starts, without and with the sky,
+// the resolve and the launch.  The wave, and what sets it apart from the mesh wave, is radiance_tree_wave.h's.
+#include <hip/hip_runtime.h>
+
+#include "device_path.h"
+#include "launch_dispatch.h"
+#include "radiance_tree_kernels.h"
+#include "radiance_tree_wave.h"
+#include "radiance_wave_parts.h"
+
+namespace rayrs {
+
+// radiance_tree_wave.h's wave, its paths started by the queries: a batch's rays, points or pixels.
+template <bool COMPACT, bool EXACT, bool SKY, int START>
+__global__ void __launch_bounds__(256) radiance_tree_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, TreeDev tree, SkyDev sky, CameraDev cam) {
+    extern __shared__ uint32_t lds_stack[];
+    tree_wave<COMPACT, EXACT, SKY>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, tree, sky, cam);
+}
+
+__global__ void __launch_bounds__(256) radiance_tree_resolve_kernel(RadianceDev rd) { radiance_resolve(rd); }
+
+hipError_t launch_radiance_tree(bool compact, const SceneDev& sc, const RadianceDev& rd, const LightsDev& lights, const LightSlotsDev& slots,
+                                const TreeDev& tree, const SkyDev& sky, bool with_sky, const CameraDev& cam, int start, int cu_count,
+                                hipStream_t stream) {
+    if (rd.n == 0u) return hipSuccess;
+    const hipError_t e = with_lit_start([&](auto S) {
+        return with_bools([&](auto C, auto E, auto K) {
+            return launch_lane_stacks(&radiance_tree_kernel<decltype(C)::value, decltype(E)::value, decltype(K)::value, decltype(S)::value>,
+                                      radiance_grid_blocks(rd, cu_count), sc.stack_lds, stream, sc, rd, lights, slots, tree, sky, cam);
+        }, compact, sc.exact != 0u, with_sky);
+    }, start);
+    if (e != hipSuccess) return e;
+    return launch_radiance_resolve(radiance_tree_resolve_kernel, rd, stream);
+}
+
+}  // namespace rayrs
