@@ -1567,6 +1567,82 @@ int rayrs_mesh_lights_tree_sample(const rayrs_mesh_lights* mesh, const double* p
 int rayrs_mesh_lights_tree_probability(const rayrs_mesh_lights* mesh, const double* position /* n*3 */, const uint32_t* j /* n */,
                                        uint64_t n, double* p /* n */);
 
+/* SH PROBES.  The radiance that arrives at a point from every direction, projected onto the nine real spherical harmonics of
+ * orders 0 to 2, per colour channel: the form an engine stores a light probe in.  A probe is a point x_i and nothing else; its
+ * directions come from the library's counter RNG, so a result is a function of (seed, index_base + i) and a call on a slice of
+ * the points with index_base moved is the slice of the whole call.  One pair of entry points serves every lighting of the
+ * radiance queries: unlit, DIRECT LIGHTING's lamps, SKY SAMPLING's sky, MESH LIGHTS' group and LIGHT TREE's.
+ *
+ * SH PROBES, specified to the operation.  Everything is f64 and unfused; the elementary functions are rayrs_numeric.h's.  For
+ * probe i at x_i (any f64 is legal) and sample s of S:
+ *
+ *     key = rr_path_key(seed, index_base + i, s)                        RADIANCE QUERY's key
+ *     u1 = draw 0, u2 = draw 1                                           the direction: Sphere::sample (geometry.rs:142-152) on
+ *     phi = 2.0 * RR_PI * u2;  (sn, cs) = rr_sincos(phi)                 the unit sphere at the origin -- LIGHT SAMPLING's sphere
+ *     r = rr_sqrt(u1 * (1.0 - u1))                                       arm without the radius and the centre
+ *     w = ((cs * 2.0) * r, (sn * 2.0) * r, 1.0 - 2.0 * u1)               used as given, NOT normalised again
+ *     L_s = the lighting's path value along the ray (x_i, w), its rng going on at draw 2
+ *
+ * A probe is not a surface: there is no virtual bounce at the point (that is IRRADIANCE's).  Without lights, sky and group the
+ * path is RADIANCE QUERY's; with any of them it is RADIANCE QUERY's path of DIRECT LIGHTING, SKY SAMPLING, MESH LIGHTS or LIGHT
+ * TREE from its first hit on, w = 1.0 for the first ray.
+ *
+ * The basis, in the order (l, m) = (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2), on the components (x, y, z)
+ * of w as they stand -- which axis is "up" is the caller's business: the library rotates nothing, z is the polar axis of these
+ * formulas and of nothing else --, every product taken from left to right as bracketed:
+ *
+ *     Y_0 = K0          Y_1 = K1 * y           Y_2 = K1 * z                          Y_3 = K1 * x
+ *     Y_4 = (K2 * x) * y                       Y_5 = (K2 * y) * z
+ *     Y_6 = K3 * (((3.0 * z) * z) - 1.0)       Y_7 = (K2 * x) * z                    Y_8 = K4 * ((x * x) - (y * y))
+ *     K0 = 0.28209479177387814  K1 = 0.4886025119029199  K2 = 1.0925484305920792  K3 = 0.31539156525252005  K4 = 0.5462742152960396
+ *
+ * (the f64 nearest to sqrt(1/4pi), sqrt(3/4pi), sqrt(15/4pi), sqrt(5/16pi), sqrt(15/16pi)).
+ *
+ * The sums.  The samples are cut into chunks by sample_chunk's rule (RADIANCE QUERY's).  Per chunk j, C_j[k][ch] starts at +0
+ * and, for each sample of the chunk in sample order, C_j[k][ch] = C_j[k][ch] + (Y_k * L_s[ch]): one multiplication, then one
+ * addition.  The probe's sum is C_0 assigned, then += C_j in chunk order, and
+ *
+ *     coeffs[i][k][ch] = sum[k][ch] * (FOUR_PI * (1.0 / (double)S)),   FOUR_PI = 4.0 * RR_PI
+ *
+ * -- the Monte-Carlo estimate of the integral of L * Y_k over the sphere with the uniform density 1 / 4pi.  queries[i] is the
+ * sum of the probe's paths' Bvh::intersect calls, shadow rays included.  NaN and infinite L_s are not laundered: they enter the
+ * sums as they are, and a point with a NaN component gives NaN where its paths do.  max_bounces == 0 gives +0 and no query.
+ *
+ * The bits are these under any schedule: on the device a sample is one item of the lighting's wave (radiance_probe.hip starts
+ * the direct, sky, mesh and tree wave with a start of its own), its L_s and count land in the scene's radiance scratch, and a
+ * projection behind the wave -- a thread per (probe, chunk) that makes w again from the key, then a thread per coefficient that
+ * adds the chunks -- forms the sums in the order above, with no atomic on an f64 and no scratch memory.  A launch takes whole
+ * probes, n_launch * S <= 2^20.  The projection's chunk sums live in a buffer of FIXED size (2^15 (probe, chunk) pairs, 7,208,960
+ * bytes), allocated at the scene's first probe call; a launch with more pairs than that is projected in rounds, so after that
+ * call the _launch form allocates and copies nothing (a group's and the sky's table are uploaded at THEIR first device call).
+ *
+ * rayrs_scene_probes and its _launch form: `lights`, `n_lights` are DIRECT LIGHTING's list (at most RAYRS_MAX_LIGHTS objects,
+ * n_lights == 0 is legal), `sky` is 0 or 1 as MESH LIGHTS' entry points take it, `mesh` is NULL, an area group or a tree group.
+ * No group and no sky: DIRECT LIGHTING's wave (with an empty list: the unlit bits); sky: SKY SAMPLING's; a group of N >= 1: MESH
+ * LIGHTS' or LIGHT TREE's by the handle's kind (an empty group is no group).  coeffs is n * 9 * 3 f64; queries (n u32) may be
+ * NULL.  The _launch form takes device pointers and a stream under RADIANCE QUERY's ordering rule.  Refusals, all decided
+ * before the device is touched, in this order: RAYRS_INVALID_ARG for a NULL scene, position or coeffs; for samples == 0, a
+ * fast_traversal above 1 or a sky above 1; for what DIRECT LIGHTING calls invalid in a list (a NULL list with n_lights > 0, an
+ * index that is no object); for a group of another scene.  Then RAYRS_UNSUPPORTED for samples > 2^20 or max_bounces > 8000; for
+ * samples * (2 * max_bounces + 1) >= 2^32; for what DIRECT LIGHTING calls unsupported in a list (more than RAYRS_MAX_LIGHTS, a
+ * triangle, its material rule) and, with sky = 1, SKY SAMPLING's empty table.  RAYRS_NO_DEVICE comes last; n == 0 is RAYRS_OK.
+ *
+ * Two calls on the host, which need no device: rayrs_probe_directions writes the w of every (i, s), i < n, s < samples, as
+ * n * samples * 3 f64 (RAYRS_INVALID_ARG for a NULL out); rayrs_sh_basis the nine Y_k of m directions, m * 9 f64, NaN and
+ * infinite components going through the formulas as they are.
+ *
+ * Out of scope: orders above 2; a bake or a film of probes; the command line; visibility or depth moments; rayrs_render_multi. */
+int rayrs_scene_probes(rayrs_scene* scene, const double* position /* n*3 */, uint64_t n, uint32_t samples, uint32_t max_bounces,
+                       uint32_t sample_chunk, uint64_t seed, uint64_t index_base, uint32_t fast_traversal, const uint32_t* lights,
+                       uint32_t n_lights, const rayrs_mesh_lights* mesh /* may be NULL: no group */, uint32_t sky,
+                       double* coeffs /* n*9*3 */, uint32_t* queries /* n, may be NULL */);
+int rayrs_scene_probes_launch(rayrs_scene* scene, const double* position, uint64_t n, uint32_t samples, uint32_t max_bounces,
+                              uint32_t sample_chunk, uint64_t seed, uint64_t index_base, uint32_t fast_traversal, const uint32_t* lights,
+                              uint32_t n_lights, const rayrs_mesh_lights* mesh /* may be NULL: no group */, uint32_t sky,
+                              double* coeffs /* n*9*3 */, uint32_t* queries /* n, may be NULL */, void* hip_stream);
+int rayrs_probe_directions(uint64_t seed, uint64_t index_base, uint64_t n, uint32_t samples, double* out /* n*samples*3 */);
+int rayrs_sh_basis(const double* direction /* m*3 */, uint64_t m, double* out /* m*9 */);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -1585,7 +1661,8 @@ int rayrs_mesh_lights_tree_probability(const rayrs_mesh_lights* mesh, const doub
  * rayrs_bake_* and its three structs (BAKE; they are not in the layout table below: all their fields are 4 or 8 bytes wide and
  * naturally aligned), and with rayrs_mesh_lights_*, rayrs_scene_radiance_mesh, rayrs_scene_irradiance_mesh, their _launch forms
  * and rayrs_render_mesh (MESH LIGHTS), and with rayrs_film_create_mesh and rayrs_bake_create_mesh (MESH-LIT FILMS AND BAKES), and with
- * rayrs_mesh_lights_create_tree and rayrs_mesh_lights_tree_* (LIGHT TREE).  The layout table below begins with this
+ * rayrs_mesh_lights_create_tree and rayrs_mesh_lights_tree_* (LIGHT TREE), and with rayrs_scene_probes, its _launch form,
+ * rayrs_probe_directions and rayrs_sh_basis (SH PROBES).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

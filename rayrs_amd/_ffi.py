@@ -48,6 +48,7 @@ SYMBOLS = [
     "rayrs_film_create_mesh", "rayrs_bake_create_mesh",
     "rayrs_mesh_lights_create_tree", "rayrs_mesh_lights_tree_nodes", "rayrs_mesh_lights_tree_entries", "rayrs_mesh_lights_tree_sample",
     "rayrs_mesh_lights_tree_probability",
+    "rayrs_scene_probes", "rayrs_scene_probes_launch", "rayrs_probe_directions", "rayrs_sh_basis",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -57,7 +58,7 @@ SYMBOLS = [
 # rayrs_amd/csrc/rayrs_selftest.h and rayrs_lab.h: private hooks of the library (tests/ and scripts/ only)
 PRIVATE_SYMBOLS = ["rayrs_test_math", "rayrs_test_rng", "rayrs_test_intersect", "rayrs_test_trace", "rayrs_test_path_trace", "rayrs_test_material", "rayrs_test_background",
                    "rayrs_lab_set", "rayrs_lab_stack_need", "rayrs_lab_round_ms", "rayrs_lab_multi_rehearse", "rayrs_lab_query_steps",
-                   "rayrs_lab_ao_refill", "rayrs_lab_ao_turns", "rayrs_lab_radiance_tuning", "rayrs_lab_radiance_turns"]
+                   "rayrs_lab_ao_refill", "rayrs_lab_ao_turns", "rayrs_lab_radiance_tuning", "rayrs_lab_radiance_turns", "rayrs_lab_probe_project_ms"]
 
 
 class MaterialDesc(C.Structure):
@@ -355,7 +356,13 @@ def lib():
                        ("rayrs_mesh_lights_tree_nodes", [vp, vp, vp, vp]),
                        ("rayrs_mesh_lights_tree_entries", [vp, vp, vp, vp]),
                        ("rayrs_mesh_lights_tree_sample", [vp, vp, vp, C.c_uint64, vp, vp, vp]),
-                       ("rayrs_mesh_lights_tree_probability", [vp, vp, vp, C.c_uint64, vp])):
+                       ("rayrs_mesh_lights_tree_probability", [vp, vp, vp, C.c_uint64, vp]),
+                       ("rayrs_scene_probes", [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
+                                               vp, C.c_uint32, vp, C.c_uint32, vp, vp]),
+                       ("rayrs_scene_probes_launch", [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                      C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]),
+                       ("rayrs_probe_directions", [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp]),
+                       ("rayrs_sh_basis", [vp, C.c_uint64, vp])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):
@@ -376,6 +383,8 @@ def lib():
         L.rayrs_lab_radiance_tuning.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
         L.rayrs_lab_radiance_turns.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
                                                C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]
+    if hasattr(L, "rayrs_lab_probe_project_ms"):
+        L.rayrs_lab_probe_project_ms.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.rayrs_test_math.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
     L.rayrs_test_rng.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
     L.rayrs_test_intersect.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp]

@@ -559,6 +559,56 @@ class Scene:
         return self._radiance("rayrs_scene_irradiance", points, normals, samples, max_bounces, sample_chunk, bias, seed, index_base,
                               fast_traversal, queries, lights, direct, mesh)
 
+    # ---- SH probes (include/rayrs_hip.h SH PROBES)
+
+    def probes(self, points, samples: int = 256, max_bounces: int = 50, seed: int = 0x5EED, index_base: int = 0, sample_chunk: int = 0,
+               fast_traversal: bool = False, queries: bool = False, lights=None, direct: bool = False,
+               mesh: Optional["MeshLights"] = None):
+        """The light arriving at every point from all directions, projected onto the nine real spherical harmonics of orders
+        0 to 2 per colour channel: coeffs (n, 9, 3) f64 in the order (l, m) = (0,0), (1,-1), (1,0), (1,1), (2,-2) .. (2,2) on
+        the scene's own axes, and with queries also the closest-hit queries of the probe's paths, (n,) uint32.  Each of the
+        `samples` paths of probe i leaves points[i] in a direction drawn uniformly over the sphere from the key of (seed,
+        index_base + i, s), so a call on points[a:b] with index_base=a returns the slice of the whole call's answer;
+        sample_chunk is radiance()'s rule for the order of the sums.  lights (with direct=True), SKY among them, and mesh (with
+        direct=True) are radiance()'s: the paths are then the direct-lit ones, a tree group included; lights=None and lights=[]
+        are the unlit paths.  A list without direct=True is refused: the one-sample mix has no probes.  sh_radiance() and
+        sh_irradiance() evaluate the answer.  (n, 3) numpy points go through host buffers; float64 tensors on the scene's GPU
+        are answered on torch's current stream and stay on the device."""
+        if lights is not None and len(lights) and not direct:
+            raise ValueError("probes with a light list need direct=True (the one-sample mix has no probes)")
+        if mesh is not None and not direct:
+            raise ValueError("mesh=... needs direct=True (a mesh-light group is a light of direct lighting)")
+        if int(samples) < 1:
+            raise ValueError("samples must be at least 1")
+        if _is_torch(points):
+            import torch
+            if points.dtype != torch.float64 or not points.is_cuda or points.device.index != self.device or not points.is_contiguous():
+                raise ValueError(f"probes on a device tensor take a contiguous float64 tensor on cuda:{self.device}")
+        else:
+            torch = None
+            points = np.ascontiguousarray(points, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError("points must be (n, 3)")
+        n = int(points.shape[0])
+        m = max(n, 1)
+        lights = _light_list([] if lights is None else lights)
+        sky = bool((lights == SKY).any())
+        lights = lights[lights != SKY]
+        args = (n, int(samples), int(max_bounces), int(sample_chunk), int(seed), int(index_base), int(bool(fast_traversal)),
+                lights.ctypes.data if len(lights) else None, len(lights), None if mesh is None else mesh._handle(), int(sky))
+        if torch is None:
+            coeffs, cnt = np.zeros((m, 9, 3)), np.zeros(m, dtype=np.uint32)
+            pts = points if n else np.zeros((1, 3))
+            _ffi.check(self._L.rayrs_scene_probes(self._h, pts.ctypes.data, *args, coeffs.ctypes.data, cnt.ctypes.data), "rayrs_scene_probes")
+        else:
+            dev = points.device
+            coeffs = torch.empty((m, 9, 3), dtype=torch.float64, device=dev)
+            cnt = torch.empty(m, dtype=torch.int32, device=dev).view(torch.uint32)
+            pts = points if n else torch.zeros((1, 3), dtype=torch.float64, device=dev)
+            _ffi.check(self._L.rayrs_scene_probes_launch(self._h, pts.data_ptr(), *args, coeffs.data_ptr(), cnt.data_ptr(),
+                                                         torch.cuda.current_stream(dev).cuda_stream), "rayrs_scene_probes_launch")
+        return (coeffs[:n], cnt[:n]) if queries else coeffs[:n]
+
     # ---- a mesh-light group (include/rayrs_hip.h MESH LIGHTS)
 
     def mesh_lights(self, tris, tree: bool = False) -> "MeshLights":
@@ -600,6 +650,13 @@ class Scene:
     def lab_radiance_tuning(self, refill_below: int = 0, shade_at: int = 0, leaf_min: int = 0):
         """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_radiance_tuning: for tests and scripts/ubench only; 0 = the default."""
         _ffi.check(self._L.rayrs_lab_radiance_tuning(self._h, int(refill_below), int(shade_at), int(leaf_min)), "rayrs_lab_radiance_tuning")
+
+    def lab_probe_project_ms(self, n: int, samples: int, sample_chunk: int = 0, repeats: int = 10) -> float:
+        """rayrs_amd/csrc/rayrs_lab.h rayrs_lab_probe_project_ms: for scripts/ubench only; ms of one projection of n probes."""
+        ms = C.c_float()
+        _ffi.check(self._L.rayrs_lab_probe_project_ms(self._h, int(n), int(samples), int(sample_chunk), int(repeats), C.addressof(ms)),
+                   "rayrs_lab_probe_project_ms")
+        return ms.value
 
     def close(self):
         if self._h is not None:
@@ -787,6 +844,73 @@ def mesh_emitters(objects) -> List[int]:
             out.append(index)
         index += 1
     return out
+
+
+# ---- SH probes on the host (include/rayrs_hip.h SH PROBES): no device is needed
+
+def probe_directions(n: int, samples: int, seed: int = 0x5EED, index_base: int = 0):
+    """The direction of every sample of the probes index_base .. index_base + n - 1 of a Scene.probes call: (n, samples, 3) f64."""
+    n, samples = int(n), int(samples)
+    if n < 0 or samples < 0:
+        raise ValueError("n and samples must not be negative")
+    out = np.zeros((n, samples, 3))
+    buf = out if out.size else np.zeros(3)
+    _ffi.check(_ffi.lib().rayrs_probe_directions(int(seed), int(index_base), n, samples, buf.ctypes.data), "rayrs_probe_directions")
+    return out
+
+
+def sh_basis(directions):
+    """Y_0 .. Y_8 of every direction (m, 3), used as given: (m, 9) f64."""
+    d = np.ascontiguousarray(directions, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError("directions must be (m, 3)")
+    out = np.zeros((max(len(d), 1), 9))
+    _ffi.check(_ffi.lib().rayrs_sh_basis(d.ctypes.data if len(d) else out.ctypes.data, len(d), out.ctypes.data), "rayrs_sh_basis")
+    return out[:len(d)]
+
+
+_SH_K = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+_SH_BAND = (1.0, 2.0 / 3.0, 2.0 / 3.0, 2.0 / 3.0, 0.25, 0.25, 0.25, 0.25, 0.25)   # clamped cosine over pi: 1, 2/3, 1/4 on l = 0, 1, 2
+
+
+def _sh_eval(coeffs, directions, band):
+    """sum_k band_k c_k Y_k(d): plain array arithmetic on numpy arrays or torch tensors, coeffs (..., 9, 3) and directions (..., 3)
+    broadcast over their leading axes -> (..., 3)."""
+    k0, k1, k2, k3, k4 = _SH_K
+    x, y, z = directions[..., 0], directions[..., 1], directions[..., 2]
+    Y = (k0 + 0.0 * x, k1 * y, k1 * z, k1 * x, k2 * x * y, k2 * y * z, k3 * (3.0 * z * z - 1.0), k2 * x * z, k4 * (x * x - y * y))
+    out = None
+    for k in range(9):
+        term = (band[k] * Y[k])[..., None] * coeffs[..., k, :]
+        out = term if out is None else out + term
+    return out
+
+
+def sh_radiance(coeffs, directions):
+    """The radiance the coefficients stand for in every direction, sum_k c_k Y_k(d): coeffs (..., 9, 3), directions (..., 3)
+    of unit length, broadcast over the leading axes -> (..., 3).  numpy in, numpy out; torch in, torch out."""
+    return _sh_eval(coeffs, directions, (1.0,) * 9)
+
+
+def sh_irradiance(coeffs, normals):
+    """The clamped-cosine convolution of the coefficients around every normal, divided by pi: Scene.irradiance's unit (a
+    Lambertian texel of albedo rho radiates rho times the value).  The band factors are 1, 2/3 and 1/4 on l = 0, 1, 2.  Shapes and
+    array kinds as sh_radiance()."""
+    return _sh_eval(coeffs, normals, _SH_BAND)
+
+
+def probe_grid(scene: Scene, shape):
+    """(nx * ny * nz, 3) f64 points at the cell centres of a grid of `shape` = (nx, ny, nz) cells over the scene's root box, x
+    fastest: probe positions for Scene.probes.  A scene whose root box is not finite (an unbounded plane) has no grid."""
+    nx, ny, nz = (int(v) for v in shape)
+    if min(nx, ny, nz) < 1:
+        raise ValueError("shape must be three positive cell counts")
+    b = np.array(scene.info()["root_box"], dtype=np.float64)
+    if not np.isfinite(b).all():
+        raise ValueError("the scene's root box is not finite: give the probe positions yourself")
+    axes = [b[2 * a] + (np.arange(m) + 0.5) * ((b[2 * a + 1] - b[2 * a]) / m) for a, m in enumerate((nx, ny, nz))]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.ascontiguousarray(np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1))
 
 
 class MeshLights:

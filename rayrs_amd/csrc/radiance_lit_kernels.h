@@ -34,6 +34,9 @@ struct LightsDev {
 // bias, n) with albedo (1, 1, 1) -- with K = 0 IRRADIANCE's ray on draws 0 and 1 --; the camera's pixel, sample_ray on draws
 // 0 and 1, draw 2 next.
 constexpr int LIT_START_RAY = 0, LIT_START_POINT = 1, LIT_START_PIXEL = 2;
+// SH PROBES' start (radiance_probe_kernels.h ProbeStart, never a with_lit_start value): the ray leaves the probe's point along
+// the direction made on draws 0 and 1, draw 2 next; there is no second array and no virtual bounce.
+constexpr int LIT_START_PROBE = 3;
 // with_lit_start(f, start) calls f(S) with S() the LIT_START_* that `start` is, as launch_dispatch.h's with_bools does for bools.
 template <class F>
 auto with_lit_start(F f, int start) {

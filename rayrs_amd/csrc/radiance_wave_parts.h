@@ -4,6 +4,7 @@
 #pragma once
 #include "device_path.h"
 #include "radiance_lit_kernels.h"
+#include "radiance_probe_table.h"
 
 namespace rayrs {
 
@@ -30,7 +31,8 @@ struct QueryStart {
 // What every sample starts from: its RNG and a ray.  LIT_START_PIXEL: sample_key and the camera's sample_ray on draws 0 and 1.
 // LIT_START_RAY: the caller's ray, draw 0 next.  LIT_START_POINT: o is the point moved along its normal by the bias and d is the
 // NORMAL, draw 0 next -- the first direction is the lighting's to make (device_path.h cosine_direction, or its own operation at
-// the point).  By value: handed out by reference, the six doubles go through the stack in the point instances.
+// the point).  LIT_START_PROBE: o is the probe's point, d the direction of draws 0 and 1 (radiance_probe_table.h), draw 2 next.
+// By value: handed out by reference, the six doubles go through the stack in the point instances.
 struct SampleStart {
     Rng rng;
     V3 o, d;
@@ -47,6 +49,14 @@ RR_DEV SampleStart sample_start(const START& start, const RadianceDev& rd, const
         return SampleStart{rng, o, d};
     }
     const double* pa = rd.a + (size_t)ray * 3u;
+    if (START::KIND == LIT_START_PROBE) {  // (rd.b is not read: a probe has no second array)
+        rng = Rng{rr_path_key(rd.seed, rd.index_base + ray, (uint64_t)s), 0};
+        const double u1 = rng.next();
+        const double u2 = rng.next();
+        double w[3];
+        probe_direction(u1, u2, w);
+        return SampleStart{rng, mk(pa[0], pa[1], pa[2]), mk(w[0], w[1], w[2])};
+    }
     const double* pb = rd.b + (size_t)ray * 3u;
     const V3 a = mk(pa[0], pa[1], pa[2]), b = mk(pb[0], pb[1], pb[2]);
     rng = Rng{rr_path_key(rd.seed, rd.index_base + ray, (uint64_t)s), 0};

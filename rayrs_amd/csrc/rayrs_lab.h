@@ -105,6 +105,13 @@ int rayrs_lab_radiance_turns(rayrs_scene* scene, uint32_t irradiance, const doub
                              uint32_t max_bounces, uint32_t sample_chunk, double bias, uint64_t seed, uint64_t index_base,
                              uint32_t fast_traversal, uint32_t* queries, uint64_t turns[3]);
 
+/* SH PROBES' projection alone (radiance_probe.hip probe_project_kernel and probe_gather_kernel, in their rounds): `repeats` times
+ * on the null stream over n probes of `samples` samples, n * samples <= 2^20, reading whatever the scene's radiance scratch
+ * holds (the last probe call's paths; the projection's time does not depend on the values) and writing to the host forms'
+ * staging, between two HIP events behind a warm-up; *ms is the mean of one (scripts/ubench/probes_bench.py).  Waits for the
+ * scene's work first. */
+int rayrs_lab_probe_project_ms(rayrs_scene* scene, uint32_t n, uint32_t samples, uint32_t sample_chunk, uint32_t repeats, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

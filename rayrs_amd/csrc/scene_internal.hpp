@@ -138,6 +138,13 @@ struct rayrs_scene {
         rayrs::DevBuf d_table;
     };
     Sky sky;
+    // What SH probes (radiance_probe_abi.cpp, include/rayrs_hip.h SH PROBES) keep beside the radiance queries' scratch and
+    // staging, which they share: the projection's chunk sums (radiance_probe_kernels.h PROBE_CHUNK_BYTES, a fixed size),
+    // allocated by the scene's first probe call and used in the scratch's order.
+    struct Probes {
+        rayrs::DevBuf d_chunks;
+    };
+    Probes probes;
     // Scenes whose walk tree is at most one record are rendered by local_pool.hip: every path resident in LDS.
     bool local_ok = false;
     rayrs::LocalScene local = {};
