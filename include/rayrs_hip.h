@@ -1643,6 +1643,91 @@ int rayrs_scene_probes_launch(rayrs_scene* scene, const double* position, uint64
 int rayrs_probe_directions(uint64_t seed, uint64_t index_base, uint64_t n, uint32_t samples, double* out /* n*samples*3 */);
 int rayrs_sh_basis(const double* direction /* m*3 */, uint64_t m, double* out /* m*9 */);
 
+/* LIGHTMAP ATLAS.  The step before a BAKE of lightmap texels: a mesh's triangles, rasterised in the UV space of a W x H atlas into
+ * the list of covered texels with their world positions and normals -- the points and normals rayrs_bake_create wants -- and the
+ * way back, per-texel values assembled into an (H, W, C) image whose chart borders are dilated.  An atlas is bound to a mesh, a
+ * UV layout, a size and a device, and to no scene (rayrs_history is the precedent); it outlives every scene.
+ *
+ * LIGHTMAP ATLAS, specified to the operation.  Everything is f64 `+ - * /` and comparisons, unfused, in the order written; every
+ * condition is written in its positive form, so that a NaN takes the "no" side.  Inputs: verts, nv * 3 f32 (vert_is_f32 = 1,
+ * each widened exactly, as rayrs_object_from_triangles_f32 widens) or f64; idx, m * 3 u32; uvs, PER CORNER, m * 3 * 2 f64
+ * (u, v of corner c of triangle k at uvs[(k*3 + c)*2 ..]); W = width, H = height; flip.  Texel (x, y), 0 <= x < W, 0 <= y < H,
+ * has the index y*W + x and its centre at px = (double)x + 0.5, py = (double)y + 0.5.
+ *
+ * COVERAGE.  For triangle k with corners (u_c, v_c), c = 0, 1, 2:
+ *     U_c = u_c * (double)W,   V_c = v_c * (double)H
+ *     w0(px, py) = (U2 - U1) * (py - V1) - (V2 - V1) * (px - U1)        the edge function opposite corner 0
+ *     w1(px, py) = (U0 - U2) * (py - V2) - (V0 - V2) * (px - U2)        ... corner 1
+ *     w2(px, py) = (U1 - U0) * (py - V0) - (V1 - V0) * (px - U0)        ... corner 2
+ *     area2 = w2(U2, V2) = (U1 - U0) * (V2 - V0) - (V1 - V0) * (U2 - U0)
+ * -- four differences, two products, one subtraction each.  If area2 < 0 the triangle is wound the other way: w0, w1, w2 and
+ * area2 are negated (exactly).  A triangle of which some U_c or V_c is not finite, or whose area2 is not finite or == 0, covers
+ * nothing.  Texel (x, y) is a CANDIDATE of k iff
+ *     (double)(x + 1) >= Umin  &&  (double)x <= Umax  &&  (double)(y + 1) >= Vmin  &&  (double)y <= Vmax,
+ * Umin, Umax, Vmin, Vmax the smallest and largest of the U_c and of the V_c (every texel whose centre lies in the triangle's
+ * bounding box is one, and the rule is part of the operation so that no rounding of an edge function can reach outside it); k
+ * COVERS a candidate iff w0 >= 0 && w1 >= 0 && w2 >= 0 at its centre.  UVs outside [0, 1] are legal: what lies outside the
+ * atlas has no texel, nothing wraps.  The OWNER of a texel is the LOWEST k that covers it, RAYRS_LIGHTMAP_NO_OWNER (0xFFFFFFFF)
+ * if none does: a centre on which the edge functions of two triangles that share the edge are both exactly 0 belongs to the
+ * lower index and is lost by neither; of two triangles laid over each other the lower index wins.
+ *
+ * TEXEL RECORD of an owned texel, k its owner, P_c = verts[idx[k*3 + c]]:
+ *     b1 = w1 / area2,   b2 = w2 / area2,   b0 = (1.0 - b1) - b2                     (after the negation, if any)
+ *     position = (b0 * P0 + b1 * P1) + b2 * P2                                       per component
+ *     normal   = Triangle::new's unit normal of (P0, P1, P2), geometry.rs:341-353, from the routine MESH LIGHTS' table uses on
+ *                the host (radiance_mesh_table.h mesh_tri_finish): e1 = P1 - P0, e2 = P2 - P0, nrm = e1 x e2,
+ *                n = nrm * (1.0 / rr_sqrt((nrm.x*nrm.x + nrm.y*nrm.y) + nrm.z*nrm.z)) -- the bits rayrs_scene_intersect reports
+ *                for a hit on a triangle of these vertices, not flipped towards anything; each component negated if flip.
+ * A triangle whose normal is not finite (no area in space) keeps its texels, with that normal: BAKE has its rules for a NaN
+ * normal (which NaN it is, sign and payload, is not specified).  The TEXEL LIST is the owned texels in ascending texel index; n
+ * is their number.
+ *
+ * ASSEMBLY of values (n rows of C channels, 1 <= C <= 4, row i belonging to list entry i) with dilate = d >= 0.  The image is
+ * H * W * C f64, the validity plane H * W bytes.  Row i goes to texel index[i], which becomes valid (1); every other texel is
+ * +0 and invalid (0).  Then d rounds of dilation.  In a round every invalid texel (x, y) with at least one valid texel --
+ * valid BEFORE the round -- among its eight neighbours inside the atlas becomes valid, with, per channel,
+ *     s = +0;  for dy = -1, 0, 1 (outer), dx = -1, 0, 1 (inner), the valid neighbours (x + dx, y + dy) in that order: s = s + value;
+ *     value = s / (double)count
+ * -- count the number of those neighbours.  Every other texel keeps its value and its validity.  NaN and infinite values
+ * travel as values.  (A round that makes no texel valid ends the rounds: every later one would change nothing.)
+ *
+ * The bits are these under any schedule.  lightmap.hip's owner pass gives each lane of a wave one triangle: a lane walks the
+ * candidates of a triangle with at most 64 of them itself; the wave's 64 lanes stride the candidates of each triangle of the
+ * wave's with up to 65536; a triangle with more goes to a list that a second launch strides with the whole grid.  The only
+ * write to the owner plane is an integer atomicMin of k; there is no atomic on an f64.  Then a stream compaction in texel order
+ * (flag and count, a scan of the workgroups' counts), and the record pass, a thread per texel, forms w1, w2 and area2 again for
+ * the owner and writes the record at the texel's place in the list.  Assembly is a scatter kernel and one dilation kernel over
+ * two planes, run once per round.
+ *
+ * Refusals, in this order: RAYRS_INVALID_ARG for a NULL out or handle; for NULL verts, idx or uvs with m > 0; for vert_is_f32
+ * or flip above 1; for a width or a height of 0 or above RAYRS_LIGHTMAP_MAX_SIDE (16384); for an idx entry >= nv; in
+ * rayrs_lightmap_assemble for NULL values with n > 0 or a NULL image, channels outside 1..4, a negative dilate.  Then
+ * RAYRS_NO_DEVICE where `device` is no HIP device of this machine (device = -1 among them).  m = 0 is legal and gives an empty
+ * atlas (n = 0).  The calls on one atlas come from one thread at a time; two atlases share nothing.
+ *
+ * Out of scope: chart-preserving or angle-based unwrapping (rayrs_amd.unwrap_triangles lays triangles out one by one);
+ * conservative (overlap) coverage and clamped barycentrics for border texels; supersampled texels and per-texel jitter;
+ * interpolated vertex normals; a device-resident hand-over of the texel list to a bake; the command line; bilinear sampling of
+ * the result; seam stitching across charts. */
+typedef struct rayrs_lightmap rayrs_lightmap;
+#define RAYRS_LIGHTMAP_NO_OWNER 0xFFFFFFFFu
+#define RAYRS_LIGHTMAP_MAX_SIDE 16384u
+
+int rayrs_lightmap_create(int device, const void* verts /* nv*3 */, uint32_t vert_is_f32, uint32_t nv, const uint32_t* idx /* m*3 */,
+                          uint32_t m, const double* uvs /* m*3*2 */, uint32_t width, uint32_t height, uint32_t flip,
+                          rayrs_lightmap** out);
+void rayrs_lightmap_destroy(rayrs_lightmap* lightmap);
+/* n, the length of the texel list. */
+int rayrs_lightmap_count(const rayrs_lightmap* lightmap, uint64_t* n);
+/* The texel list into host buffers, each of which may be NULL: the texel indices (n u32, ascending), the positions, the normals
+ * and the barycentrics (b0, b1, b2) (n * 3 f64 each). */
+int rayrs_lightmap_texels(rayrs_lightmap* lightmap, uint32_t* index, double* points, double* normals, double* bary);
+/* The owner plane, H * W u32. */
+int rayrs_lightmap_owner(rayrs_lightmap* lightmap, uint32_t* owner);
+/* ASSEMBLY above: values n * channels f64 (host); image H * W * channels f64; valid H * W bytes, may be NULL. */
+int rayrs_lightmap_assemble(rayrs_lightmap* lightmap, const double* values, uint32_t channels, int32_t dilate, double* image,
+                            uint8_t* valid);
+
 /* The boundary's version: bumped whenever a struct of this header changes the meaning of a field or an entry point
  * its behaviour.  5 = round 5: rayrs_render_params.exact_traversal became fast_traversal (opposite sense: zero is now
  * the reference's visit set), the device self-test hooks left this header.  6 = round 6: rayrs_scene_info_t.hot_*,
@@ -1662,7 +1747,7 @@ int rayrs_sh_basis(const double* direction /* m*3 */, uint64_t m, double* out /*
  * naturally aligned), and with rayrs_mesh_lights_*, rayrs_scene_radiance_mesh, rayrs_scene_irradiance_mesh, their _launch forms
  * and rayrs_render_mesh (MESH LIGHTS), and with rayrs_film_create_mesh and rayrs_bake_create_mesh (MESH-LIT FILMS AND BAKES), and with
  * rayrs_mesh_lights_create_tree and rayrs_mesh_lights_tree_* (LIGHT TREE), and with rayrs_scene_probes, its _launch form,
- * rayrs_probe_directions and rayrs_sh_basis (SH PROBES).  The layout table below begins with this
+ * rayrs_probe_directions and rayrs_sh_basis (SH PROBES), and with rayrs_lightmap_* (LIGHTMAP ATLAS).  The layout table below begins with this
  * number, so a binding that checks itself against the table fails on a version change as well.  A binding MUST compare
  * rayrs_abi_version() with the RAYRS_ABI_VERSION it was written against when it loads the library.  Every struct a caller fills must be zero-initialised
  * first: fields are added where padding used to be, and values out of a field's range are refused. */

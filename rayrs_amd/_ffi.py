@@ -49,6 +49,8 @@ SYMBOLS = [
     "rayrs_mesh_lights_create_tree", "rayrs_mesh_lights_tree_nodes", "rayrs_mesh_lights_tree_entries", "rayrs_mesh_lights_tree_sample",
     "rayrs_mesh_lights_tree_probability",
     "rayrs_scene_probes", "rayrs_scene_probes_launch", "rayrs_probe_directions", "rayrs_sh_basis",
+    "rayrs_lightmap_create", "rayrs_lightmap_destroy", "rayrs_lightmap_count", "rayrs_lightmap_texels", "rayrs_lightmap_owner",
+    "rayrs_lightmap_assemble",
     "rayrs_abi_layout", "rayrs_abi_version",
     "rayrs_io_last_error", "rayrs_buffer_free", "rayrs_ply_load", "rayrs_ply_save", "rayrs_obj_load", "rayrs_obj_load_spheres",
     "rayrs_hdr_load", "rayrs_hdr_save", "rayrs_image_to_bytes", "rayrs_ppm_save", "rayrs_png_save",
@@ -58,7 +60,7 @@ SYMBOLS = [
 # rayrs_amd/csrc/rayrs_selftest.h and rayrs_lab.h: private hooks of the library (tests/ and scripts/ only)
 PRIVATE_SYMBOLS = ["rayrs_test_math", "rayrs_test_rng", "rayrs_test_intersect", "rayrs_test_trace", "rayrs_test_path_trace", "rayrs_test_material", "rayrs_test_background",
                    "rayrs_lab_set", "rayrs_lab_stack_need", "rayrs_lab_round_ms", "rayrs_lab_multi_rehearse", "rayrs_lab_query_steps",
-                   "rayrs_lab_ao_refill", "rayrs_lab_ao_turns", "rayrs_lab_radiance_tuning", "rayrs_lab_radiance_turns", "rayrs_lab_probe_project_ms"]
+                   "rayrs_lab_ao_refill", "rayrs_lab_ao_turns", "rayrs_lab_radiance_tuning", "rayrs_lab_radiance_turns", "rayrs_lab_probe_project_ms", "rayrs_lab_lightmap_ms"]
 
 
 class MaterialDesc(C.Structure):
@@ -362,7 +364,14 @@ def lib():
                        ("rayrs_scene_probes_launch", [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                                       C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]),
                        ("rayrs_probe_directions", [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp]),
-                       ("rayrs_sh_basis", [vp, C.c_uint64, vp])):
+                       ("rayrs_sh_basis", [vp, C.c_uint64, vp]),
+                       ("rayrs_lightmap_create", [C.c_int, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(vp)]),
+                       ("rayrs_lightmap_destroy", [vp]),
+                       ("rayrs_lightmap_count", [vp, C.POINTER(C.c_uint64)]),
+                       ("rayrs_lightmap_texels", [vp, vp, vp, vp, vp]),
+                       ("rayrs_lightmap_owner", [vp, vp]),
+                       ("rayrs_lightmap_assemble", [vp, vp, C.c_uint32, C.c_int32, vp, vp])):
         if hasattr(L, name) or "RAYRS_HIP_LIB" not in os.environ:
             getattr(L, name).argtypes = args
     if hasattr(L, "rayrs_history_destroy"):
@@ -373,6 +382,10 @@ def lib():
     if hasattr(L, "rayrs_bake_destroy"):
         L.rayrs_bake_destroy.restype = None
         L.rayrs_bake_state_bytes.restype = C.c_uint64
+    if hasattr(L, "rayrs_lightmap_destroy"):
+        L.rayrs_lightmap_destroy.restype = None
+    if hasattr(L, "rayrs_lab_lightmap_ms"):
+        L.rayrs_lab_lightmap_ms.argtypes = [vp, vp]
     if hasattr(L, "rayrs_lab_query_steps"):  # (private: rayrs_amd/csrc/rayrs_lab.h; an older build behind RAYRS_HIP_LIB has none)
         L.rayrs_lab_query_steps.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]
     if hasattr(L, "rayrs_lab_ao_refill"):

@@ -1531,6 +1531,177 @@ def bake_until(bake, tau: float, pass_samples: int = 16, max_samples: int = 1024
     return st, reason
 
 
+# ---- lightmap atlases (include/rayrs_hip.h LIGHTMAP ATLAS)
+
+LIGHTMAP_MAX_SIDE = 16384
+
+
+def unwrap_triangles(m: int, cell: int = 8, gutter: int = 1):
+    """A UV layout for m triangles that ignores the mesh's shape: (uvs (m, 3, 2) f64, width, height).  Triangles 2c and 2c + 1
+    share square cell c -- `cell` texels a side, the cells row by row in a grid of ceil(sqrt(ceil(m / 2))) columns -- as the two
+    right triangles on either side of its diagonal, each inset so that at least `gutter` texels lie between the texels of any two
+    triangles (no texel one triangle covers has a texel of another within `gutter` steps, diagonal steps included).  The atlas
+    is the grid's size times `cell`; the layout is a function of (m, cell, gutter) alone.  It is NOT a chart-preserving unwrap:
+    neighbouring triangles of the mesh are not neighbours in the atlas, and every triangle gets the same texels whatever its
+    size.  In cell coordinates (texels, L = cell - gutter, T = cell - 2 * gutter - 2) the even triangle is (0.25, 0.25),
+    (T + 1.25, 0.25), (0.25, T + 1.25) and covers the texels i + j <= T; the odd one is (L - 0.25, L - 0.25), (T + 2 * gutter +
+    1.75 - L, L - 0.25), (L - 0.25, T + 2 * gutter + 1.75 - L) and covers i + j >= T + 2 * gutter + 1 of 0 .. L - 1."""
+    m, cell, gutter = int(m), int(cell), int(gutter)
+    if m < 0 or gutter < 0 or cell < 2 * gutter + 2:
+        raise ValueError("unwrap_triangles: m >= 0, gutter >= 0 and cell >= 2 * gutter + 2")
+    cells = (m + 1) // 2
+    cols = 1
+    while cols * cols < cells:
+        cols += 1
+    rows = max(1, -(-cells // cols))
+    width, height = cols * cell, rows * cell
+    if width > LIGHTMAP_MAX_SIDE or height > LIGHTMAP_MAX_SIDE:
+        raise ValueError(f"unwrap_triangles: a {width} x {height} atlas is above {LIGHTMAP_MAX_SIDE} a side")
+    L, T = float(cell - gutter), float(cell - 2 * gutter - 2)
+    lo = T + 2.0 * gutter + 1.75 - L
+    corners = np.array([[(0.25, 0.25), (T + 1.25, 0.25), (0.25, T + 1.25)],
+                        [(L - 0.25, L - 0.25), (lo, L - 0.25), (L - 0.25, lo)]])
+    k = np.arange(m)
+    c = k // 2
+    origin = np.stack([(c % cols) * cell, (c // cols) * cell], axis=-1).astype(np.float64)   # (m, 2)
+    uvs = (corners[k % 2] + origin[:, None, :]) / np.array([float(width), float(height)])
+    return np.ascontiguousarray(uvs.reshape(m, 3, 2)), width, height
+
+
+class Lightmap:
+    """A lightmap atlas (include/rayrs_hip.h LIGHTMAP ATLAS): the triangles (verts (nv, 3) f32 or f64, idx (m, 3)) rasterised in
+    UV space -- uvs per corner (m, 3, 2), or per vertex (nv, 2), expanded through idx -- into the texels of a width x height
+    atlas on HIP device `device`.  n texels are owned; texels() gives their indices, world positions and normals (flip=True: the
+    normals negated), which is what a Bake wants (bake()), and image() takes per-texel values back into an (H, W, C) picture with
+    dilated chart borders.  Texel (x, y) has its centre at u = (x + 0.5) / width, v = (y + 0.5) / height, and row y of the image
+    is v's: nothing is turned upside down.  The atlas is bound to no scene."""
+
+    def __init__(self, verts, idx, uvs, width: int, height: int, flip: bool = False, device: int = 0):
+        verts = np.ascontiguousarray(verts)
+        if verts.dtype not in (np.float32, np.float64):
+            verts = verts.astype(np.float64)
+        idx = np.asarray(idx)
+        if verts.ndim != 2 or verts.shape[1] != 3 or idx.ndim != 2 or idx.shape[1] != 3:
+            raise ValueError("verts must be (nv, 3) and idx (m, 3)")
+        if idx.dtype.kind not in "iu" or (idx.size and (int(idx.min()) < 0 or int(idx.max()) >= len(verts))):
+            raise ValueError("idx must hold integers below the number of vertices")
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        uvs = np.ascontiguousarray(uvs, dtype=np.float64)
+        if uvs.shape == (len(verts), 2) and uvs.shape != (len(idx), 3, 2):
+            uvs = np.ascontiguousarray(uvs[idx.astype(np.int64)])
+        if uvs.shape != (len(idx), 3, 2):
+            raise ValueError("uvs must be (m, 3, 2) per corner or (nv, 2) per vertex")
+        width, height = int(width), int(height)
+        if not (1 <= width <= LIGHTMAP_MAX_SIDE and 1 <= height <= LIGHTMAP_MAX_SIDE):
+            raise ValueError(f"width and height must be 1 .. {LIGHTMAP_MAX_SIDE}")
+        self._L, self._h = _ffi.lib(), None
+        self.width, self.height, self.flip, self.device, self.m = width, height, bool(flip), int(device), len(idx)
+        dummy = np.zeros(6)
+        h = C.c_void_p()
+        _ffi.check(self._L.rayrs_lightmap_create(self.device, verts.ctypes.data if len(verts) else dummy.ctypes.data,
+                                                 1 if verts.dtype == np.float32 else 0, len(verts),
+                                                 idx.ctypes.data if len(idx) else dummy.ctypes.data, len(idx),
+                                                 uvs.ctypes.data if len(idx) else dummy.ctypes.data, width, height, 1 if flip else 0,
+                                                 C.byref(h)), "rayrs_lightmap_create")
+        self._h = h
+        n = C.c_uint64(0)
+        _ffi.check(self._L.rayrs_lightmap_count(self._h, C.byref(n)), "rayrs_lightmap_count")
+        self.n = int(n.value)
+
+    @classmethod
+    def from_object(cls, obj, uvs=None, cell: int = 8, gutter: int = 1, width: Optional[int] = None, height: Optional[int] = None,
+                    flip: bool = False, device: int = 0) -> "Lightmap":
+        """The atlas of a kind == "mesh" Object (or the one-element list Object.from_triangles returns).  uvs=None: every
+        triangle gets its own texels (unwrap_triangles(m, cell, gutter)), and the atlas its size from that; with uvs, width and
+        height are required."""
+        if isinstance(obj, (list, tuple)) and len(obj) == 1:
+            obj = obj[0]
+        if not isinstance(obj, Object) or obj.kind != "mesh":
+            raise ValueError('Lightmap.from_object takes an Object of kind "mesh"')
+        if uvs is None:
+            uvs, w, h = unwrap_triangles(len(obj.idx), cell, gutter)
+            if (width is not None and int(width) != w) or (height is not None and int(height) != h):
+                raise ValueError(f"the per-triangle unwrap of this mesh is {w} x {h}")
+            width, height = w, h
+        elif width is None or height is None:
+            raise ValueError("with uvs, width and height are required")
+        return cls(obj.verts, obj.idx, uvs, width, height, flip=flip, device=device)
+
+    def _open(self, where):
+        if self._h is None:
+            raise _ffi.RayrsError(-1, where)  # a closed atlas
+        return self._h
+
+    @property
+    def coverage(self) -> float:
+        """The owned share of the atlas's texels."""
+        return self.n / float(self.width * self.height)
+
+    def _list(self, index=False, points=False, normals=False, bary=False):
+        m = max(self.n, 1)
+        out = [np.zeros(m, dtype=np.uint32) if index else None] + [np.zeros((m, 3)) if want else None for want in (points, normals, bary)]
+        _ffi.check(self._L.rayrs_lightmap_texels(self._open("rayrs_lightmap_texels"), *[None if a is None else a.ctypes.data for a in out]),
+                   "rayrs_lightmap_texels")
+        return [None if a is None else a[:self.n] for a in out]
+
+    def texels(self):
+        """(index (n,) uint32 ascending: y * width + x, points (n, 3) f64, normals (n, 3) f64)."""
+        index, points, normals, _ = self._list(index=True, points=True, normals=True)
+        return index, points, normals
+
+    def bary(self):
+        """The barycentrics (b0, b1, b2) of the texels' centres in their owners, (n, 3) f64."""
+        return self._list(bary=True)[3]
+
+    def owner(self):
+        """(H, W) int64: the triangle that owns each texel, -1 where none does."""
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        _ffi.check(self._L.rayrs_lightmap_owner(self._open("rayrs_lightmap_owner"), out.ctypes.data), "rayrs_lightmap_owner")
+        own = out.astype(np.int64)
+        own[out == 0xFFFFFFFF] = -1
+        return own
+
+    def image(self, values, dilate: int = 2, return_valid: bool = False):
+        """values (n,) or (n, C), C = 1 .. 4, one row per texel of texels() -> the (H, W, C) f64 image (a (n,) input: (H, W)):
+        the rows at their texels, +0 elsewhere, then `dilate` rounds in which every texel without a value that has neighbours
+        with one takes their mean.  return_valid: also the (H, W) bool plane of the texels that hold a value."""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        flat = values.ndim == 1
+        if flat:
+            values = values.reshape(-1, 1)
+        if values.ndim != 2 or values.shape[0] != self.n or not 1 <= values.shape[1] <= 4:
+            raise ValueError(f"values must be ({self.n},) or ({self.n}, C) with C = 1 .. 4")
+        if int(dilate) < 0 or int(dilate) >= 2 ** 31:
+            raise ValueError("dilate must be 0 .. 2^31 - 1")
+        ch = values.shape[1]
+        img, valid = np.zeros((self.height, self.width, ch)), np.zeros((self.height, self.width), dtype=np.uint8)
+        if self.n == 0:
+            values = np.zeros((1, ch))
+        _ffi.check(self._L.rayrs_lightmap_assemble(self._open("rayrs_lightmap_assemble"), values.ctypes.data, ch, int(dilate), img.ctypes.data,
+                                                   valid.ctypes.data), "rayrs_lightmap_assemble")
+        if flat:
+            img = img[:, :, 0]
+        return (img, valid.astype(bool)) if return_valid else img
+
+    def bake(self, scene: "Scene", **bake_args) -> "Bake":
+        """Bake(scene, points, normals, kind="irradiance", **bake_args) at the atlas's texels; bake.values() then goes to image()."""
+        if "kind" in bake_args:
+            raise ValueError("a lightmap's bake is an irradiance bake")
+        _, points, normals = self.texels()
+        return Bake(scene, points, normals, kind="irradiance", **bake_args)
+
+    def close(self):
+        if self._h is not None:
+            self._L.rayrs_lightmap_destroy(self._h)   # (no scene to outlive: the atlas owns all it frees)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- temporal accumulation (include/rayrs_hip.h TEMPORAL ACCUMULATION)
 
 # Starting points, not tuned values: the weight a history pixel may carry into a blend, in samples (16 frames of 16); the

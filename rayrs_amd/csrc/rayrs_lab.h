@@ -112,6 +112,11 @@ int rayrs_lab_radiance_turns(rayrs_scene* scene, uint32_t irradiance, const doub
  * scene's work first. */
 int rayrs_lab_probe_project_ms(rayrs_scene* scene, uint32_t n, uint32_t samples, uint32_t sample_chunk, uint32_t repeats, float* ms);
 
+/* LIGHTMAP ATLAS: the HIP-event times of the atlas's rayrs_lightmap_create, in milliseconds -- the owner pass (the plane's fill
+ * included), the compaction's count and scan, the record pass (the list's allocation included)
+ * (scripts/ubench/lightmap_bench.py). */
+int rayrs_lab_lightmap_ms(const rayrs_lightmap* lightmap, double ms[3]);
+
 #ifdef __cplusplus
 }
 #endif
