@@ -1,5 +1,5 @@
 // bake.hip -- the bake (include/rayrs_hip.h BAKE): progressive, adaptive radiance queries at fixed points.  Its wave kernels are
-// radiance_direct_wave.h's and radiance_sky_wave.h's waves, started per (entry, chunk) item of a pass's sample window
+// radiance_direct_wave.h's wave without and with the sky, started per (entry, chunk) item of a pass's sample window
 // (bake_kernels.h BakeStart); behind every launch, on the same stream, bake_accumulate_kernel adds the launch's chunk sums to the
 // points' records.  The selection of an adaptive pass is a stream compaction over the points -- flag and count, scan the
 // workgroups' counts, scatter -- whose result depends on the records alone.  No arithmetic of a sample is written here: a
@@ -10,7 +10,6 @@
 #include "device_path.h"
 #include "launch_dispatch.h"
 #include "radiance_direct_wave.h"
-#include "radiance_sky_wave.h"
 
 namespace rayrs {
 
@@ -18,7 +17,7 @@ template <bool COMPACT, bool EXACT, int KIND>
 __global__ void __launch_bounds__(256) bake_direct_kernel(SceneDev sc, RadianceDev rd, BakeStartDev bs, LightsDev lights, LightSlotsDev slots) {
     extern __shared__ uint32_t lds_stack[];
     const CameraDev cam{};  // (read by LIT_START_PIXEL only: never here)
-    direct_wave<COMPACT, EXACT>(BakeStart<KIND>{bs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, cam);
+    direct_wave<COMPACT, EXACT>(BakeStart<KIND>{bs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, NoSky{}, cam);
 }
 
 template <bool COMPACT, bool EXACT, int KIND>
@@ -26,7 +25,7 @@ __global__ void __launch_bounds__(256) bake_sky_kernel(SceneDev sc, RadianceDev 
                                                        SkyDev sky) {
     extern __shared__ uint32_t lds_stack[];
     const CameraDev cam{};
-    sky_wave<COMPACT, EXACT>(BakeStart<KIND>{bs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
+    direct_wave<COMPACT, EXACT>(BakeStart<KIND>{bs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
 }
 
 namespace {

@@ -1,5 +1,5 @@
 // bake_kernels.h -- the bake (include/rayrs_hip.h BAKE: rayrs_bake_*): a device-resident accumulation buffer over the caller's
-// rays or points.  Its records, the start a bake pass gives the direct and the sky wave (the third beside QueryStart and
+// rays or points.  Its records, the start a bake pass gives the direct and the group wave (the third beside QueryStart and
 // FilmStart), what bake.hip's kernels are handed, and their launch wrappers.  The scratch, the thresholds, the light table and the
 // slots are the radiance queries' (radiance_kernels.h, radiance_lit_kernels.h, radiance_direct_kernels.h).
 #pragma once
@@ -49,7 +49,7 @@ __device__ __forceinline__ void bake_entry(const BakeStartDev& bs, uint32_t e, u
     }
 }
 
-// The bake's start of radiance_direct_wave.h's and radiance_sky_wave.h's wave.  An item is (entry, chunk of the pass) in
+// The bake's start of radiance_direct_wave.h's and radiance_group_wave.h's waves.  An item is (entry, chunk of the pass) in
 // launch-local numbering, item = entry * chunks + chunk; a lane's `ray` is the point's index in the bake, so the sample's RNG key
 // is rr_path_key(seed, index_base + point, s): the key of the one-point query the contract names.
 template <int START>

@@ -1,5 +1,5 @@
 // bake_mesh.hip -- the mesh-lit bakes (include/rayrs_hip.h MESH-LIT FILMS AND BAKES): the bake's wave kernels with a mesh-light
-// group among the lights.  They are radiance_mesh_wave.h's wave, started per (entry, chunk) item of a pass's sample window
+// group among the lights.  They are radiance_group_wave.h's wave, started per (entry, chunk) item of a pass's sample window
 // (bake_kernels.h BakeStart); bake.hip's bake_accumulate_kernel follows every launch on the same stream, unchanged, and the
 // select, the status, the noise and the read are bake.hip's.  A unit of its own, as radiance_mesh.hip is beside
 // radiance_direct.hip.  No arithmetic of a sample is written here: a chunk's sum is the wave's.
@@ -8,7 +8,7 @@
 #include "device_path.h"
 #include "launch_dispatch.h"
 #include "passes_mesh_kernels.h"
-#include "radiance_mesh_wave.h"
+#include "radiance_group_wave.h"
 
 namespace rayrs {
 
@@ -17,7 +17,7 @@ __global__ void __launch_bounds__(256) bake_mesh_kernel(SceneDev sc, RadianceDev
                                                         MeshDev mesh, SkyDev sky) {
     extern __shared__ uint32_t lds_stack[];
     const CameraDev cam{};  // (read by LIT_START_PIXEL only: never here)
-    mesh_wave<COMPACT, EXACT, SKY>(BakeStart<KIND>{bs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
+    group_wave<COMPACT, EXACT, SKY>(BakeStart<KIND>{bs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
 }
 
 hipError_t launch_bake_mesh(bool compact, const SceneDev& sc, const RadianceDev& rd, const BakeStartDev& bs, const LightsDev& lights,

@@ -1,5 +1,5 @@
 // film_direct.hip -- the direct-lit films (include/rayrs_hip.h DIRECT-LIT FILMS): a second producer of a film pass's chunk sums
-// beside the path kernels of rayrs_render.  Its kernels are radiance_direct_wave.h's and radiance_sky_wave.h's waves, started per
+// beside the path kernels of rayrs_render.  Its kernels are radiance_direct_wave.h's wave without and with the sky, started per
 // (tile, pixel, chunk) item of a pass's sample window (film_direct_kernels.h FilmStart) in the numbering film.hip's
 // film_accumulate_kernel reads, which follows every launch on the same stream; and a small kernel that adds up the launch's query
 // counts and in-image pixels.  No arithmetic of a sample is written here: a chunk's sum is the waves'.
@@ -9,7 +9,6 @@
 #include "film_direct_kernels.h"
 #include "launch_dispatch.h"
 #include "radiance_direct_wave.h"
-#include "radiance_sky_wave.h"
 
 namespace rayrs {
 
@@ -17,14 +16,14 @@ template <bool COMPACT, bool EXACT>
 __global__ void __launch_bounds__(256) film_direct_kernel(SceneDev sc, RadianceDev rd, FilmStartDev fs, LightsDev lights, LightSlotsDev slots,
                                                           CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    direct_wave<COMPACT, EXACT>(FilmStart{fs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, cam);
+    direct_wave<COMPACT, EXACT>(FilmStart{fs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, NoSky{}, cam);
 }
 
 template <bool COMPACT, bool EXACT>
 __global__ void __launch_bounds__(256) film_sky_kernel(SceneDev sc, RadianceDev rd, FilmStartDev fs, LightsDev lights, LightSlotsDev slots,
                                                        SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    sky_wave<COMPACT, EXACT>(FilmStart{fs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
+    direct_wave<COMPACT, EXACT>(FilmStart{fs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
 }
 
 // One lane per item of the launch.  An item the start skipped stored no count and is not read; a pixel is counted at its first

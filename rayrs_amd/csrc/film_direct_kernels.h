@@ -1,5 +1,5 @@
 // film_direct_kernels.h -- the direct-lit films (include/rayrs_hip.h DIRECT-LIT FILMS: rayrs_film_create_direct,
-// rayrs_film_create_sky): the start a film pass gives the direct and the sky wave, what film_direct.hip's kernels are handed
+// rayrs_film_create_sky): the start a film pass gives the direct wave (and film_mesh.hip's group wave), what film_direct.hip's kernels are handed
 // beside the waves' arguments, and their launch wrappers.  The scratch, the thresholds, the light table and the slots are the
 // radiance queries' (radiance_kernels.h, radiance_lit_kernels.h, radiance_direct_kernels.h); the item numbering is the one
 // film.hip's film_accumulate_kernel reads a pass's chunk sums by.
@@ -41,7 +41,7 @@ __device__ __forceinline__ bool film_item_pixel(const FilmStartDev& fs, const Ca
     return own.in_share && row < cam.H && col < cam.W;
 }
 
-// The film's start of radiance_direct_wave.h's and radiance_sky_wave.h's wave.  A lane's `ray` is its pixel, row << 16 | col (a
+// The film's start of radiance_direct_wave.h's and radiance_group_wave.h's waves.  A lane's `ray` is its pixel, row << 16 | col (a
 // film's sides are below 65536); the RNG key and the primary ray are LIT_START_PIXEL's.
 struct FilmStart {
     static constexpr int KIND = LIT_START_PIXEL;

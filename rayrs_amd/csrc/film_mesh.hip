@@ -1,5 +1,5 @@
 // film_mesh.hip -- the mesh-lit films (include/rayrs_hip.h MESH-LIT FILMS AND BAKES): a third producer of a film pass's chunk sums
-// beside the path kernels and film_direct.hip's.  Its kernels are radiance_mesh_wave.h's wave, started per (tile, pixel, chunk)
+// beside the path kernels and film_direct.hip's.  Its kernels are radiance_group_wave.h's wave, started per (tile, pixel, chunk)
 // item of a pass's sample window (film_direct_kernels.h FilmStart); film_direct.hip's count kernel and film.hip's
 // film_accumulate_kernel follow every launch on the same stream, unchanged.  A unit of its own, as radiance_mesh.hip is beside
 // radiance_direct.hip.  No arithmetic of a sample is written here: a chunk's sum is the wave's.
@@ -8,7 +8,7 @@
 #include "device_path.h"
 #include "launch_dispatch.h"
 #include "passes_mesh_kernels.h"
-#include "radiance_mesh_wave.h"
+#include "radiance_group_wave.h"
 
 namespace rayrs {
 
@@ -16,7 +16,7 @@ template <bool COMPACT, bool EXACT, bool SKY>
 __global__ void __launch_bounds__(256) film_mesh_kernel(SceneDev sc, RadianceDev rd, FilmStartDev fs, LightsDev lights, LightSlotsDev slots,
                                                         MeshDev mesh, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    mesh_wave<COMPACT, EXACT, SKY>(FilmStart{fs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
+    group_wave<COMPACT, EXACT, SKY>(FilmStart{fs}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
 }
 
 hipError_t launch_film_mesh(bool compact, const SceneDev& sc, const RadianceDev& rd, const FilmStartDev& fs, const LightsDev& lights,

@@ -1,5 +1,5 @@
 // passes_mesh_kernels.h -- the mesh-lit films and bakes (include/rayrs_hip.h MESH-LIT FILMS AND BAKES: rayrs_film_create_mesh,
-// rayrs_bake_create_mesh): the launch wrappers of film_mesh.hip's and bake_mesh.hip's kernels, which are radiance_mesh_wave.h's
+// rayrs_bake_create_mesh): the launch wrappers of film_mesh.hip's and bake_mesh.hip's kernels, which are radiance_group_wave.h's
 // wave started by a film pass (film_direct_kernels.h FilmStart) and by a bake pass (bake_kernels.h BakeStart).  Everything else
 // of a pass -- the scratch, the item numbering, the counts, the accumulate kernels -- is the direct-lit film's and the bake's.
 #pragma once

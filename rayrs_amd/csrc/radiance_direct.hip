@@ -12,11 +12,11 @@
 
 namespace rayrs {
 
-// radiance_direct_wave.h's wave, its paths started by the queries: a batch's rays, points or pixels.
+// radiance_direct_wave.h's wave without the sky, its paths started by the queries: a batch's rays, points or pixels.
 template <bool COMPACT, bool EXACT, int START>
 __global__ void __launch_bounds__(256) radiance_direct_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    direct_wave<COMPACT, EXACT>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, cam);
+    direct_wave<COMPACT, EXACT>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, NoSky{}, cam);
 }
 
 __global__ void __launch_bounds__(256) radiance_direct_resolve_kernel(RadianceDev rd) { radiance_resolve(rd); }

@@ -44,6 +44,9 @@ RR_DEV bool direct_listed(const LightsDev& lights, const LightSlotsDev& slots, u
     return in;
 }
 
+// What the direct wave's kernels pass where the sky's are handed the sky: the lamps of the list are the only lights.
+struct NoSky {};
+
 // What a diffuse bounce at (position, normal) adds to the loop's turn, K >= 1.  The three draws b, u1, u2 are taken here.
 struct DirectBounce {
     bool shadow;  // a shadow ray Ray{position, l_s} is to be traced, worth `credit` * emit() of a listed object it meets
@@ -51,7 +54,7 @@ struct DirectBounce {
     V3 credit;    // throughput * C
     double w_next;
 };
-RR_DEV DirectBounce direct_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& rng, const LightsDev& lights) {
+RR_DEV DirectBounce direct_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& rng, const LightsDev& lights, const NoSky&) {
     const uint32_t K = lights.n;
     const double b = rng.next();
     const double u1 = rng.next();

@@ -1,36 +1,48 @@
-// radiance_direct_wave.h -- the wave of the radiance queries with direct lighting (include/rayrs_hip.h DIRECT LIGHTING), written
-// once for whoever starts its paths: radiance_direct.hip's kernels (a batch's rays, points or pixels: QueryStart) and
-// film_direct.hip's (a film pass's (tile, pixel, chunk) items: film_direct_kernels.h FilmStart).  One path per lane from its first
-// ray to its last, in registers, fused with the closest-hit walk in its resumable pieces; finished lanes are shaded, idle lanes
-// refilled from one device-wide cursor, one record or one leaf group per step.  A lane walks TWO rays per diffuse bounce, one
-// after the other: the shadow ray towards a sampled point of a light, then the continuation.  Both leave the same point, so what
-// the lane keeps while the shadow ray walks is the continuation's direction, the shadow sample's worth and whether the roulette
-// let the path go on -- not a second ray.
+// radiance_direct_wave.h -- the wave of the radiance queries with direct lighting from the lamps of the list (include/rayrs_hip.h
+// DIRECT LIGHTING) or from the lamps and the sky (SKY SAMPLING), written once for both and for whoever starts its paths: the
+// queries (radiance_direct.hip, radiance_sky.hip: a batch's rays, points or pixels, QueryStart), the film's passes
+// (film_direct.hip: (tile, pixel, chunk) items, film_direct_kernels.h FilmStart), the bake's (bake.hip) and the probes
+// (radiance_probe.hip).  Which lighting it is, the type of the `sky` argument says: SkyDev, or NoSky.  One path per lane from
+// its first ray to its last, in registers, fused with the closest-hit walk in its resumable pieces; finished lanes are shaded,
+// idle lanes refilled from one device-wide cursor, one record or one leaf group per step.  A lane walks TWO rays per diffuse
+// bounce, one after the other: the shadow ray towards a sampled point of a light, then the continuation.  Both leave the same
+// point, so what the lane keeps while the shadow ray walks is the continuation's direction, the shadow sample's worth and whether
+// the roulette let the path go on -- not a second ray.
+//
+// What the sky changes (where SKY is read, and the overload of direct_bounce the sky's type picks): the shadow ray's direction
+// may come from the sky's table (radiance_sky_table.h), a shadow ray that misses is credited the background, every diffuse bounce
+// has a shadow sample (the list may be empty, the sky is always there), and the background a path's own ray escapes to is
+// weighted by w.  p_env of the continuation is evaluated at the bounce, so the state a lane carries is the same.
 #pragma once
+#include <type_traits>
+
 #include "device_path.h"
 #include "radiance_direct_device.h"
 #include "radiance_direct_kernels.h"
+#include "radiance_sky_device.h"
 #include "radiance_wave_parts.h"
 
 namespace rayrs {
 
-// The start of sample s of ray (point, pixel) `ray`: its RNG and its first ray.  LIT_START_POINT with lights is IRRADIANCE,
-// DIRECT's virtual bounce: `first` is then its shadow sample and the weight of the first ray's meeting with a listed object.
+// The start of sample s of ray (point, pixel) `ray`: its RNG and its first ray.  LIT_START_POINT with lights (with the sky:
+// whatever K is) is IRRADIANCE, DIRECT's virtual bounce: `first` is then its shadow sample and the weight of what the first ray
+// meets (a listed object, or the sky).
 struct DirectStart {
     Rng rng;
     V3 o, d;
     DirectBounce first;
 };
-template <class START>
-RR_DEV DirectStart direct_sample_start(const START& start, const RadianceDev& rd, const LightsDev& lights, const CameraDev& cam,
-                                       uint32_t ray, uint32_t s) {
+template <class START, class SKYARG>
+RR_DEV DirectStart direct_sample_start(const START& start, const RadianceDev& rd, const LightsDev& lights, const SKYARG& sky,
+                                       const CameraDev& cam, uint32_t ray, uint32_t s) {
+    constexpr bool SKY = !std::is_same<SKYARG, NoSky>::value;
     SampleStart st = sample_start(start, rd, cam, ray, s);
     DirectBounce first;
     first.shadow = false, first.l_s = mk(0.0, 0.0, 1.0), first.credit = mk(0.0, 0.0, 0.0), first.w_next = 1.0;
     if (START::KIND == LIT_START_POINT) {  // IRRADIANCE's ray, then DIRECT's virtual bounce at the point
         const V3 n = st.d;
         st.d = cosine_direction(n, st.rng);
-        if (lights.n != 0u) first = direct_bounce(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), st.o, n, st.d, st.rng, lights);
+        if (SKY || lights.n != 0u) first = direct_bounce(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), st.o, n, st.d, st.rng, lights, sky);
     }
     return DirectStart{st.rng, st.o, st.d, first};
 }
@@ -40,10 +52,12 @@ RR_DEV DirectStart direct_sample_start(const START& start, const RadianceDev& rd
 // 2 * max_bounces + 1 of them.  A chunk's sum is made in this one lane in sample order and stored once, so no f64 sum depends on
 // which lanes did what when.  A start that SKIPS asks the cursor again in the same turn for the lanes whose items it turned
 // down, until every idle lane holds an item or the launch has none left: such an item takes no lane and stores nothing.
-template <bool COMPACT, bool EXACT, class START>
+// The sky's table is read inside direct_bounce only, by indices its searches keep inside the table.
+template <bool COMPACT, bool EXACT, class START, class SKYARG>
 RR_DEV void direct_wave(const START& start, const LaneStack& stack, const SceneDev& sc, const RadianceDev& rd, const LightsDev& lights,
-                        const LightSlotsDev& slots, const CameraDev& cam) {
+                        const LightSlotsDev& slots, const SKYARG& sky, const CameraDev& cam) {
     constexpr bool POINT = START::KIND == LIT_START_POINT;
+    constexpr bool SKY = !std::is_same<SKYARG, NoSky>::value;
     const unsigned long long n_items = start.n_items(rd);
 
     bool has = false;  // the lane holds a path: walking while tv.cur != TRAV_DONE, then finished (waiting to be shaded)
@@ -80,10 +94,17 @@ RR_DEV void direct_wave(const START& start, const LaneStack& stack, const SceneD
                 bool ended = true;
                 V3 result = light;
                 if (shadow) {  // the shadow sample's credit, then the continuation or the sample's end (the roulette's word)
-                    if (tv.best_prim != 0xffffffffu && direct_listed(lights, slots, tv.best_prim)) {
-                        const PrimRec<COMPACT> rec = load_prim<COMPACT>(sc.prims, tv.best_prim);
-                        const double* emit = sc.surfaces[rec.tag() >> 8].emit;
-                        const V3 worth = v_mul(credit, mk(emit[0], emit[1], emit[2]));
+                    const bool missed = tv.best_prim == 0xffffffffu;
+                    if (missed ? SKY : direct_listed(lights, slots, tv.best_prim)) {  // the sky's light (SKY), or a listed object's
+                        V3 source;
+                        if (SKY && missed) {
+                            source = background(sc, d);
+                        } else {
+                            const PrimRec<COMPACT> rec = load_prim<COMPACT>(sc.prims, tv.best_prim);
+                            const double* emit = sc.surfaces[rec.tag() >> 8].emit;
+                            source = mk(emit[0], emit[1], emit[2]);
+                        }
+                        const V3 worth = v_mul(credit, source);
                         if (POINT && bounce == 0u) first = worth;  // (the path has not met a surface yet)
                         else light = v_add(light, worth);
                     }
@@ -102,9 +123,9 @@ RR_DEV void direct_wave(const START& start, const LaneStack& stack, const SceneD
                         if (direct_listed(lights, slots, tv.best_prim)) e = v_scale(e, w);
                         light = v_add(light, v_mul(thr, e));
                         w = 1.0;
-                        if (diffuse && lights.n != 0u) {
+                        if (diffuse && (SKY || lights.n != 0u)) {
                             const DirectBounce db = direct_bounce(mk(surf->color[0], surf->color[1], surf->color[2]), thr, position,
-                                                                  hp.normal, ev.dir, rng, lights);
+                                                                  hp.normal, ev.dir, rng, lights, sky);
                             shadow = db.shadow, credit = db.credit, w = db.w_next;
                             if (shadow) d = db.l_s;
                         }
@@ -118,11 +139,13 @@ RR_DEV void direct_wave(const START& start, const LaneStack& stack, const SceneD
                         if (shadow) o = position, l = ev.dir, ended = false, new_ray = true;
                         else if (goes_on) o = position, d = ev.dir, ended = false, new_ray = true;
                     }
+                } else if constexpr (SKY) {
+                    result = v_add(light, v_mul(thr, v_scale(background(sc, d), w)));  // light + throughput * (background(dir) * w)
                 } else {
                     result = escape(sc, d, thr, light);
                 }
                 if (ended) {
-                    if (POINT && lights.n != 0u) result = v_add(first, result);  // L = credit + radiance(..)
+                    if (POINT && (SKY || lights.n != 0u)) result = v_add(first, result);  // L = credit + radiance(..)
                     sum = v_add(sum, result);
                     s++;
                     if (s < s_end) {
@@ -162,7 +185,7 @@ RR_DEV void direct_wave(const START& start, const LaneStack& stack, const SceneD
             }
             // ---- a new sample's start; every new ray is one Bvh::intersect call
             if (new_sample) {
-                const DirectStart st = direct_sample_start(start, rd, lights, cam, ray, s);
+                const DirectStart st = direct_sample_start(start, rd, lights, sky, cam, ray, s);
                 rng = st.rng, o = st.o, d = st.d;
                 thr = mk(1.0, 1.0, 1.0), light = mk(0.0, 0.0, 0.0);
                 bounce = 0u;

@@ -1,27 +1,34 @@
-// radiance_tree_wave.h -- the wave of the radiance queries with a mesh-light group chosen by a light tree (include/rayrs_hip.h LIGHT
-// TREE), for radiance_tree.hip's kernels (QueryStart).  It is radiance_mesh_wave.h's wave restated with this bounce and this met
-// weight -- one path per lane, two rays per diffuse bounce, the same state between them, the same three words more than the sky
-// wave's -- and what differs is this: a group-drawn direction comes from the tree's descent at the shading point
-// (radiance_tree_device.h), and a primitive met by the path's own ray is told from one word of the tree's entry table, which is
-// the entry whose path the met weight descends.
+// radiance_group_wave.h -- the wave of the radiance queries with a mesh-light group among the lights of direct lighting, written
+// once for both ways of drawing from the group (GROUP: MeshDev, include/rayrs_hip.h MESH LIGHTS, by area; TreeDev, LIGHT TREE, by
+// the tree's descent from the shading point) and for whoever starts its paths: the queries (radiance_mesh.hip, radiance_tree.hip),
+// the film's and the bake's passes (film_mesh.hip, bake_mesh.hip) and the probes (radiance_probe.hip).  It is
+// radiance_direct_wave.h's wave restated with the group's bounce -- one path per lane, two rays per diffuse bounce, the same state
+// between them -- and what differs is this: every diffuse bounce has a shadow sample (the group is never empty here), its direction
+// may come from the group's tables, a shadow ray aimed at a triangle is credited only where that very triangle is its closest
+// hit, and a listed triangle met by the path's own ray is weighted in area measure at the hit.  So a lane carries three more words
+// than the direct wave's: pc of its last diffuse bounce, and the slot its shadow ray was aimed at.  What the two groups do
+// differently is behind four overloads of radiance_mesh_device.h and radiance_tree_device.h: group_bounce, and group_met,
+// group_listed and group_met_weight for a primitive the path's own ray met (the area group tells it from one bitmap word; the
+// tree from one word of its entry table, which is the entry whose path the met weight descends).
 #pragma once
 #include "device_path.h"
 #include "radiance_direct_wave.h"
+#include "radiance_mesh_device.h"
+#include "radiance_mesh_kernels.h"
 #include "radiance_tree_device.h"
-#include "radiance_tree_kernels.h"
 
 namespace rayrs {
 
 // The start of sample s of ray (point, pixel) `ray`: its RNG and its first ray.  LIT_START_POINT is IRRADIANCE, DIRECT's virtual
 // bounce, whatever K is: `first` is its shadow sample and the weights of what the first ray meets.
-struct TreeStart {
+struct MeshStart {
     Rng rng;
     V3 o, d;
     MeshBounce first;
 };
-template <bool SKY, class START>
-RR_DEV TreeStart tree_path_start(const START& start, const RadianceDev& rd, const LightsDev& lights, const TreeDev& tree, const SkyDev& sky,
-                                 const CameraDev& cam, uint32_t ray, uint32_t s) {
+template <bool SKY, class START, class GROUP>
+RR_DEV MeshStart group_path_start(const START& start, const RadianceDev& rd, const LightsDev& lights, const GROUP& group, const SkyDev& sky,
+                                  const CameraDev& cam, uint32_t ray, uint32_t s) {
     SampleStart st = sample_start(start, rd, cam, ray, s);
     MeshBounce first;
     first.shadow = false, first.l_s = mk(0.0, 0.0, 1.0), first.credit = mk(0.0, 0.0, 0.0), first.w_next = 1.0, first.pc = 0.0;
@@ -29,17 +36,20 @@ RR_DEV TreeStart tree_path_start(const START& start, const RadianceDev& rd, cons
     if (START::KIND == LIT_START_POINT) {  // IRRADIANCE's ray, then the virtual bounce at the point, whatever K is
         const V3 n = st.d;
         st.d = cosine_direction(n, st.rng);
-        first = tree_bounce<SKY>(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), st.o, n, st.d, st.rng, lights, tree, sky);
+        first = group_bounce<SKY>(mk(1.0, 1.0, 1.0), mk(1.0, 1.0, 1.0), st.o, n, st.d, st.rng, lights, group, sky);
     }
-    return TreeStart{st.rng, st.o, st.d, first};
+    return MeshStart{st.rng, st.o, st.d, first};
 }
 
-// radiance_mesh_wave.h mesh_wave's wave and its termination argument, turn for turn.  The tree's tables are read inside
-// tree_bounce and tree_met_weight (by references the build wrote, which stay inside them whatever the point is) and, one word of
-// the entry table, at a hit (by the slot of a primitive the walk answered with).
-template <bool COMPACT, bool EXACT, bool SKY, class START>
-RR_DEV void tree_wave(const START& start, const LaneStack& stack, const SceneDev& sc, const RadianceDev& rd, const LightsDev& lights,
-                      const LightSlotsDev& slots, const TreeDev& tree, const SkyDev& sky, const CameraDev& cam) {
+// radiance_direct_wave.h direct_wave's wave and its termination argument, turn for turn: a lane that holds a path either walks
+// (its path's ray or a shadow ray) or waits to be shaded, every shade turn ends a ray, and a path has at most
+// 2 * max_bounces + 1 of them.  A chunk's sum is made in this one lane in sample order and stored once, so no f64 sum depends on
+// which lanes did what when.  The group's tables are read inside group_bounce and group_met_weight (by indices the area group's
+// search keeps inside them, by references the tree's build wrote, which stay inside them whatever the point is) and, one word of
+// the bitmap or of the entry table, at a hit (by the slot of a primitive the walk answered with).
+template <bool COMPACT, bool EXACT, bool SKY, class START, class GROUP>
+RR_DEV void group_wave(const START& start, const LaneStack& stack, const SceneDev& sc, const RadianceDev& rd, const LightsDev& lights,
+                       const LightSlotsDev& slots, const GROUP& group, const SkyDev& sky, const CameraDev& cam) {
     constexpr bool POINT = START::KIND == LIT_START_POINT;
     const unsigned long long n_items = start.n_items(rd);
     const double m_lights = (double)(lights.n + 1u + (SKY ? 1u : 0u));  // (double)M
@@ -110,17 +120,17 @@ RR_DEV void tree_wave(const START& start, const LaneStack& stack, const SceneDev
                     const Scatter ev = direct_material_evaluate(surf, hp.normal, hp.view, rng, diffuse);
                     if (ev.scatter) {
                         V3 e = mk(surf->emit[0], surf->emit[1], surf->emit[2]);
-                        const uint32_t met = tree.entry[tv.best_prim];  // the entry of a listed triangle
-                        if (met != TREE_UNLISTED) {
-                            if (lit) e = v_scale(e, tree_met_weight(tree, met, m_lights, pc, o, d, position, hp.normal));
+                        const auto met = group_met(group, tv.best_prim);  // a listed triangle: which one, where the group asks
+                        if (group_listed(group, met)) {
+                            if (lit) e = v_scale(e, group_met_weight(group, met, m_lights, pc, o, d, position, hp.normal));
                         } else if (direct_listed(lights, slots, tv.best_prim)) {
                             e = v_scale(e, w);
                         }
                         light = v_add(light, v_mul(thr, e));
                         w = 1.0, lit = false;
                         if (diffuse) {
-                            const MeshBounce mb = tree_bounce<SKY>(mk(surf->color[0], surf->color[1], surf->color[2]), thr, position,
-                                                                   hp.normal, ev.dir, rng, lights, tree, sky);
+                            const MeshBounce mb = group_bounce<SKY>(mk(surf->color[0], surf->color[1], surf->color[2]), thr, position,
+                                                                    hp.normal, ev.dir, rng, lights, group, sky);
                             shadow = mb.shadow, credit = mb.credit, w = mb.w_next, pc = mb.pc, aim = mb.aim, lit = true;
                             if (shadow) d = mb.l_s;
                         }
@@ -180,7 +190,7 @@ RR_DEV void tree_wave(const START& start, const LaneStack& stack, const SceneDev
             }
             // ---- a new sample's start; every new ray is one Bvh::intersect call
             if (new_sample) {
-                const TreeStart st = tree_path_start<SKY>(start, rd, lights, tree, sky, cam, ray, s);
+                const MeshStart st = group_path_start<SKY>(start, rd, lights, group, sky, cam, ray, s);
                 rng = st.rng, o = st.o, d = st.d;
                 thr = mk(1.0, 1.0, 1.0), light = mk(0.0, 0.0, 0.0);
                 bounce = 0u;

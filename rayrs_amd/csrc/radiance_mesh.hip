@@ -1,22 +1,22 @@
 // radiance_mesh.hip -- the radiance queries with a mesh-light group among the lights of direct lighting (include/rayrs_hip.h MESH
 // LIGHTS).  A unit of its own beside radiance_direct.hip and radiance_sky.hip: the kernels of the queries' three starts, without
-// and with the sky, the resolve and the launch.  The wave itself, and what sets it apart from the direct and the sky wave, is
-// radiance_mesh_wave.h's.
+// and with the sky, the resolve and the launch.  The wave itself, and what sets it apart from the direct wave, is
+// radiance_group_wave.h's, which radiance_tree.hip's kernels run with the tree's group.
 #include <hip/hip_runtime.h>
 
 #include "device_path.h"
 #include "launch_dispatch.h"
 #include "radiance_mesh_kernels.h"
-#include "radiance_mesh_wave.h"
+#include "radiance_group_wave.h"
 #include "radiance_wave_parts.h"
 
 namespace rayrs {
 
-// radiance_mesh_wave.h's wave, its paths started by the queries: a batch's rays, points or pixels.
+// radiance_group_wave.h's wave with the area group, its paths started by the queries: a batch's rays, points or pixels.
 template <bool COMPACT, bool EXACT, bool SKY, int START>
 __global__ void __launch_bounds__(256) radiance_mesh_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, MeshDev mesh, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    mesh_wave<COMPACT, EXACT, SKY>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
+    group_wave<COMPACT, EXACT, SKY>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
 }
 
 __global__ void __launch_bounds__(256) radiance_mesh_resolve_kernel(RadianceDev rd) { radiance_resolve(rd); }

@@ -3,7 +3,7 @@
 // densities, the sky's and the material evaluation are taken as they are (radiance_lit_device.h, radiance_sky_table.h,
 // radiance_direct_device.h); mesh_sample and p_tri are radiance_mesh_table.h's, the functions the host calls run.  No density
 // here sums over the group: a group-drawn sample is weighted in area measure at the point it drew, and the continuation at the
-// point it meets (radiance_mesh_wave.h).  All f64, unfused, in the header's operation order.
+// point it meets (radiance_group_wave.h).  All f64, unfused, in the header's operation order.
 #pragma once
 #include "device_path.h"
 #include "radiance_direct_device.h"
@@ -41,12 +41,23 @@ struct MeshBounce {
     double w_next, pc;
     uint32_t aim;  // MESH_NO_AIM: a lamp or the sky was drawn
 };
-// The three draws b, u1, u2 are taken here.  A lane that drew the group searches its prefix table on its own (one binary search
-// over global memory, then one 128-byte record); a lane that drew the sky searches the sky's; a lane that drew a lamp picks it
-// out of the kernel arguments by comparison.
-template <bool SKY>
-RR_DEV MeshBounce mesh_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& rng, const LightsDev& lights, const MeshDev& mesh,
-                              const SkyDev& sky) {
+// The group's arm of the bounce, drawn by area: the direction ls from pos to the point u1, u2 draw, its density p_tri, and the
+// slot of the triangle drawn.  One binary search of the prefix table over global memory, then one 128-byte record.
+RR_DEV uint32_t group_aim(const MeshDev& mesh, const double pos[3], double u1, double u2, double ls[3], double& p_tri) {
+    double q[3];
+    const uint32_t j = mesh_sample(mesh, u1, u2, q);
+    const MeshTri* t = mesh_tri(mesh, j);
+    const double nj[3] = {t->n[0], t->n[1], t->n[2]};
+    p_tri = mesh_aim(pos, q, nj, mesh.T, ls);
+    return t->slot;
+}
+
+// The three draws b, u1, u2 are taken here.  A lane that drew the group asks the group's own group_aim (GROUP: MeshDev, or
+// radiance_tree_device.h's TreeDev); a lane that drew the sky searches the sky's table; a lane that drew a lamp picks it out of
+// the kernel arguments by comparison.
+template <bool SKY, class GROUP>
+RR_DEV MeshBounce group_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& rng, const LightsDev& lights, const GROUP& group,
+                               const SkyDev& sky) {
     const uint32_t K = lights.n, M = K + 1u + (SKY ? 1u : 0u);
     const double m = (double)M;
     const double b = rng.next();
@@ -60,14 +71,10 @@ RR_DEV MeshBounce mesh_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& r
     out.aim = MESH_NO_AIM;
     double p_tri = 0.0;
     if (k == K) {
-        double q[3], ls[3];
-        const uint32_t j = mesh_sample(mesh, u1, u2, q);
-        const MeshTri* t = mesh_tri(mesh, j);
+        double ls[3];
         const double pos[3] = {position.x, position.y, position.z};
-        const double nj[3] = {t->n[0], t->n[1], t->n[2]};
-        p_tri = mesh_aim(pos, q, nj, mesh.T, ls);
+        out.aim = group_aim(group, pos, u1, u2, ls, p_tri);
         out.l_s = mk(ls[0], ls[1], ls[2]);
-        out.aim = t->slot;
     } else if (SKY && k == K + 1u) {
         double d[3];
         sky_sample(sky, u1, u2, d);
@@ -102,9 +109,13 @@ RR_DEV MeshBounce mesh_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& r
     return out;
 }
 
+// What the wave learns of the primitive its path's ray met: whether it is one of the group's triangles, one bitmap word.
+RR_DEV bool group_met(const MeshDev& mesh, uint32_t prim) { return mesh_listed(mesh, prim); }
+RR_DEV bool group_listed(const MeshDev&, bool met) { return met; }
+
 // The weight of a listed triangle's emission met by the path's ray Ray{o, d} at `position` = ray.point(t), where the triangle's
 // normal is `normal` (either side): the cosine arm's pc against the group's density at that point, in solid angle, over M.
-RR_DEV double mesh_met_weight(const MeshDev& mesh, double m, double pc, V3 o, V3 d, V3 position, V3 normal) {
+RR_DEV double group_met_weight(const MeshDev& mesh, bool, double m, double pc, V3 o, V3 d, V3 position, V3 normal) {
     const double p = v_mag2(v_sub(o, position)) / (rr_fabs(v_dot(normal, d)) * mesh.T);
     return p > 0.0 ? pc / (pc + p / m) : 1.0;
 }

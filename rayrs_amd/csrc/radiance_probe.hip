@@ -1,5 +1,5 @@
-// radiance_probe.hip -- SH probes (include/rayrs_hip.h SH PROBES).  A unit of its own: the direct, the sky, the mesh and the tree
-// wave (radiance_direct_wave.h, radiance_sky_wave.h, radiance_mesh_wave.h, radiance_tree_wave.h) started by the probes
+// radiance_probe.hip -- SH probes (include/rayrs_hip.h SH PROBES).  A unit of its own: the direct wave without and with the sky
+// (radiance_direct_wave.h) and the group wave with the area and the tree's group (radiance_group_wave.h), started by the probes
 // (radiance_probe_kernels.h ProbeStart: an item is one sample of one probe), and the projection behind them, which takes
 // radiance_resolve's place: every sample's direction made again from its key, the nine harmonics, and the sums in the header's
 // order.  The waves keep no accumulator of the projection: they stand at 200 to 230 VGPRs as they are.
@@ -8,10 +8,8 @@
 #include "device_path.h"
 #include "launch_dispatch.h"
 #include "radiance_direct_wave.h"
-#include "radiance_mesh_wave.h"
+#include "radiance_group_wave.h"
 #include "radiance_probe_kernels.h"
-#include "radiance_sky_wave.h"
-#include "radiance_tree_wave.h"
 #include "radiance_wave_parts.h"
 
 namespace rayrs {
@@ -19,25 +17,25 @@ namespace rayrs {
 template <bool COMPACT, bool EXACT>
 __global__ void __launch_bounds__(256) probe_direct_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    direct_wave<COMPACT, EXACT>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, cam);
+    direct_wave<COMPACT, EXACT>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, NoSky{}, cam);
 }
 
 template <bool COMPACT, bool EXACT>
 __global__ void __launch_bounds__(256) probe_sky_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    sky_wave<COMPACT, EXACT>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
+    direct_wave<COMPACT, EXACT>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
 }
 
 template <bool COMPACT, bool EXACT, bool SKY>
 __global__ void __launch_bounds__(256) probe_mesh_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, MeshDev mesh, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    mesh_wave<COMPACT, EXACT, SKY>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
+    group_wave<COMPACT, EXACT, SKY>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, mesh, sky, cam);
 }
 
 template <bool COMPACT, bool EXACT, bool SKY>
 __global__ void __launch_bounds__(256) probe_tree_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, TreeDev tree, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    tree_wave<COMPACT, EXACT, SKY>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, tree, sky, cam);
+    group_wave<COMPACT, EXACT, SKY>(ProbeStart{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, tree, sky, cam);
 }
 
 // One thread per (probe, chunk) pair of the round: C[k][ch] from zero, for each sample of the chunk in sample order

@@ -1,5 +1,5 @@
 // radiance_probe_kernels.h -- SH probes (include/rayrs_hip.h SH PROBES: rayrs_scene_probes and its _launch form): the start a
-// probe call gives the direct, the sky, the mesh and the tree wave (the fourth beside QueryStart, FilmStart and BakeStart), what
+// probe call gives the direct and the group wave (the fourth beside QueryStart, FilmStart and BakeStart), what
 // radiance_probe.hip's projection kernels are handed, and the launch wrappers.  The wave's scratch, the thresholds, the light
 // table, the slots and the groups are the radiance queries' (radiance_kernels.h, radiance_lit_kernels.h,
 // radiance_direct_kernels.h, radiance_sky_kernels.h, radiance_mesh_kernels.h, radiance_tree_kernels.h).
@@ -66,8 +66,8 @@ struct ProbeStart {
 
 // The wave of a probe launch on a grid of at most cu_count * RADIANCE_BLOCKS_PER_CU workgroups: every item's L_s into rd.partial
 // and its query count into rd.partial_queries.  rd.chunk = 1, rd.chunks = rd.samples, rd.a the launch's points, rd.b unread.
-// tree != nullptr: the tree wave; else mesh != nullptr: the mesh wave; else with_sky: the sky wave; else the direct wave (an empty
-// list: the unlit bits).  with_sky also picks the mesh and the tree wave's sky instance.
+// tree != nullptr: the group wave with the tree's group; else mesh != nullptr: with the area group; else the direct wave, with
+// the sky where with_sky (without it, an empty list: the unlit bits).  with_sky also picks the group wave's sky instance.
 hipError_t launch_probe_wave(bool compact, const SceneDev& sc, const RadianceDev& rd, const LightsDev& lights, const LightSlotsDev& slots,
                              const MeshDev* mesh, const TreeDev* tree, const SkyDev& sky, bool with_sky, int cu_count, hipStream_t stream);
 // Behind it on the same stream, one round: probe_project_kernel, a thread per pair (its direction made again from the key, the

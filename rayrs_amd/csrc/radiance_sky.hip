@@ -1,22 +1,21 @@
 // radiance_sky.hip -- the radiance queries with the sky among the lights of direct lighting (include/rayrs_hip.h SKY SAMPLING).
 // A unit of its own beside radiance_direct.hip: the kernels of the queries' three starts, the resolve and the launch.  The wave
-// itself, and what sets it apart from the direct wave, is radiance_sky_wave.h's, which the sky-lit film's kernels
-// (film_direct.hip) run with a start of their own.
+// itself is radiance_direct_wave.h's, handed the sky; what the sky changes in it is said there.
 #include <hip/hip_runtime.h>
 
 #include "device_path.h"
 #include "launch_dispatch.h"
+#include "radiance_direct_wave.h"
 #include "radiance_sky_kernels.h"
-#include "radiance_sky_wave.h"
 #include "radiance_wave_parts.h"
 
 namespace rayrs {
 
-// radiance_sky_wave.h's wave, its paths started by the queries: a batch's rays, points or pixels.
+// radiance_direct_wave.h's wave with the sky, its paths started by the queries: a batch's rays, points or pixels.
 template <bool COMPACT, bool EXACT, int START>
 __global__ void __launch_bounds__(256) radiance_sky_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    sky_wave<COMPACT, EXACT>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
+    direct_wave<COMPACT, EXACT>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, sky, cam);
 }
 
 __global__ void __launch_bounds__(256) radiance_sky_resolve_kernel(RadianceDev rd) { radiance_resolve(rd); }

@@ -24,8 +24,8 @@ RR_DEV double sky_mix_density(const LightsDev& lights, const SkyDev& sky, V3 pos
 
 // What a diffuse bounce at (position, normal) adds to the loop's turn, K >= 0.  The three draws b, u1, u2 are taken here.  A lane
 // that drew the sky searches the table on its own (two binary searches over global memory); a lane that drew a lamp picks it out
-// of the kernel arguments by comparison, as direct_bounce does.
-RR_DEV DirectBounce sky_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& rng, const LightsDev& lights, const SkyDev& sky) {
+// of the kernel arguments by comparison, as the lamps' own direct_bounce does.
+RR_DEV DirectBounce direct_bounce(V3 albedo, V3 thr, V3 position, V3 n, V3 l, Rng& rng, const LightsDev& lights, const SkyDev& sky) {
     const uint32_t K = lights.n, M = K + 1u;
     const double b = rng.next();
     const double u1 = rng.next();

@@ -1,21 +1,22 @@
 // radiance_tree.hip -- the radiance queries with a mesh-light group whose triangles are chosen by a light tree (include/rayrs_hip.h
 // LIGHT TREE).  A unit of its own beside radiance_mesh.hip: the kernels of the queries' three starts, without and with the sky,
-// the resolve and the launch.  The wave, and what sets it apart from the mesh wave, is radiance_tree_wave.h's.
+// the resolve and the launch.  The wave is radiance_group_wave.h's, the one radiance_mesh.hip's kernels run;
+// what the tree's group does differently is radiance_tree_device.h's.
 #include <hip/hip_runtime.h>
 
 #include "device_path.h"
 #include "launch_dispatch.h"
 #include "radiance_tree_kernels.h"
-#include "radiance_tree_wave.h"
+#include "radiance_group_wave.h"
 #include "radiance_wave_parts.h"
 
 namespace rayrs {
 
-// radiance_tree_wave.h's wave, its paths started by the queries: a batch's rays, points or pixels.
+// radiance_group_wave.h's wave with the tree's group, its paths started by the queries: a batch's rays, points or pixels.
 template <bool COMPACT, bool EXACT, bool SKY, int START>
 __global__ void __launch_bounds__(256) radiance_tree_kernel(SceneDev sc, RadianceDev rd, LightsDev lights, LightSlotsDev slots, TreeDev tree, SkyDev sky, CameraDev cam) {
     extern __shared__ uint32_t lds_stack[];
-    tree_wave<COMPACT, EXACT, SKY>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, tree, sky, cam);
+    group_wave<COMPACT, EXACT, SKY>(QueryStart<START>{}, lane_stack(lds_stack, rd.spill, sc), sc, rd, lights, slots, tree, sky, cam);
 }
 
 __global__ void __launch_bounds__(256) radiance_tree_resolve_kernel(RadianceDev rd) { radiance_resolve(rd); }

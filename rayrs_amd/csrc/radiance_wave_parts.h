@@ -1,5 +1,5 @@
 // radiance_wave_parts.h -- what is the same text in the waves of radiance.hip, radiance_lit.hip, radiance_direct_wave.h and
-// radiance_sky_wave.h, written once: the queries' start (which item is which ray and chunk), the start of a sample before the
+// radiance_group_wave.h, written once: the queries' start (which item is which ray and chunk), the start of a sample before the
 // lighting has its say, and the body of the four resolve kernels, which keep their names and their units.
 #pragma once
 #include "device_path.h"

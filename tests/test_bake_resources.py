@@ -1,6 +1,6 @@
 """The resources of the bake's kernels, from the kernel metadata hipcc writes for gfx950 (no GPU needed).
 
-bake.hip's wave kernels are radiance_direct_wave.h's and radiance_sky_wave.h's waves with a third start (bake_kernels.h
+bake.hip's wave kernels are radiance_direct_wave.h's wave, without and with the sky, with a third start (bake_kernels.h
 BakeStart): they must keep what the waves have in radiance_direct.hip, radiance_sky.hip and film_direct.hip -- nothing in scratch,
 and registers that allow two waves per SIMD (512 per lane and SIMD: at most 256 a wave).  Only the metadata is read."""
 import os
